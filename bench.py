@@ -18,7 +18,12 @@ all-gather), weak scaling (per-GPU batch fixed).
 fwd + bwd of the cross-entropy on the image tokens (train.py:150-152) + Adam, bf16 autocast for the library GEMMs, tokens/s.
 --workload e2e (BASELINE configs[4]): frozen VQ-SEG + VQ-IMG encode -> tokens -> the same transformer step, samples/s.
 
-Rank 0 prints ONE JSON line; besides the driver's contract it carries
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the result
+line (metric, value, unit, higher_is_better, dtype, ms_per_step and the run's configuration).  --dump-outputs DIR: what the timed path
+returned in its last timed step, as DIR/<name>.npy (float32 / float64, 64 MB at most; seeded fixed samples of the larger arrays), from inputs
+that are identical from run to run with the same arguments -- two builds compare output for output.
+
+--full adds everything beyond the headline figure.  Rank 0 prints ONE JSON line; with --full it also carries
   "roofline":     the dominant kernel timed live with HIP events on the launch stream inside the timed steps, against the bf16
                   MFMA peak (vq: the 3x3 128->128 conv at 256^2, fwd + dgrad launches, per loader population and launch-weighted
                   -- in training every launch is prologue-free since round 3; transformer / e2e: the causal-attention forward
@@ -27,8 +32,9 @@ Rank 0 prints ONE JSON line; besides the driver's contract it carries
                   "step_traffic_bytes" / "step_traffic_over_algorithmic" / "step_traffic_groupnorm_share": what a whole step moves -- both from the
                   committed rocprofv3 --pmc passes over this very command (tools/step_traffic.sh -> profiles/r06_step_traffic.json; a
                   profiled run cannot also be the timed one);
-  "cpu_baseline": the reference itself where a checkout exists (MAS_REFERENCE_ROOT or /root/reference: kind "reference"), else the CPU
-                  oracle (oracle/vq_oracle.py, a port of the reference's arithmetic: kind "port" -- the GPU box has no checkout), timed
+  "encoder_stack": Encoder.forward of the benched batch timed on its own after the timed steps, against the HBM and MFMA rooflines;
+  "cpu_baseline": the reference itself where MAS_REFERENCE_ROOT names a checkout of it (kind "reference"), else the CPU
+                  oracle (oracle/vq_oracle.py, a port of the reference's arithmetic: kind "port"), timed
                   on this host's cores on a bounded sample (rank 0, N=1, vq workload only);
   "also":         (vq workload, N=1) compact results of short `--workload transformer` and `--workload e2e` runs (BASELINE configs
                   4 and 5) made right after the headline measurement, so that they carry the same driver clock; --no-also skips them.
@@ -60,7 +66,7 @@ SEG_CFG = dict(ddconfig=dict(z_channels=256, in_channels=159, out_channels=159, 
                n_embed=256, embed_dim=256, init_steps=3000, reservoir_size=12500)    # conf/seg_config.yaml:13-32
 TR_CFG = dict(num_layers=24, hidden_dim=1024, num_attn_heads=16, image_vocab_size=8192, seg_vocab_size=256,
               text_vocab_size=49408 + 256, image_tokens_per_dim=32, seg_tokens_per_dim=16, text_length=256)
-PEAK_BF16_TFLOPS = 2500.0      # dense MFMA bf16 peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0      # dense MFMA bf16 peak of the MI355X (vendor figure)
 # what v_mfma_f32_32x32x16_bf16 from registers alone sustains on RANDOM bf16 operands on this part: the package power limit holds such a
 # loop at 1.865 GHz (constant operands: 2477 TFLOP/s at 2.386 GHz) -- measured, profiles/r05_energy_budget.txt (tools/probes/mfma_power.hip)
 RANDOM_DATA_MFMA_CEILING_TFLOPS = 1890.0
@@ -88,6 +94,11 @@ def parse():
                     help="mas: mas_hip.optim.Adam (the same update as torch.optim.Adam, every parameter in one launch; tests/test_gpu_adam.py); "
                          "torch: torch.optim.Adam(fused=True); torch-default: torch.optim.Adam(params, lr, betas) exactly as the reference's "
                          "train.py:61 constructs it (torch's default foreach implementation)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / clock / traffic figures, the encoder stack, "
+                         "the CPU baseline and (vq, N=1) the short transformer / e2e runs under 'also'; the --no-* options below apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-batch", type=int, default=2)
     ap.add_argument("--cpu-baseline-all-cores", action="store_true",
@@ -103,10 +114,10 @@ def parse():
 # CPU baseline (vq workload)
 # --------------------------------------------------------------------------------------------------------------------
 def _reference_root():
-    """the reference checkout, if this machine has one (MAS_REFERENCE_ROOT, else /root/reference): the GPU box has none"""
-    for r in (os.environ.get("MAS_REFERENCE_ROOT"), "/root/reference"):
-        if r and os.path.isfile(os.path.join(r, "models", "vqvae.py")):
-            return r
+    """the reference checkout MAS_REFERENCE_ROOT names, if it holds one"""
+    r = os.environ.get("MAS_REFERENCE_ROOT")
+    if r and os.path.isfile(os.path.join(r, "models", "vqvae.py")):
+        return r
     return None
 
 
@@ -452,6 +463,40 @@ def _emit(out):
     print(json.dumps(out), flush=True)
 
 
+_DUMP_BYTES = 64 * 2 ** 20
+_ARRAY_SAMPLE = 8 * 2 ** 20          # elements of one dumped output at most (a seeded fixed sample of a larger one)
+_PARAM_SAMPLE = 2 * 2 ** 20          # parameter elements dumped (seeded fixed sample of all parameters, concatenated in model order)
+
+
+def _sample(t, k, seed):
+    """t flattened, or a seeded fixed sample of up to k of its elements (k draws, repeats dropped, ascending index order) when it has more"""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= k:
+        return flat
+    idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), size=k))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def _dump_outputs(out_dir, arrays, params):
+    """--dump-outputs: `arrays` (name -> tensor, the last timed step's outputs; integer tokens are exact in float32) plus the trained
+    parameters as a per-parameter float64 sum and a seeded fixed sample, to out_dir/<name>.npy"""
+    import numpy as np
+    params = [p.detach() for p in params]
+    arrays = {k: (_sample(t, _ARRAY_SAMPLE, seed=2 + i) if t.numel() > _ARRAY_SAMPLE else t) for i, (k, t) in enumerate(arrays.items())}
+    arrays["param_sums"] = torch.stack([p.double().sum() for p in params])
+    arrays["param_sample"] = _sample(torch.cat([p.float().reshape(-1) for p in params]), _PARAM_SAMPLE, seed=1)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        a = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        total += a.nbytes
+        if total > _DUMP_BYTES:
+            raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {_DUMP_BYTES}-byte budget at '{name}'")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _par(world, args, ddp):
     return f"dp{world}" + ((" (DistributedDataParallel" if args.dp == "ddp" else " (mas_hip.dp.GradReducer: 128 MiB flat buckets" + (" crossing the links as bf16," if args.grad_dtype == "bf16" else ","))
                            + " RCCL all-reduce overlapped with backward)" if ddp else "")
@@ -495,7 +540,9 @@ def run_vq(args):
         else:
             launch()
 
-    ops.set_launch_hook(hook)
+    if args.full:
+        ops.set_launch_hook(hook)
+    last = {}
 
     def step():
         rec, q = net(x)
@@ -507,10 +554,12 @@ def run_vq(args):
         # the reference's own set_to_none behaviour; with the reducer too since round 5 (its buckets are then flattened by one batched copy
         # each -- keeping .grad a view of the bucket made autograd ADD into it: 345 in-place add launches per step, +1.5 ms)
         opt.zero_grad(set_to_none=reducer is None or _REDUCER_SET_TO_NONE)
+        if args.dump_outputs:
+            last.update(rec=rec.detach(), q_loss=q.detach(), loss=loss.detach())
         return loss
 
     torch.cuda.reset_peak_memory_stats(dev)
-    cp = _ClockPower(dev) if rank == 0 else None
+    cp = _ClockPower(dev) if rank == 0 and args.full else None
 
     def on_start(on):
         dom["on"] = on
@@ -522,6 +571,9 @@ def run_vq(args):
     ops.set_launch_hook(None)
     peak_gib = torch.cuda.max_memory_allocated(dev) / 2 ** 30
     spread = _replica_spread(model, ddp)
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, last, model.parameters())
+        last.clear()
 
     if rank == 0:
         value = batch * world * args.steps / dt
@@ -572,7 +624,7 @@ def run_vq(args):
                                "algorithmic_gflop_per_launch": round(flops / 1e9, 1),
                                "algorithmic_hbm_gbs": round(bytes_ / (avg_ms * 1e-3) / 1e9, 1),
                                "hbm_frac": round(bytes_ / (avg_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
-        if not args.no_encoder_stack:
+        if args.full and not args.no_encoder_stack:
             out["encoder_stack"] = _encoder_stack(model, x, batch, args.dtype)
         if "roofline" in out:
             st = _step_traffic()
@@ -608,9 +660,9 @@ def run_vq(args):
             out["roofline"]["random_data_mfma_ceiling_tflops"] = RANDOM_DATA_MFMA_CEILING_TFLOPS
             out["roofline"]["frac_of_random_data_mfma_ceiling"] = round(ach / RANDOM_DATA_MFMA_CEILING_TFLOPS, 4)
             out["roofline"]["random_data_mfma_ceiling_source"] = "profiles/r05_energy_budget.txt (tools/probes/mfma_power.hip, >= 5 s loops, hwmon-sampled)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_batch, all_cores=args.cpu_baseline_all_cores)
-        if world == 1 and not args.no_also and os.environ.get("MAS_BENCH_ALSO", "1") == "1":
+        if args.full and world == 1 and not args.no_also and os.environ.get("MAS_BENCH_ALSO", "1") == "1":
             del model, net, opt, x                               # free the HBM the other workloads need
             torch.cuda.empty_cache()
             out["also"] = _also_workloads()
@@ -632,7 +684,7 @@ def _also_workloads(budget_s=240):
     for wl, extra in (("transformer", ["--steps", "12", "--warmup", "6"]), ("e2e", ["--steps", "3", "--warmup", "2"])):
         t0 = time.perf_counter()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wl, "--gpus", "1", "--no-cpu-baseline"] + extra,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", wl, "--gpus", "1", "--full", "--no-cpu-baseline"] + extra,
                                capture_output=True, text=True, timeout=budget_s)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             d = json.loads(line[-1])
@@ -716,7 +768,9 @@ def run_transformer(args, e2e):
         att["ev"].append((e0, e1, qkv.shape[0]))
         return r
 
-    ops._CausalAttention.forward = staticmethod(timed_fwd)
+    if args.full:
+        ops._CausalAttention.forward = staticmethod(timed_fwd)
+    last = {}
 
     def step():
         from token_data import tokenize_batch
@@ -735,6 +789,10 @@ def run_transformer(args, e2e):
                     loss.backward()
             else:
                 loss.backward()
+            if args.dump_outputs and m0 + micro >= batch:     # the step's last micro-batch
+                last.update(logits=logits.detach(), loss=loss.detach())
+                if e2e:
+                    last.update(image_tokens=it.detach(), seg_tokens=st.detach())
         if reducer is not None:
             reducer.finish()
         opt.step()
@@ -744,6 +802,9 @@ def run_transformer(args, e2e):
     dt, final_loss = _timed(step, args, ddp, dev, on_start=lambda on: att.__setitem__("on", on))
     ops._CausalAttention.forward = staticmethod(orig)
     spread = _replica_spread(model, ddp)
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, last, model.parameters())
+        last.clear()
     if rank == 0:
         samples = batch * world * args.steps
         gf = TR_FWD_GFLOP_PER_SAMPLE * 3

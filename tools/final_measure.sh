@@ -6,9 +6,9 @@ O=$R/gpurun_out/final; mkdir -p $O
 cd $R
 timeout 1800 python -m pytest tests -m gpu -q --timeout 900 2>&1 | tail -3 > $O/pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
-timeout 600 python bench.py --workload transformer > $O/bench_transformer.json 2> $O/bench_transformer.err
-timeout 600 python bench.py --workload e2e > $O/bench_e2e.json 2> $O/bench_e2e.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --workload transformer --full > $O/bench_transformer.json 2> $O/bench_transformer.err
+timeout 600 python bench.py --workload e2e --full > $O/bench_e2e.json 2> $O/bench_e2e.err
 [ -x tools/probes/mfma_peak ] || bash tools/probes/build.sh > /dev/null 2>&1
 KB="timeout 100 python tools/kbench.py"
 {

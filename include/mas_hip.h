@@ -265,6 +265,27 @@ int mas_attn_causal_fwd(const void* q, const void* k, const void* v, void* o, fl
 int mas_attn_causal_bwd(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
                         int dtype, int B, int H, int S, int hd, float scale, void* stream);
 
+/* ---- Dropout  (reference models/transformer.py:32,92 attn_drop on the probabilities; models/modules.py:99,127 ResnetBlock dropout)
+ * Generator: Philox4x32-10 (Random123), make-a-scene_amd/csrc/mas_philox.h.  seed: DEVICE pointer to two int64 {seed, offset}, read by
+ * the kernels (no host synchronisation, safe under graph capture).  key = (lo32(seed), hi32(seed)).  Each call yields 8 16-bit values;
+ * slot j is bits 16 (j & 1) .. +15 of output word j >> 1.  An element is kept iff its value >= t = round(p * 65536) (p quantised to
+ * 1/65536), kept values are scaled by 65536 / (65536 - t); p = 1 (t = 65536) gives zeros.  p in [0, 1].
+ *   attention (b, h, query, key), bh = b*H + h:  counter = (key >> 2, query >> 1, bh, lo32(offset)),  slot = 4 (query & 1) + (key & 3)
+ *     -- one call per (bh, 4-query block, 4-key block, query half), independent of any kernel's tiling.
+ *   element-wise, flat index i (memory order):    counter = (lo32(i >> 3), hi32(i >> 3), 0, lo32(offset)),  slot = i & 7.
+ * mas_attn_causal_fwd_drop / _bwd_drop: mas_attn_causal_fwd / _bwd with O = (P o Z s) V; dV = (P o Z s)^T dO, dS = P o (dP o Z s - D)
+ * scale; lse and D are those of the undropped P.  The backward regenerates Z: nothing [S, S] is stored.  Same envelope as the plain
+ * entries (bf16 head width 128 forward: the generic kernel).
+ * mas_attn_dropout_mask: keep[b, h, query, key] (uint8 0 / 1, [B,H,S,S] contiguous) for tests and debugging.
+ * mas_dropout_apply: y = x o Z s over n elements (x, y 16-byte aligned; y may be x); its own backward with the same seed.            */
+int mas_attn_causal_fwd_drop(const void* q, const void* k, const void* v, void* o, float* lse, int dtype, int B, int H,
+                             int S, int hd, int ld_q, int ld_k, int ld_v, long long q_bs, long long k_bs, long long v_bs,
+                             float scale, float p, const int64_t* seed, void* stream);
+int mas_attn_causal_bwd_drop(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
+                             int dtype, int B, int H, int S, int hd, float scale, float p, const int64_t* seed, void* stream);
+int mas_attn_dropout_mask(const int64_t* seed, int B, int H, int S, float p, uint8_t* keep, void* stream);
+int mas_dropout_apply(const void* x, void* y, long long n, int dtype, float p, const int64_t* seed, void* stream);
+
 /* ---- single-head spatial self-attention core of AttnBlock  (replaces the two torch.bmm + softmax of models/modules.py:174-187 and
  * their autograd).  qkv: [N, S, 3C] bf16, q | k | v stacked on the channel axis (the fused 1x1 projection, NHWC with S = h*w);
  * out [N, S, C] = softmax_keys(q k^T * C^-1/2) v;  lse [N, S] fp32 (log-sum-exp of the scaled scores; may be NULL when no backward

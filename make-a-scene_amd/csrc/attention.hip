@@ -12,6 +12,7 @@
 //                                        score accumulators: lane = query, registers = keys)
 // fp32 online softmax (running max / sum per query), bf16 or exact-fp32 MFMA operands (template T).
 #include "mas_common.h"
+#include "mas_philox.h"
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -29,6 +30,23 @@ struct AttnParams {
     float scale;
     int lpt;                        // grid = (B * H, tiles) instead of (tiles, B * H): see fa_lpt()
 };
+// the DROP = true kernels take the parameters with the dropout fields appended; the DROP = false ones keep the plain struct, so their
+// kernel argument segment (and with it every instruction, down to the offsets of the hidden arguments) is the one they always had
+struct AttnDropParams : AttnParams {
+    const long long* drop_seed;     // device {seed, offset} (mapping: include/mas_hip.h, "Dropout")
+    unsigned drop_t;                // keep iff the score's 16-bit value >= drop_t
+    float drop_scale;               // 65536 / (65536 - drop_t), 0 for p = 1
+};
+template <bool DROP> using FaFwdArgs = typename std::conditional<DROP, AttnDropParams, AttnParams>::type;
+
+// Dropout of P inside the flash kernels (template flag DROP; DROP = false compiles to the kernels as they were).  The keep mask is a pure
+// function of (seed, offset, b*H + h, query, key): the backward kernels regenerate it, nothing [S,S] is stored.  The scale of the kept
+// probabilities goes into the forward's final 1/l and the dkv kernel's dV store; dP takes it per score.
+struct FaDrop { unsigned s0, s1, off, t; float sc; };
+__device__ __forceinline__ FaDrop fa_drop(const long long* seed, unsigned t, float sc) {
+    const unsigned long long sd = (unsigned long long)seed[0], of = (unsigned long long)seed[1];
+    return FaDrop{(unsigned)sd, (unsigned)(sd >> 32), (unsigned)of, t, sc};
+}
 
 // Causal attention work per work-group grows linearly with its tile index, and the grid (12 tiles x 128 heads at S = 1536, B = 8) is
 // 1.5 rounds of the 1024 resident work-groups.  With the tile index in blockIdx.x the dispatcher hands out heavy and light work-groups
@@ -37,8 +55,8 @@ struct AttnParams {
 // a head's work-groups all land on XCD (head % 8): its K / V stay in one L2 (49.0 -> 46.2 ms per MakeAScene step, profiles/r03_attn_lpt.txt).
 static int fa_lpt() { return 1; }
 
-template <typename T, int HD>
-__global__ __launch_bounds__(NT) void attn_causal_fwd_kernel(AttnParams p) {
+template <typename T, int HD, bool DROP = false>
+__global__ __launch_bounds__(NT) void attn_causal_fwd_kernel(FaFwdArgs<DROP> p) {
     using V8 = typename Vec8<T>::type;
     constexpr int EPU = 16 / (int)sizeof(T);
     constexpr int DT = HD < 32 ? 32 : HD;       // O^T rows padded to a 32-row MFMA tile
@@ -138,6 +156,15 @@ __global__ __launch_bounds__(NT) void attn_causal_fwd_kernel(AttnParams p) {
         for (int i = 0; i < NMI; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
+        if constexpr (DROP) {                   // registers 4j .. 4j+3 = keys k0 + 8j + 4g + 0..3: one Philox call each
+            const FaDrop dr = fa_drop(p.drop_seed, p.drop_t, p.drop_scale);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned km = mas_attn_keep_q(dr.s0, dr.s1, dr.off, bh, query, k0 + 8 * j + 4 * g, dr.t);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[4 * j + e] = ((km >> e) & 1) ? s[4 * j + e] : 0.0f;
+            }
+        }
         // ---- O^T += V^T . P^T : the B operand is the probabilities themselves.  MFMA step t pairs element j of
         // lane group g with key(t,g,j) = 16t + 8(j>>2) + 4g + (j&3) -- exactly the key owned by accumulator
         // register 8t+j -- so P needs no shuffle; V^T is read with the same key permutation (two 4-key runs).
@@ -159,7 +186,8 @@ __global__ __launch_bounds__(NT) void attn_causal_fwd_kernel(AttnParams p) {
 
     // ---- normalise and store: lane = query, accumulator rows = head dims -------------------------------
     if (query < p.S) {
-        const float inv = 1.0f / l;
+        float inv = 1.0f / l;
+        if constexpr (DROP) inv *= p.drop_scale;
         T* dst = reinterpret_cast<T*>(p.o) + ((size_t)b * p.S + query) * ((size_t)p.H * HD) + (size_t)h * HD;
 #pragma unroll
         for (int i = 0; i < NMI; ++i)
@@ -402,7 +430,9 @@ __device__ long long g_fa_trace[32];
 #define FA_T(i) do { } while (0)
 #define FA_FORCE(x) do { } while (0)
 #endif
-__global__ __launch_bounds__(NT, 4) void attn_causal_fwd_bf16_v2_kernel(AttnParams p) {
+// (DROP: the Philox work does not fit 128 VGPRs without scratch; 3 work-groups per CU, <= 168 VGPRs)
+template <bool DROP>
+__global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kernel(FaFwdArgs<DROP> p) {
     using T = bf16_t;
 #ifdef FA_TRACE
     const bool fa_tr = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 192;
@@ -584,6 +614,17 @@ __global__ __launch_bounds__(NT, 4) void attn_causal_fwd_bf16_v2_kernel(AttnPara
 #pragma unroll
                     for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
             }
+            if constexpr (DROP) {                                   // after the row sum: l and lse are those of the undropped P
+                const FaDrop dr = fa_drop(p.drop_seed, p.drop_t, p.drop_scale);
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const unsigned km = mas_attn_keep_q(dr.s0, dr.s1, dr.off, bh, query, k0 + sub * 32 + 8 * j + 4 * g, dr.t);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) s[sub][4 * j + e] = ((km >> e) & 1) ? s[sub][4 * j + e] : 0.0f;
+                    }
+            }
             FA_FORCE(l);
             FA_FORCE(s[1][15]);
             FA_T(3);                                                // mask + softmax (+ rescale)
@@ -621,7 +662,8 @@ __global__ __launch_bounds__(NT, 4) void attn_causal_fwd_bf16_v2_kernel(AttnPara
     }
 
     if (query < p.S) {                               // lane = query, accumulator rows = head dims (4 consecutive per register quad)
-        const float inv = 1.0f / l;
+        float inv = 1.0f / l;
+        if constexpr (DROP) inv *= p.drop_scale;
         T* dst = reinterpret_cast<T*>(p.o) + ((size_t)b * p.S + query) * ((size_t)p.H * HD) + (size_t)h * HD;
 #pragma unroll
         for (int i = 0; i < NMI; ++i)
@@ -651,11 +693,12 @@ __global__ __launch_bounds__(NT, 4) void attn_causal_fwd_bf16_v2_kernel(AttnPara
 extern "C" int mas_fa_trace(long long* out32) { return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_fa_trace), sizeof(long long) * 32); }
 namespace {
 #endif
-int launch_fwd_fast_v2(const AttnParams& p, hipStream_t s) {
-    AttnParams q = p;
+template <bool DROP>
+int launch_fwd_fast_v2(const AttnDropParams& p, hipStream_t s) {
+    FaFwdArgs<DROP> q = p;
     q.lpt = fa_lpt();
     const dim3 grid = q.lpt ? dim3(p.B * p.H, mas_cdiv(p.S, QT)) : dim3(mas_cdiv(p.S, QT), p.B * p.H);
-    hipLaunchKernelGGL(attn_causal_fwd_bf16_v2_kernel, grid, dim3(NT), F2_LDS, s, q);
+    hipLaunchKernelGGL(attn_causal_fwd_bf16_v2_kernel<DROP>, grid, dim3(NT), F2_LDS, s, q);
     MAS_CHECK_LAUNCH("attn_causal_fwd_v2");
     return MAS_OK;
 }
@@ -699,6 +742,12 @@ struct AttnBwdParams {
     float scale;
     int lpt;                        // (see AttnParams)
 };
+struct AttnBwdDropParams : AttnBwdParams {      // (see AttnDropParams)
+    const long long* drop_seed;
+    unsigned drop_t;
+    float drop_scale;
+};
+template <bool DROP> using FaBwdArgs = typename std::conditional<DROP, AttnBwdDropParams, AttnBwdParams>::type;
 
 template <typename T, int HD>
 __global__ __launch_bounds__(NT) void attn_bwd_delta_kernel(AttnBwdParams p) {
@@ -747,8 +796,8 @@ __device__ __forceinline__ typename Vec8<T>::type ld_perm(const T* trow, int t, 
     return v;
 }
 
-template <typename T, int HD>
-__global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(AttnBwdParams p) {
+template <typename T, int HD, bool DROP = false>
+__global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(FaBwdArgs<DROP> p) {
     using V8 = typename Vec8<T>::type;
     constexpr int EPU = 16 / (int)sizeof(T);
     constexpr int DT = HD < 32 ? 32 : HD, NKK = HD / 16, NMI = DT / 32;
@@ -808,6 +857,21 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(AttnBwdParams p) {
             mma16(s, ld8<T>(&qrow[l31 * RS + kk * 16 + g * 8]), kf[kk]);
             mma16(dp, ld8<T>(&grow[l31 * RS + kk * 16 + g * 8]), vf[kk]);
         }
+        if constexpr (DROP) {                       // registers 4j .. 4j+3 = queries q0 + 8j + 4g + 0..3: two Philox calls each
+            const FaDrop dr = fa_drop(p.drop_seed, p.drop_t, p.drop_scale);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned km = mas_attn_keep_k(dr.s0, dr.s1, dr.off, bh, key, q0 + 8 * j + 4 * g, dr.t);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * j + e, qi = acc_row(lane, r), query = q0 + qi;
+                    const bool ok = (key <= query) && (query < p.S) && (key < p.S), kp = (km >> e) & 1;
+                    const float pv = ok ? __expf(s[r] * p.scale - s_lse[qi]) : 0.0f;
+                    s[r] = kp ? pv : 0.0f;                                              // (P o Z)[query][key]; dV takes the scale at the store
+                    dp[r] = pv * ((kp ? dp[r] * dr.sc : 0.0f) - s_delta[qi]) * p.scale;   // dS = P o (dP o Z s - D) scale
+                }
+            }
+        } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int qi = acc_row(lane, r), query = q0 + qi;
@@ -815,6 +879,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(AttnBwdParams p) {
             const float pv = ok ? __expf(s[r] * p.scale - s_lse[qi]) : 0.0f;
             s[r] = pv;                               // P[query][key]
             dp[r] = pv * (dp[r] - s_delta[qi]) * p.scale;   // dS[query][key]
+        }
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -827,6 +892,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(AttnBwdParams p) {
                 mma16(dk[i], ld_perm<T>(&qtr[(i * 32 + l31) * TS], t, g), sf);    // dK^T += Q^T dS
             }
         }
+    }
+    if constexpr (DROP) {
+#pragma unroll
+        for (int i = 0; i < NMI; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dv[i][r] *= p.drop_scale;
     }
     if (key < p.S) {
         T* dkp = reinterpret_cast<T*>(p.dk) + head + (size_t)key * p.ld;
@@ -841,8 +912,8 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_kernel(AttnBwdParams p) {
     }
 }
 
-template <typename T, int HD>
-__global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnBwdParams p) {
+template <typename T, int HD, bool DROP = false>
+__global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(FaBwdArgs<DROP> p) {
     using V8 = typename Vec8<T>::type;
     constexpr int EPU = 16 / (int)sizeof(T);
     constexpr int DT = HD < 32 ? 32 : HD, NKK = HD / 16, NMI = DT / 32;
@@ -896,12 +967,27 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_kernel(AttnBwdParams p) {
             mma16(s, ld8<T>(&krow[l31 * RS + kk * 16 + g * 8]), qf[kk]);
             mma16(dp, ld8<T>(&vrow[l31 * RS + kk * 16 + g * 8]), gf[kk]);
         }
+        if constexpr (DROP) {
+            const FaDrop dr = fa_drop(p.drop_seed, p.drop_t, p.drop_scale);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned km = mas_attn_keep_q(dr.s0, dr.s1, dr.off, bh, query, k0 + 8 * j + 4 * g, dr.t);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * j + e, key = k0 + acc_row(lane, r);
+                    const bool ok = (key <= query) && (key < p.S);
+                    const float pv = ok ? __expf(s[r] * p.scale - my_lse) : 0.0f;
+                    dp[r] = pv * ((((km >> e) & 1) ? dp[r] * dr.sc : 0.0f) - my_delta) * p.scale;
+                }
+            }
+        } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int key = k0 + acc_row(lane, r);
             const bool ok = (key <= query) && (key < p.S);
             const float pv = ok ? __expf(s[r] * p.scale - my_lse) : 0.0f;
             dp[r] = pv * (dp[r] - my_delta) * p.scale;      // dS^T[key][query]
+        }
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -992,7 +1078,8 @@ __device__ __forceinline__ void fa_dma_tile(fa_i32x4 rs, unsigned lds_tile, int 
 #ifndef FA_DKV_WGS
 #define FA_DKV_WGS 2
 #endif
-__global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(AttnBwdParams p) {
+template <bool DROP>
+__global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwdArgs<DROP> p) {
     using T = bf16_t;
     constexpr int HD = 64, NKK = 4, NMI = 2, QT2 = 64;
     constexpr int STAGE = 2 * FaTile::BYTES + 2 * QT2 * (int)sizeof(float);
@@ -1116,8 +1203,23 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(AttnB
                     s[r] = ((key <= query) && (query < p.S) && (key < p.S)) ? s[r] : 0.0f;
                 }
             }
+            if constexpr (DROP) {                   // registers 4j .. 4j+3 = queries qs + 8j + 4g + 0..3: two Philox calls each
+                const FaDrop dr = fa_drop(p.drop_seed, p.drop_t, p.drop_scale);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned km = mas_attn_keep_k(dr.s0, dr.s1, dr.off, bh, key, qs + 8 * j + 4 * g, dr.t);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = 4 * j + e;
+                        const bool kp = (km >> e) & 1;
+                        dp[r] = s[r] * ((kp ? dp[r] * dr.sc : 0.0f) - d4[j][e]) * p.scale;   // dS = P o (dP o Z s - D) scale
+                        s[r] = kp ? s[r] : 0.0f;                                              // P o Z (dV takes the scale at the store)
+                    }
+                }
+            } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) dp[r] = s[r] * (dp[r] - d4[r >> 2][r & 3]) * p.scale;                            // dS[query][key]
+            }
 #else
             if (needs_mask && c2 == 12345.0f) s[0] = l4[0][0] + d4[0][0];
 #endif
@@ -1145,6 +1247,12 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(AttnB
         __syncthreads();
         cur ^= 1;
     }
+    if constexpr (DROP) {
+#pragma unroll
+        for (int i = 0; i < NMI; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dv[i][r] *= p.drop_scale;
+    }
     if (key < p.S) {                                 // lane = key, accumulator rows = head dims (4 consecutive per register quad)
         T* dkp = reinterpret_cast<T*>(p.dk) + head + (size_t)key * p.ld;
         T* dvp = reinterpret_cast<T*>(p.dv) + head + (size_t)key * p.ld;
@@ -1164,7 +1272,8 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(AttnB
 #ifndef FA_DQ_WGS
 #define FA_DQ_WGS 3
 #endif
-__global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(AttnBwdParams p) {       // (round 3: DMA staging -> <= 168 VGPRs, 3 waves per SIMD)
+template <bool DROP>
+__global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdArgs<DROP> p) {       // (round 3: DMA staging -> <= 168 VGPRs, 3 waves per SIMD)
     using T = bf16_t;
     constexpr int HD = 64, NKK = 4, NMI = 2, KT2 = 64;
     constexpr int STAGE = 2 * FaTile::BYTES;
@@ -1263,8 +1372,18 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(AttnBwd
                     s[r] = ((key <= query) && (key < p.S)) ? s[r] : 0.0f;
                 }
             }
+            if constexpr (DROP) {
+                const FaDrop dr = fa_drop(p.drop_seed, p.drop_t, p.drop_scale);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const unsigned km = mas_attn_keep_q(dr.s0, dr.s1, dr.off, bh, query, ks + 8 * j + 4 * g, dr.t);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dp[4 * j + e] = s[4 * j + e] * ((((km >> e) & 1) ? dp[4 * j + e] * dr.sc : 0.0f) - my_delta) * p.scale;
+                }
+            } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) dp[r] = s[r] * (dp[r] - my_delta) * p.scale;                                     // dS^T[key][query]
+            }
 #else
             if (needs_mask && c2 == 12345.0f) s[0] = my_lse2 + my_delta;
 #endif
@@ -1302,53 +1421,121 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(AttnBwd
     }
 }
 
-int launch_bwd_fast64(const AttnBwdParams& p, hipStream_t s) {
+template <bool DROP>
+int launch_bwd_fast64(const AttnBwdDropParams& pd, hipStream_t s) {
+    const AttnBwdParams& p = pd;
     const long long rows = (long long)p.B * p.H * p.S;
     hipLaunchKernelGGL((attn_bwd_delta_kernel<bf16_t, 64>), dim3((unsigned)((rows + NT - 1) / NT)), dim3(NT), 0, s, p);
-    AttnBwdParams q = p;
+    FaBwdArgs<DROP> q = pd;
     q.lpt = fa_lpt();
     const dim3 grid = q.lpt ? dim3(p.B * p.H, mas_cdiv(p.S, QT)) : dim3(mas_cdiv(p.S, QT), p.B * p.H);
     constexpr size_t lds_dkv = 2 * (2 * FaTile::BYTES + 2 * 64 * sizeof(float)), lds_dq = 2 * (2 * FaTile::BYTES);
-    hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel, grid, dim3(NT), lds_dkv, s, q);
-    hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel, grid, dim3(NT), lds_dq, s, q);
+    hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<DROP>, grid, dim3(NT), lds_dkv, s, q);
+    hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<DROP>, grid, dim3(NT), lds_dq, s, q);
     MAS_CHECK_LAUNCH("attn_causal_bwd");
     return MAS_OK;
 }
 
-template <typename T, int HD>
-int launch_bwd(const AttnBwdParams& p, hipStream_t s) {
+template <typename T, int HD, bool DROP>
+int launch_bwd(const AttnBwdDropParams& pd, hipStream_t s) {
+    const AttnBwdParams& p = pd;
+    const FaBwdArgs<DROP> a = pd;
     const long long rows = (long long)p.B * p.H * p.S;
     hipLaunchKernelGGL((attn_bwd_delta_kernel<T, HD>), dim3((unsigned)((rows + NT - 1) / NT)), dim3(NT), 0, s, p);
     const dim3 grid(mas_cdiv(p.S, QT), p.B * p.H);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD>), grid, dim3(NT), 0, s, p);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD>), grid, dim3(NT), 0, s, p);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD, DROP>), grid, dim3(NT), 0, s, a);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD, DROP>), grid, dim3(NT), 0, s, a);
     MAS_CHECK_LAUNCH("attn_causal_bwd");
     return MAS_OK;
 }
 
-template <typename T>
-int launch_bwd_hd(const AttnBwdParams& p, int hd, hipStream_t s) {
+template <typename T, bool DROP>
+int launch_bwd_hd(const AttnBwdDropParams& p, int hd, hipStream_t s) {
     switch (hd) {
-        case 16: return launch_bwd<T, 16>(p, s);
-        case 32: return launch_bwd<T, 32>(p, s);
-        case 64: return launch_bwd<T, 64>(p, s);
-        case 128: return launch_bwd<T, 128>(p, s);
+        case 16: return launch_bwd<T, 16, DROP>(p, s);
+        case 32: return launch_bwd<T, 32, DROP>(p, s);
+        case 64: return launch_bwd<T, 64, DROP>(p, s);
+        case 128: return launch_bwd<T, 128, DROP>(p, s);
         default: MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_bwd: head_dim %d not in {16,32,64,128}", hd);
     }
 }
 
-template <typename T>
-int launch_hd(const AttnParams& p, int hd, hipStream_t s) {
+template <typename T, bool DROP>
+int launch_hd(const AttnDropParams& pd, int hd, hipStream_t s) {
+    const FaFwdArgs<DROP> p = pd;
     const dim3 grid(mas_cdiv(p.S, QT), p.B * p.H);
     switch (hd) {
-        case 16: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 16>), grid, dim3(NT), 0, s, p); break;
-        case 32: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 32>), grid, dim3(NT), 0, s, p); break;
-        case 64: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 64>), grid, dim3(NT), 0, s, p); break;
-        case 128: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 128>), grid, dim3(NT), 0, s, p); break;
+        case 16: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 16, DROP>), grid, dim3(NT), 0, s, p); break;
+        case 32: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 32, DROP>), grid, dim3(NT), 0, s, p); break;
+        case 64: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 64, DROP>), grid, dim3(NT), 0, s, p); break;
+        case 128: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 128, DROP>), grid, dim3(NT), 0, s, p); break;
         default: MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_fwd: head_dim %d not in {16,32,64,128}", hd);
     }
     MAS_CHECK_LAUNCH("attn_causal_fwd");
     return MAS_OK;
+}
+
+// the host halves of the entries: drop_t == 0 and a null seed select the DROP = false kernels
+int attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int dtype, int B, int H, int S, int hd, int ld_q, int ld_k,
+             int ld_v, long long q_bs, long long k_bs, long long v_bs, float scale, const long long* seed, unsigned drop_t, hipStream_t s) {
+    if (!q || !k || !v || !o) MAS_FAIL(MAS_EINVAL, "attn_causal_fwd: null argument");
+    if (B <= 0 || H <= 0 || S <= 0) MAS_FAIL(MAS_EINVAL, "attn_causal_fwd: bad shape B=%d H=%d S=%d", B, H, S);
+    AttnDropParams p;
+    p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
+    p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v;
+    p.B = B; p.H = H; p.S = S; p.scale = scale; p.lpt = 0;
+    p.drop_seed = seed; p.drop_t = drop_t; p.drop_scale = mas_drop_scale(drop_t);
+    const bool drop = seed != nullptr;
+    if (dtype == MAS_BF16) {
+        const bool fast = (hd == 64 || hd == 128) && fa_aligned(q, q_bs, ld_q) && fa_aligned(k, k_bs, ld_k) && fa_aligned(v, v_bs, ld_v) &&
+                          (reinterpret_cast<uintptr_t>(o) & 7) == 0 && !attn_generic();
+        if (fast) {
+            // v2 (DMA staging, swizzled unpadded LDS, 4 work-groups per CU) needs 31-bit byte offsets inside one (batch, head) slab
+            const bool small = (long long)S * ld_k * 2 < 0x7fffffffLL && (long long)S * ld_v * 2 < 0x7fffffffLL;
+            if (hd == 64 && small) return drop ? launch_fwd_fast_v2<true>(p, s) : launch_fwd_fast_v2<false>(p, s);
+            // (with dropout the v1 kernel -- head width 128, or 64 beyond v2's offsets -- is not instantiated: the generic bf16 kernel runs)
+            if (!drop) return hd == 64 ? launch_fwd_fast<64>(p, s) : launch_fwd_fast<128>(p, s);
+        }
+        return drop ? launch_hd<bf16_t, true>(p, hd, s) : launch_hd<bf16_t, false>(p, hd, s);
+    }
+    if (dtype == MAS_F32) return drop ? launch_hd<float, true>(p, hd, s) : launch_hd<float, false>(p, hd, s);
+    MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_fwd: dtype %d", dtype);
+}
+
+int attn_bwd(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv, int dtype, int B, int H, int S,
+             int hd, float scale, const long long* seed, unsigned drop_t, hipStream_t s) {
+    if (!qkv || !o || !dout || !lse || !delta || !dqkv) MAS_FAIL(MAS_EINVAL, "attn_causal_bwd: null argument");
+    if (B <= 0 || H <= 0 || S <= 0) MAS_FAIL(MAS_EINVAL, "attn_causal_bwd: bad shape");
+    const size_t esz = mas_esize(dtype);
+    const int d = H * hd;
+    AttnBwdDropParams p;
+    const unsigned char* x = reinterpret_cast<const unsigned char*>(qkv);
+    unsigned char* gx = reinterpret_cast<unsigned char*>(dqkv);
+    p.q = x; p.k = x + (size_t)d * esz; p.v = x + (size_t)2 * d * esz;
+    p.dq = gx; p.dk = gx + (size_t)d * esz; p.dv = gx + (size_t)2 * d * esz;
+    p.o = o; p.dout = dout; p.lse = lse; p.delta = delta;
+    p.ld = 3 * d; p.bs = (long long)S * 3 * d; p.B = B; p.H = H; p.S = S; p.scale = scale; p.lpt = 0;
+    p.drop_seed = seed; p.drop_t = drop_t; p.drop_scale = mas_drop_scale(drop_t);
+    const bool drop = seed != nullptr;
+    if (dtype == MAS_BF16) {
+        const bool al = ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(dqkv) | reinterpret_cast<uintptr_t>(dout)) & 15) == 0 && (d % 8) == 0;
+        if (hd == 64 && al && !attn_generic()) return drop ? launch_bwd_fast64<true>(p, s) : launch_bwd_fast64<false>(p, s);
+        return drop ? launch_bwd_hd<bf16_t, true>(p, hd, s) : launch_bwd_hd<bf16_t, false>(p, hd, s);
+    }
+    if (dtype == MAS_F32) return drop ? launch_bwd_hd<float, true>(p, hd, s) : launch_bwd_hd<float, false>(p, hd, s);
+    MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_bwd: dtype %d", dtype);
+}
+
+// [B, H, S, S] keep mask (1 = kept) from the same device function the query-major kernels call: one thread per (bh, query, 4-key block)
+__global__ __launch_bounds__(NT) void attn_dropout_mask_kernel(const long long* seed, int BH, int S, unsigned t, uint8_t* keep) {
+    const int kblocks = (S + 3) / 4;
+    const long long idx = (long long)blockIdx.x * NT + threadIdx.x, total = (long long)BH * S * kblocks;
+    if (idx >= total) return;
+    const int kb = (int)(idx % kblocks), query = (int)((idx / kblocks) % S), bh = (int)(idx / ((long long)kblocks * S));
+    const FaDrop dr = fa_drop(seed, t, 0.0f);
+    const unsigned km = mas_attn_keep_q(dr.s0, dr.s1, dr.off, bh, query, 4 * kb, dr.t);
+    uint8_t* row = keep + ((size_t)bh * S + query) * S;
+    for (int e = 0; e < 4 && 4 * kb + e < S; ++e) row[4 * kb + e] = (uint8_t)((km >> e) & 1);
 }
 
 }  // namespace
@@ -1357,48 +1544,43 @@ extern "C" int mas_attn_causal_fwd(const void* q, const void* k, const void* v, 
                                    int S, int hd, int ld_q, int ld_k, int ld_v, long long q_bs, long long k_bs,
                                    long long v_bs, float scale, void* stream) {
     MAS_ENTER();
-    if (!q || !k || !v || !o) MAS_FAIL(MAS_EINVAL, "attn_causal_fwd: null argument");
-    if (B <= 0 || H <= 0 || S <= 0) MAS_FAIL(MAS_EINVAL, "attn_causal_fwd: bad shape B=%d H=%d S=%d", B, H, S);
-    AttnParams p;
-    p.q = q; p.k = k; p.v = v; p.o = o; p.lse = lse;
-    p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.ld_q = ld_q; p.ld_k = ld_k; p.ld_v = ld_v;
-    p.B = B; p.H = H; p.S = S; p.scale = scale; p.lpt = 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MAS_BF16) {
-        const bool fast = (hd == 64 || hd == 128) && fa_aligned(q, q_bs, ld_q) && fa_aligned(k, k_bs, ld_k) && fa_aligned(v, v_bs, ld_v) &&
-                          (reinterpret_cast<uintptr_t>(o) & 7) == 0 && !attn_generic();
-        if (fast) {
-            // v2 (DMA staging, swizzled unpadded LDS, 4 work-groups per CU) needs 31-bit byte offsets inside one (batch, head) slab
-            const bool small = (long long)S * ld_k * 2 < 0x7fffffffLL && (long long)S * ld_v * 2 < 0x7fffffffLL;
-            if (hd == 64 && small) return launch_fwd_fast_v2(p, s);
-            return hd == 64 ? launch_fwd_fast<64>(p, s) : launch_fwd_fast<128>(p, s);
-        }
-        return launch_hd<bf16_t>(p, hd, s);
-    }
-    if (dtype == MAS_F32) return launch_hd<float>(p, hd, s);
-    MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_fwd: dtype %d", dtype);
+    return attn_fwd(q, k, v, o, lse, dtype, B, H, S, hd, ld_q, ld_k, ld_v, q_bs, k_bs, v_bs, scale, nullptr, 0u,
+                    reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int mas_attn_causal_bwd(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
                                    int dtype, int B, int H, int S, int hd, float scale, void* stream) {
     MAS_ENTER();
-    if (!qkv || !o || !dout || !lse || !delta || !dqkv) MAS_FAIL(MAS_EINVAL, "attn_causal_bwd: null argument");
-    if (B <= 0 || H <= 0 || S <= 0) MAS_FAIL(MAS_EINVAL, "attn_causal_bwd: bad shape");
-    const size_t esz = mas_esize(dtype);
-    const int d = H * hd;
-    AttnBwdParams p;
-    const unsigned char* x = reinterpret_cast<const unsigned char*>(qkv);
-    unsigned char* gx = reinterpret_cast<unsigned char*>(dqkv);
-    p.q = x; p.k = x + (size_t)d * esz; p.v = x + (size_t)2 * d * esz;
-    p.dq = gx; p.dk = gx + (size_t)d * esz; p.dv = gx + (size_t)2 * d * esz;
-    p.o = o; p.dout = dout; p.lse = lse; p.delta = delta;
-    p.ld = 3 * d; p.bs = (long long)S * 3 * d; p.B = B; p.H = H; p.S = S; p.scale = scale; p.lpt = 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MAS_BF16) {
-        const bool al = ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(dqkv) | reinterpret_cast<uintptr_t>(dout)) & 15) == 0 && (d % 8) == 0;
-        if (hd == 64 && al && !attn_generic()) return launch_bwd_fast64(p, s);
-        return launch_bwd_hd<bf16_t>(p, hd, s);
-    }
-    if (dtype == MAS_F32) return launch_bwd_hd<float>(p, hd, s);
-    MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_bwd: dtype %d", dtype);
+    return attn_bwd(qkv, o, dout, lse, delta, dqkv, dtype, B, H, S, hd, scale, nullptr, 0u, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mas_attn_causal_fwd_drop(const void* q, const void* k, const void* v, void* o, float* lse, int dtype, int B, int H,
+                                        int S, int hd, int ld_q, int ld_k, int ld_v, long long q_bs, long long k_bs,
+                                        long long v_bs, float scale, float p, const int64_t* seed, void* stream) {
+    MAS_ENTER();
+    if (!seed) MAS_FAIL(MAS_EINVAL, "attn_causal_fwd_drop: null seed");
+    if (!(p >= 0.0f && p <= 1.0f)) MAS_FAIL(MAS_EINVAL, "attn_causal_fwd_drop: p = %g outside [0, 1]", (double)p);
+    return attn_fwd(q, k, v, o, lse, dtype, B, H, S, hd, ld_q, ld_k, ld_v, q_bs, k_bs, v_bs, scale, reinterpret_cast<const long long*>(seed),
+                    mas_drop_threshold(p), reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mas_attn_causal_bwd_drop(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
+                                        int dtype, int B, int H, int S, int hd, float scale, float p, const int64_t* seed, void* stream) {
+    MAS_ENTER();
+    if (!seed) MAS_FAIL(MAS_EINVAL, "attn_causal_bwd_drop: null seed");
+    if (!(p >= 0.0f && p <= 1.0f)) MAS_FAIL(MAS_EINVAL, "attn_causal_bwd_drop: p = %g outside [0, 1]", (double)p);
+    return attn_bwd(qkv, o, dout, lse, delta, dqkv, dtype, B, H, S, hd, scale, reinterpret_cast<const long long*>(seed), mas_drop_threshold(p),
+                    reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mas_attn_dropout_mask(const int64_t* seed, int B, int H, int S, float p, uint8_t* keep, void* stream) {
+    MAS_ENTER();
+    if (!seed || !keep) MAS_FAIL(MAS_EINVAL, "attn_dropout_mask: null argument");
+    if (B <= 0 || H <= 0 || S <= 0) MAS_FAIL(MAS_EINVAL, "attn_dropout_mask: bad shape");
+    if (!(p >= 0.0f && p <= 1.0f)) MAS_FAIL(MAS_EINVAL, "attn_dropout_mask: p = %g outside [0, 1]", (double)p);
+    const long long total = (long long)B * H * S * ((S + 3) / 4);
+    hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream),
+                       reinterpret_cast<const long long*>(seed), B * H, S, mas_drop_threshold(p), keep);
+    MAS_CHECK_LAUNCH("attn_dropout_mask");
+    return MAS_OK;
 }

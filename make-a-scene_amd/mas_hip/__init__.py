@@ -99,6 +99,11 @@ _SIGNATURES = {
     "mas_vq_bwd": (_i, [_p, _p, _p, _p, _p, _f, _i, _i, _i, _p, _p, _p]),
     "mas_attn_causal_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, _f, _p]),
     "mas_attn_causal_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
+    "mas_attn_causal_fwd_drop": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, _f, _f, _p,
+                                      _p]),
+    "mas_attn_causal_bwd_drop": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p, _p]),
+    "mas_attn_dropout_mask": (_i, [_p, _i, _i, _i, _f, _p, _p]),
+    "mas_dropout_apply": (_i, [_p, _p, C.c_longlong, _i, _f, _p, _p]),
     "mas_spatial_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "mas_spatial_attn_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mas_attn_decode": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f, _p]),

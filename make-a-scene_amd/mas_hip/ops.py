@@ -1382,7 +1382,7 @@ class _CausalAttention(torch.autograd.Function):
     recomputes them tile by tile from the saved log-sum-exp and writes d(qkv) in place, no atomics)."""
 
     @staticmethod
-    def forward(ctx, qkv, n_heads, cd, scale=None):
+    def forward(ctx, qkv, n_heads, cd, scale=None, p=0.0):
         _require_cuda(qkv, "causal_attention")
         x = qkv.to(cd).contiguous()
         b, s, d3 = x.shape
@@ -1393,52 +1393,153 @@ class _CausalAttention(torch.autograd.Function):
         lse = torch.empty((b, n_heads, s), dtype=torch.float32, device=x.device)
         esz = x.element_size()
         base = x.data_ptr()
-        check(lib().mas_attn_causal_fwd(C.c_void_p(base), C.c_void_p(base + d * esz), C.c_void_p(base + 2 * d * esz), _ptr(o), _ptr(lse),
-                                        _DT[cd], b, n_heads, s, hd, d3, d3, d3, s * d3, s * d3, s * d3, scale, _stream()),
-              "attn_causal_fwd")
+        q_, k_, v_ = C.c_void_p(base), C.c_void_p(base + d * esz), C.c_void_p(base + 2 * d * esz)
+        seed = None
+        if p > 0.0:                         # dropout of P inside the kernels: the mask is regenerated by the backward from this seed
+            seed = drop_seed(x.device)
+            check(lib().mas_attn_causal_fwd_drop(q_, k_, v_, _ptr(o), _ptr(lse), _DT[cd], b, n_heads, s, hd, d3, d3, d3, s * d3, s * d3,
+                                                 s * d3, scale, float(p), _ptr(seed), _stream()), "attn_causal_fwd_drop")
+        else:
+            check(lib().mas_attn_causal_fwd(q_, k_, v_, _ptr(o), _ptr(lse), _DT[cd], b, n_heads, s, hd, d3, d3, d3, s * d3, s * d3, s * d3,
+                                            scale, _stream()), "attn_causal_fwd")
         ctx.n_heads = n_heads
         ctx.scale = scale
+        ctx.p = float(p)
         ctx.in_dtype = qkv.dtype
-        ctx.save_for_backward(x, o, lse)
+        ctx.save_for_backward(x, o, lse, seed)
         return o.to(qkv.dtype)
 
     @staticmethod
     def backward(ctx, do):
-        x, o, lse = ctx.saved_tensors
+        x, o, lse, seed = ctx.saved_tensors
         b, s, d3 = x.shape
         h = ctx.n_heads
         hd = d3 // 3 // h
         g = do.to(x.dtype).contiguous()
         dx = torch.empty_like(x)
         delta = torch.empty_like(lse)
-        check(lib().mas_attn_causal_bwd(_ptr(x), _ptr(o), _ptr(g), _ptr(lse), _ptr(delta), _ptr(dx), _DT[x.dtype], b, h, s, hd,
-                                        ctx.scale, _stream()), "attn_causal_bwd")
-        return dx.to(ctx.in_dtype), None, None, None
+        if seed is not None:
+            check(lib().mas_attn_causal_bwd_drop(_ptr(x), _ptr(o), _ptr(g), _ptr(lse), _ptr(delta), _ptr(dx), _DT[x.dtype], b, h, s, hd,
+                                                 ctx.scale, ctx.p, _ptr(seed), _stream()), "attn_causal_bwd_drop")
+        else:
+            check(lib().mas_attn_causal_bwd(_ptr(x), _ptr(o), _ptr(g), _ptr(lse), _ptr(delta), _ptr(dx), _DT[x.dtype], b, h, s, hd,
+                                            ctx.scale, _stream()), "attn_causal_bwd")
+        return dx.to(ctx.in_dtype), None, None, None, None
 
 
-def causal_attention(qkv: torch.Tensor, n_heads: int, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+def causal_attention(qkv: torch.Tensor, n_heads: int, dtype: Optional[torch.dtype] = None, dropout_p: float = 0.0) -> torch.Tensor:
     """``dtype`` None: the arithmetic follows the INPUT -- bf16 kernels for a bf16 projection (what ``nn.Linear`` emits
     under ``torch.autocast(bfloat16)``), exact-fp32 kernels for an fp32 one (the reference's un-autocast
-    ``train_transformer`` loop, train.py:150).  Pass ``dtype`` to force one."""
+    ``train_transformer`` loop, train.py:150).  Pass ``dtype`` to force one.
+    ``dropout_p`` > 0: dropout of the attention probabilities (the reference's ``attn_drop``, transformer.py:32,92) inside the kernels,
+    seeded from torch's CUDA generator (``drop_seed``); p is quantised to 1/65536 (include/mas_hip.h, "Dropout").  The caller passes
+    0 outside training."""
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p <= 1.0:
+        raise ValueError(f"causal_attention: dropout probability {dropout_p} outside [0, 1]")
     if dtype is None:
         dtype = qkv.dtype
     if dtype not in _DT:
         raise RuntimeError(f"causal_attention: dtype {dtype} not supported (float32 / bfloat16)")
     b, s, d3 = qkv.shape
     hd = d3 // 3 // n_heads
+    # (p = 0 keeps the call exactly as it was: bench.py --full wraps _CausalAttention.forward with the four-argument signature)
+    drop = (None, dropout_p) if dropout_p > 0.0 else ()
     if hd in _ATTN_HEAD_DIMS:
-        return _CausalAttention.apply(qkv, n_heads, dtype)
+        return _CausalAttention.apply(qkv, n_heads, dtype, *drop)
     if hd > _ATTN_HEAD_DIMS[-1]:                                    # wider than any kernel instantiation: ATen's fused attention on the GPU
         q, k, v = (t.reshape(b, s, n_heads, hd).transpose(1, 2).to(dtype) for t in qkv.split(n_heads * hd, dim=-1))
-        o = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True)
+        o = torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True, dropout_p=dropout_p)
         return o.transpose(1, 2).reshape(b, s, n_heads * hd).to(qkv.dtype)
     # any other head width (the reference's constructor takes every hidden_dim divisible by the head count, models/transformer.py:17-35): the
     # heads are zero-padded to the next width the kernels have -- zero dimensions add nothing to a score, produce zero context columns and
     # receive zero gradients -- with the softmax scale of the TRUE width.  Differentiable torch ops around the same node; off the benched path.
     hp = next(v for v in _ATTN_HEAD_DIMS if v >= hd)
     x = torch.nn.functional.pad(qkv.reshape(b, s, 3, n_heads, hd), (0, hp - hd)).reshape(b, s, 3 * n_heads * hp)
-    o = _CausalAttention.apply(x, n_heads, dtype, float(hd) ** -0.5)
+    o = _CausalAttention.apply(x, n_heads, dtype, float(hd) ** -0.5, *drop[1:])     # (padding does not touch P: the mask is the same)
     return o.reshape(b, s, n_heads, hp)[..., :hd].reshape(b, s, n_heads * hd)
+
+
+# --------------------------------------------------------------------------- #
+# dropout (Philox4x32-10 in the kernels: make-a-scene_amd/csrc/mas_philox.h; mapping: include/mas_hip.h, "Dropout")
+# --------------------------------------------------------------------------- #
+def drop_seed(device) -> torch.Tensor:
+    """{seed, offset}: two int64 drawn on the device from torch's default CUDA generator -- ``torch.manual_seed`` reproduces a run and
+    ``torch.utils.checkpoint``'s RNG-state replay redraws the same pair (the same masks); no host synchronisation"""
+    return torch.randint(0, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
+
+
+def _dropout_apply(x: torch.Tensor, p: float, seed: torch.Tensor) -> torch.Tensor:
+    x = x.contiguous(memory_format=torch.channels_last) if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) else x.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    y = torch.empty_like(x)
+    check(lib().mas_dropout_apply(_ptr(x), _ptr(y), x.numel(), _DT[x.dtype], float(p), _ptr(seed), _stream()), "dropout_apply")
+    return y
+
+
+class _Dropout(torch.autograd.Function):
+    """y = x o Z * 65536 / (65536 - t) (``mas_dropout_apply``); the backward is the same launch on dy with the saved seed (no mask stored).
+    The mask follows the flat index in MEMORY order (channels_last tensors stay channels_last)."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        _require_cuda(x, "dropout")
+        if x.dtype not in _DT:
+            raise RuntimeError(f"dropout: dtype {x.dtype} not supported (float32 / bfloat16)")
+        seed = drop_seed(x.device)
+        ctx.p = p
+        ctx.cl = x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last)
+        ctx.save_for_backward(seed)
+        return _dropout_apply(x, p, seed)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (seed,) = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last) if ctx.cl else dy.contiguous()
+        return _dropout_apply(dy, ctx.p, seed), None
+
+
+def dropout(x: torch.Tensor, p: float, training: bool = True) -> torch.Tensor:
+    """``F.dropout`` on the GPU through ``mas_dropout_apply``: p = 0 or not training returns x itself (nothing drawn); p = 1 gives zeros;
+    p is quantised to 1/65536."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"dropout: probability {p} outside [0, 1]")
+    if not training or p == 0.0:
+        return x
+    return _Dropout.apply(x, p)
+
+
+class _GroupNormAct(torch.autograd.Function):
+    """act(GroupNorm(x)) materialised (``mas_gn_stats`` + ``mas_gn_act``), backward ``gn_bwd``: the tensor ResnetBlock's dropout acts on
+    (reference modules.py:126-127).  x channels_last bf16 / fp32."""
+
+    @staticmethod
+    def forward(ctx, x, gn_w, gn_b, groups, eps, act):
+        _require_cuda(x, "group_norm_act")
+        x = nhwc(x)
+        mr, ss = gn_stats(x, gn_w.detach().float(), gn_b.detach().float(), groups, eps)
+        if _gn_act_ok(x.shape[1], x.dtype):
+            a = gn_act(x, ss, act)
+        else:                               # channel counts outside the streaming kernel's envelope (see _gn_bwd_aten): ATen on the GPU
+            n, c = x.shape[:2]
+            u = x.float() * ss[..., 0].view(n, c, 1, 1) + ss[..., 1].view(n, c, 1, 1)
+            a = (u * torch.sigmoid(u) if act == ACT_AFFINE_SILU else u).to(x.dtype).contiguous(memory_format=torch.channels_last)
+        ctx.groups, ctx.act = groups, act
+        ctx.save_for_backward(x, gn_w, mr, ss)
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        x, gn_w, mr, ss = ctx.saved_tensors
+        dx, dgw, dgb = gn_bwd(x, nhwc(da, x.dtype), None, ctx.groups, ctx.act, gn_w.detach().float(), mr, ss)
+        return dx, dgw.to(gn_w.dtype), dgb.to(gn_w.dtype), None, None, None
+
+
+def group_norm_act(x: torch.Tensor, norm, act: int = ACT_AFFINE_SILU, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """act(norm(x)) as a channels_last tensor of ``dtype`` (default: the compute dtype); ``norm`` is a GroupNorm module"""
+    return _GroupNormAct.apply(nhwc(x, dtype or compute_dtype()), norm.weight, norm.bias, norm.num_groups, norm.eps, act)
 
 
 def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: int, n_heads: int) -> torch.Tensor:

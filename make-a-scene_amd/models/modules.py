@@ -187,7 +187,13 @@ class ResnetBlock(nn.Module):
 
     def forward(self, x):
         if self.training and self.dropout.p > 0:
-            raise NotImplementedError("dropout > 0 is off the hot path (the reference always builds blocks with dropout=0.0)")
+            # the reference's order (modules.py:124-136): conv1(silu(gn1(x))), silu(gn2(.)) materialised, dropout (mas_dropout_apply), conv2
+            # with the shortcut in its epilogue.  Off the fused node: the reference never builds blocks with dropout > 0.
+            h = self.conv1.fused(x, self.norm1, ACT_AFFINE_SILU)
+            a = ops.dropout(ops.group_norm_act(h, self.norm2, ACT_AFFINE_SILU, dtype=h.dtype), self.dropout.p, True)
+            if self.in_channels != self.out_channels:
+                x = self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x)
+            return self.conv2(a, residual=x)
         plain = self.conv1.in_dtype is None and self.conv2.out_dtype is None and self.conv1.bias is not None and self.conv2.bias is not None
         if plain and self.in_channels == self.out_channels:
             return ops.resblock(x, self.norm1, self.conv1, self.norm2, self.conv2)     # one autograd node (fused skip gradient)

@@ -107,11 +107,15 @@ class SelfAttention(nn.Module):
         self.rudalle_relax = rudalle_relax
 
     def forward(self, x, mask, use_cache=False, cache=None):
-        if self.rudalle_relax or (self.training and self.attn_drop.p > 0):
-            raise NotImplementedError("rudalle_relax / attention dropout are off the measured path (reference defaults: off)")
+        if self.rudalle_relax:
+            raise NotImplementedError("rudalle_relax is off the measured path (reference default: off)")
         if not use_cache:
             qkv = self.qkv(x)
-            context = ops.causal_attention(qkv, self.num_attn_heads)     # `mask` is causal by construction (transformer.py:260-263)
+            # `mask` is causal by construction (transformer.py:260-263); attn_drop (transformer.py:32,92) runs inside the kernels
+            if self.training and self.attn_drop.p > 0:
+                context = ops.causal_attention(qkv, self.num_attn_heads, dropout_p=self.attn_drop.p)
+            else:
+                context = ops.causal_attention(qkv, self.num_attn_heads)
             return self.out_drop(self.out_proj(context)), cache
         return self._forward_cached(x, cache)
 
@@ -147,7 +151,16 @@ class SelfAttention(nn.Module):
         kbuf[:, past:s_tot] = qkv[..., d:2 * d]
         vbuf[:, past:s_tot] = qkv[..., 2 * d:]
         q = qkv[..., :d]
-        if cache is None and nq > 1:
+        if self.training and self.attn_drop.p > 0:
+            # training-mode dropout on the cached path (the reference applies attn_drop there too, transformer.py:92): ATen on the GPU
+            hd = d // h
+            qh = q.reshape(b, nq, h, hd).transpose(1, 2).float()
+            kh, vh = (t[:, :s_tot].reshape(b, s_tot, h, hd).transpose(1, 2).float() for t in (kbuf, vbuf))
+            allowed = torch.arange(s_tot, device=x.device)[None, :] <= (past + torch.arange(nq, device=x.device))[:, None]
+            sc = torch.matmul(qh, kh.transpose(-1, -2)) * (float(hd) ** -0.5)
+            pr = self.attn_drop(torch.softmax(sc.masked_fill(~allowed, float("-inf")), dim=-1))
+            context = torch.matmul(pr, vh).transpose(1, 2).reshape(b, nq, d).to(dt)
+        elif cache is None and nq > 1:
             context = ops.causal_attention(qkv, h)                  # prefill: the training kernel on the whole prompt
         else:
             context = ops.attention_decode(q, kbuf, vbuf, past, h)  # decode: one pass over the cached rows

@@ -408,6 +408,55 @@ int mas_bn_apply_act(const void* x, const float* scale_shift, void* y, float slo
 int mas_bn_bwd_apply_act(const void* x, const void* dy, const float* mean_rstd, const float* gamma, const float* scale_shift, float slope,
                          const double* sums, void* dx, int dtype, int M, int C, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * FaceLoss (reference losses/face_loss.py): the face-aware term of the VQ-IMG objective, a frozen caffe-style ResNet-50 in
+ * evaluation mode on <= 6 face crops of 254 x 254 (face.hip).  Activations are NHWC in `dtype` (MAS_BF16 / MAS_F32); every sum
+ * runs in fp32 in a fixed order (no float atomics).  The 52 1x1 / 3x3 convolutions go through mas_conv_fwd.
+ *   MasFaceRow: one face row, geometry computed on the host: image b of img (src 0) or rec (src 1), crop box (top, left, h, w),
+ *     Resize(256) size rh x rw, CenterCrop(254) offsets ct, cl.
+ *   MasFaceImage: a [N,3,H,W] image of any strides (elements), fp32 or bf16.
+ *   mas_face_crop_fwd : out[r][y][x][c] (NHWC, out_dtype) = CenterCrop(Resize(crop(src_r))) with torch's antialiased bilinear weights
+ *                       (align_corners = False); pixels of the box outside the image read 0.
+ *   mas_face_crop_bwd : the exact adjoint as a gather: drec (written in full, its own strides) = sum over the rows in table order of
+ *                       the rows' fp32 gradients dfaces [n_rows][254][254][3].  Every row is taken as a rec row.
+ *   mas_face_stem_fwd / _dgrad : the 7x7 / stride 2 / pad 3 convolution 3 -> 64 (w fp32 OIHW) on [R,254,254,3] -> [R,127,127,64],
+ *                       and its data gradient (dx fp32).
+ *   mas_face_bn_fold  : the evaluation-mode affine pairs of n_items BatchNorm2d layers (items: a DEVICE table) into
+ *                       scale_shift[(off + c) * 2 + {0,1}], one launch.
+ *   mas_face_pool_fwd / _bwd : relu(bn(y)) -> MaxPool2d(3, 2, ceil_mode) over an [R,H,W,C] map; idx (one byte per output) holds the
+ *                       window index of the first maximum; the backward writes dy = relu'(u) * scale * (gather of dz) + seed.
+ *   mas_face_join_fwd : out = relu(y3 * s3 + t3 + (ssr ? r * sr + tr : r)), the Bottleneck's residual join.
+ *   mas_face_join_bwd : g = [out > 0] (dout + dadd) (either may be NULL), dy3 = g * s3, dres = ssr ? g * sr : g.
+ *   mas_face_relu_bn_bwd : dy = [a > 0] da * s (a = relu(bn(y)) saved by the forward).
+ *   mas_face_subsample2x : y[n][h][w][c] = x[n][2h][2w][c], y [N, ceil(H/2), ceil(W/2), C] (the stride of a 1x1 / stride-2 conv).
+ *   mas_face_l1_fwd   : out6[i] = alpha_i * sum |p0 - p1| / chw_i over the `half` row pairs (row q against row half + q) of feature i,
+ *                       out6[5] = their sum; workspace of mas_face_l1_workspace(f) floats.  Two launches (partials, fixed-order fold).
+ *   mas_face_l1_bwd   : seeds[i] [nb rows of feature i] = (dl6[i] + dl6[5]) * alpha_i * sign(p(row0 + k) - p(row0 + k - half)) / chw_i
+ *                       (seeds: a HOST array of five device pointers; sign(0) = 0).                                                  */
+#define MAS_FACE_SIZE 254
+#define MAS_FACE_MAX_ROWS 8
+typedef struct { int32_t src, b, top, left, h, w, rh, rw, ct, cl; } MasFaceRow;
+typedef struct { void* data; int32_t dtype, N, C, H, W, pad_; int64_t sn, sc, sh, sw; } MasFaceImage;
+typedef struct { const float* weight; const float* bias; const float* mean; const float* var; int32_t C, off; float eps; int32_t pad_; } MasFaceBnItem;
+typedef struct { const void* p[5]; int32_t chw[5]; int32_t half; int32_t dtype; float alpha[5]; } MasFaceFeats;
+int mas_face_crop_fwd(const MasFaceImage* img, const MasFaceImage* rec, const MasFaceRow* rows, int n_rows, void* out, int out_dtype,
+                      void* stream);
+int mas_face_crop_bwd(const float* dfaces, const MasFaceRow* rows, int n_rows, const MasFaceImage* drec, void* stream);
+int mas_face_stem_fwd(const void* x, const float* w, void* y, int dtype, int R, void* stream);
+int mas_face_stem_dgrad(const void* dy, const float* w, float* dx, int dtype, int R, void* stream);
+int mas_face_bn_fold(const MasFaceBnItem* items, int n_items, float* scale_shift, void* stream);
+int mas_face_pool_fwd(const void* y, const float* scale_shift, void* z, unsigned char* idx, int dtype, int R, int H, int W, int C, void* stream);
+int mas_face_pool_bwd(const void* y, const float* scale_shift, const void* dz, const unsigned char* idx, const void* seed, void* dy, int dtype,
+                      int R, int H, int W, int C, void* stream);
+int mas_face_join_fwd(const void* y3, const float* ss3, const void* r, const float* ssr, void* out, int dtype, int M, int C, void* stream);
+int mas_face_join_bwd(const void* dout, const void* dadd, const void* out, const float* ss3, const float* ssr, void* dy3, void* dres, int dtype,
+                      int M, int C, void* stream);
+int mas_face_relu_bn_bwd(const void* da, const void* a, const float* scale_shift, void* dy, int dtype, int M, int C, void* stream);
+int mas_face_subsample2x(const void* x, void* y, int dtype, int N, int H, int W, int C, void* stream);
+int mas_face_l1_workspace(const MasFaceFeats* f);
+int mas_face_l1_fwd(const MasFaceFeats* f, float* workspace, float* out6, void* stream);
+int mas_face_l1_bwd(const MasFaceFeats* f, int row0, int nb, const float* dl6, void* const* seeds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,10 +7,11 @@ networks at absolute paths -- LPIPS-VGG16 (``/home/ubuntu/.../vgg.pth``, lpips.p
 (face_loss.py:76) -- are pluggable here.  ``perceptual_loss="lpips"`` (the DEFAULT, as the reference's constructor always builds
 it, loss_img.py:45) is ``losses.lpips_with_object.LPIPSWithObject`` on the HIP convolutions (weights from ``MAS_LPIPS_CKPT`` /
 ``MAS_VGG16_CKPT``; missing weights are reported loudly by ``LPIPS.load_from_pretrained``); a callable is used as given; an
-explicit ``None`` opts out.  ``face_loss``: the reference always builds ``FaceLoss()`` (loss_img.py:48) -- a pretrained
-face-embedding network that is not part of this repository (out of scope) -- so the default here
-(``"reference"``) logs ONCE that the face term is absent from the objective and contributes 0; pass a callable to supply it, or
-``None`` to opt out silently.  The arithmetic below is the reference's line for line.  ``forward`` keeps the reference's signature and return shapes
+explicit ``None`` opts out.  ``face_loss``: the reference always builds ``FaceLoss()`` (loss_img.py:48), a pretrained
+face-embedding network whose weights are not part of this repository.  The default here (``"reference"``) builds
+``losses.face_loss.FaceLoss`` (HIP, evaluation mode) when its checkpoint exists (``MAS_FACE_CKPT``, or the reference's path);
+otherwise it logs ONCE that the face term is absent from the objective and contributes 0.  A callable is used as given, ``None``
+opts out silently.  The arithmetic below is the reference's line for line.  ``forward`` keeps the reference's signature and return shapes
 (optimizer_idx 0 -> ``loss, (nll_loss, object_loss, face_loss)``; 1 -> ``d_loss``)."""
 import warnings
 
@@ -53,13 +54,18 @@ class VQLPIPSWithDiscriminator(nn.Module):
         if isinstance(face_loss, str):
             if face_loss != "reference":
                 raise ValueError("face_loss: a callable, None, or 'reference' (the default)")
-            if not VQLPIPSWithDiscriminator._face_warned:
-                VQLPIPSWithDiscriminator._face_warned = True
-                warnings.warn("VQLPIPSWithDiscriminator: the reference adds FaceLoss() (losses/face_loss.py: a pretrained face-embedding "
-                              "network, not part of this repository) to the generator objective; it is ABSENT here and contributes 0 "
-                              "-- pass face_loss=<callable(images, reconstructions, bbox_face)> to supply it, face_loss=None to "
-                              "silence this message")
-            face_loss = None
+            from .face_loss import FaceLoss, ckpt_path
+            if ckpt_path() is not None:
+                face_loss = FaceLoss()
+            else:
+                if not VQLPIPSWithDiscriminator._face_warned:
+                    VQLPIPSWithDiscriminator._face_warned = True
+                    warnings.warn("VQLPIPSWithDiscriminator: the reference adds FaceLoss() (losses/face_loss.py: a pretrained face-embedding "
+                                  "network whose weights are not part of this repository) to the generator objective; no checkpoint was "
+                                  "found, so it is ABSENT here and contributes 0.  Set MAS_FACE_CKPT to the reference's "
+                                  "face_loss_weights.pt to train with it -- or pass face_loss=<callable(images, reconstructions, "
+                                  "bbox_face)> to supply another, face_loss=None to silence this message")
+                face_loss = None
         self.face_loss = face_loss                    # callable(images, reconstructions, bbox_face) -> scalar, or None
         self.discriminator = Discriminator().apply(weights_init)
         self.discriminator_iter_start = disc_start

@@ -53,6 +53,28 @@ class AdamItem(C.Structure):
                 ("pad_", C.c_int32)]
 
 
+class FaceRow(C.Structure):
+    """Mirror of ``MasFaceRow`` (include/mas_hip.h): one face row of FaceLoss, its geometry computed on the host."""
+    _fields_ = [(n, C.c_int32) for n in ("src", "b", "top", "left", "h", "w", "rh", "rw", "ct", "cl")]
+
+
+class FaceImage(C.Structure):
+    """Mirror of ``MasFaceImage`` (include/mas_hip.h): a [N,3,H,W] image of any element strides."""
+    _fields_ = [("data", C.c_void_p)] + [(n, C.c_int32) for n in ("dtype", "N", "C", "H", "W", "pad_")] + \
+               [(n, C.c_int64) for n in ("sn", "sc", "sh", "sw")]
+
+
+class FaceBnItem(C.Structure):
+    """Mirror of ``MasFaceBnItem`` (include/mas_hip.h): one BatchNorm2d layer of the evaluation-mode fold."""
+    _fields_ = [(n, C.c_void_p) for n in ("weight", "bias", "mean", "var")] + [("C", C.c_int32), ("off", C.c_int32), ("eps", C.c_float),
+                                                                                ("pad_", C.c_int32)]
+
+
+class FaceFeats(C.Structure):
+    """Mirror of ``MasFaceFeats`` (include/mas_hip.h): the five feature maps of the face L1 distance."""
+    _fields_ = [("p", C.c_void_p * 5), ("chw", C.c_int32 * 5), ("half", C.c_int32), ("dtype", C.c_int32), ("alpha", C.c_float * 5)]
+
+
 _p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _SIGNATURES = {
     "mas_abi_version": (C.c_int, []),
@@ -131,6 +153,20 @@ _SIGNATURES = {
     "mas_layernorm_pair_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
     "mas_colsum_workspace": (_sz, [_i, _i]),
     "mas_colsum": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
+    "mas_face_crop_fwd": (_i, [C.POINTER(FaceImage), C.POINTER(FaceImage), C.POINTER(FaceRow), _i, _p, _i, _p]),
+    "mas_face_crop_bwd": (_i, [_p, C.POINTER(FaceRow), _i, C.POINTER(FaceImage), _p]),
+    "mas_face_stem_fwd": (_i, [_p, _p, _p, _i, _i, _p]),
+    "mas_face_stem_dgrad": (_i, [_p, _p, _p, _i, _i, _p]),
+    "mas_face_bn_fold": (_i, [_p, _i, _p, _p]),
+    "mas_face_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mas_face_pool_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "mas_face_join_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "mas_face_join_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "mas_face_relu_bn_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "mas_face_subsample2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "mas_face_l1_workspace": (_i, [C.POINTER(FaceFeats)]),
+    "mas_face_l1_fwd": (_i, [C.POINTER(FaceFeats), _p, _p, _p]),
+    "mas_face_l1_bwd": (_i, [C.POINTER(FaceFeats), _i, _i, _p, C.POINTER(_p), _p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1,0 +1,365 @@
+"""FaceLoss (reference losses/face_loss.py) as ONE autograd node over libmas_hip (csrc/face.hip + the convolution dispatch).
+
+Host side of the face-aware VQ-IMG term: the face geometry (torchvision's crop / ``Resize(256)`` / ``CenterCrop(254)`` rules, computed
+from the host boxes -- no device-to-host synchronisation), the reference's ``faces[:6]`` row selection, and the frozen ResNet-50 in
+evaluation mode, forward and data gradient.  Activations are NHWC in the compute dtype (bf16 by default, fp32 in parity mode).  The
+backward runs the network only for the rows that come from ``rec``: they are always the tail of the surviving rows (the row pairs
+are (q, half + q) and ``half = min(n, 3) <= n``), so it works on slices of the saved maps."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import ACT_NONE, FaceBnItem, FaceFeats, FaceImage, FaceRow, check, lib
+from . import ops
+
+FACE = 254            # CenterCrop(254)
+RESIZE = 256          # Resize(256): the short side
+MAX_ROWS = 6          # faces[:6] (reference face_loss.py:140)
+ALPHAS = (0.1, 0.25 * 0.01, 0.25 * 0.1, 0.25 * 0.2, 0.25 * 0.02)
+_DT = {torch.float32: 0, torch.bfloat16: 1}
+
+
+# --------------------------------------------------------------------------- #
+# geometry (host)
+# --------------------------------------------------------------------------- #
+def resized_size(h: int, w: int):
+    """torchvision ``Resize(256)`` on an h x w crop: the short side becomes 256, the long one ``int(256 * long / short)``."""
+    if w <= h:
+        return int(RESIZE * h / w), RESIZE
+    return RESIZE, int(RESIZE * w / h)
+
+
+def center_offsets(rh: int, rw: int):
+    """torchvision ``CenterCrop(254)``: Python's ``round`` (halves to even)."""
+    return int(round((rh - FACE) / 2.0)), int(round((rw - FACE) / 2.0))
+
+
+def face_geometry(box):
+    """[x_min, y_min, x_max, y_max] -> dict(top, left, h, w, rh, rw, ct, cl); a box without area is a ValueError (the reference's
+    Resize would divide by zero)."""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    h, w = y1 - y0, x1 - x0
+    if h <= 0 or w <= 0:
+        raise ValueError(f"FaceLoss: face box {[x0, y0, x1, y1]} has no area (height {h}, width {w})")
+    rh, rw = resized_size(h, w)
+    ct, cl = center_offsets(rh, rw)
+    return dict(top=y0, left=x0, h=h, w=w, rh=rh, rw=rw, ct=ct, cl=cl)
+
+
+def face_list(bboxes, n_images: int):
+    """(image index, box) per face in the reference's order: images, then boxes (``zip(imgs, recs, bboxes)`` stops at the shorter)."""
+    out = []
+    for b, boxes in zip(range(n_images), bboxes):
+        for box in boxes:
+            out.append((b, box))
+    return out
+
+
+def surviving_rows(n: int):
+    """The rows of ``cat([gt faces], [rec faces])[:6]`` as (src, face): src 0 = img, 1 = rec.  Pairs are (q, half + q),
+    half = len // 2: for n = 4 that is (gt0, gt3), (gt1, rec0), (gt2, rec1); for n >= 6 no rec row survives."""
+    return ([(0, i) for i in range(n)] + [(1, i) for i in range(n)])[:MAX_ROWS]
+
+
+def plan(bboxes, n_images: int):
+    """-> (n faces, list of MasFaceRow for the surviving rows).  Geometry of the dropped rows is still validated, as the reference
+    crops them."""
+    faces = face_list(bboxes, n_images)
+    geo = [face_geometry(box) for _, box in faces]
+    rows = []
+    for src, i in surviving_rows(len(faces)):
+        g = geo[i]
+        rows.append(FaceRow(src, faces[i][0], g["top"], g["left"], g["h"], g["w"], g["rh"], g["rw"], g["ct"], g["cl"]))
+    return len(faces), rows
+
+
+def _image(t: torch.Tensor) -> FaceImage:
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise ValueError(f"FaceLoss: images must be [N, 3, H, W], got {tuple(t.shape)}")
+    if t.dtype not in _DT:
+        raise TypeError(f"FaceLoss: images must be float32 or bfloat16, got {t.dtype}")
+    n, c, h, w = t.shape
+    sn, sc, sh, sw = t.stride()
+    return FaceImage(t.data_ptr(), _DT[t.dtype], n, c, h, w, 0, sn, sc, sh, sw)
+
+
+def _rows_array(rows):
+    arr = (FaceRow * len(rows))()
+    for i, r in enumerate(rows):
+        arr[i] = r
+    return arr
+
+
+def crop_faces(img, rec, rows, dtype):
+    """[R, 3, 254, 254] (channels_last, ``dtype``): CenterCrop(Resize(crop(.))) of every row, one launch."""
+    out = torch.empty((len(rows), 3, FACE, FACE), dtype=dtype, device=img.device, memory_format=torch.channels_last)
+    gi, gr = _image(img), _image(rec)
+    check(lib().mas_face_crop_fwd(C.byref(gi), C.byref(gr), _rows_array(rows), len(rows), C.c_void_p(out.data_ptr()), _DT[dtype], ops._stream()),
+          "face_crop_fwd")
+    return out
+
+
+def crop_faces_bwd(dfaces: torch.Tensor, rows, like: torch.Tensor):
+    """d ``like`` (its dtype and layout) from the fp32 NHWC gradients of ``rows`` (all taken as rows of ``like``), one launch."""
+    drec = torch.empty_like(like)
+    g = _image(drec)
+    check(lib().mas_face_crop_bwd(C.c_void_p(dfaces.data_ptr()), _rows_array(rows), len(rows), C.byref(g), ops._stream()), "face_crop_bwd")
+    return drec
+
+
+class FaceCrop(torch.autograd.Function):
+    """The crop pass as an autograd node of its own (``FaceLoss.prepare_faces`` and the training-mode path)."""
+
+    @staticmethod
+    def forward(ctx, img, rec, rows, dtype):
+        ctx.rows = rows
+        ctx.save_for_backward(img, rec)
+        return crop_faces(img, rec, rows, dtype)
+
+    @staticmethod
+    def backward(ctx, dfaces):
+        img, rec = ctx.saved_tensors
+        d = dfaces.float().contiguous(memory_format=torch.channels_last)
+        grads = []
+        for src, t in ((0, img), (1, rec)):
+            if not ctx.needs_input_grad[src]:
+                grads.append(None)
+                continue
+            sel = [i for i, r in enumerate(ctx.rows) if r.src == src]
+            if not sel:
+                grads.append(torch.zeros_like(t))
+                continue
+            grads.append(crop_faces_bwd(d[sel].contiguous(memory_format=torch.channels_last), [ctx.rows[i] for i in sel], t))
+        return grads[0], grads[1], None, None
+
+
+# --------------------------------------------------------------------------- #
+# the network (evaluation mode)
+# --------------------------------------------------------------------------- #
+def blocks_of(mod):
+    """[(layer index 1..4, Bottleneck)] in forward order"""
+    return [(li, blk) for li in range(1, 5) for blk in getattr(mod, f"layer{li}")]
+
+
+def bn_layers(mod):
+    out = [mod.bn1]
+    for _, blk in blocks_of(mod):
+        out += [blk.bn1, blk.bn2, blk.bn3]
+        if blk.downsample is not None:
+            out.append(blk.downsample[1])
+    return out
+
+
+_bn_tables = {}
+
+
+def fold_bn(mod):
+    """The 53 evaluation-mode affine pairs from the CURRENT running statistics, one launch: -> (scale_shift [sum C, 2] fp32,
+    {id(bn): channel offset}).  Only the device table of buffer ADDRESSES is cached (keyed on them); the values are read every call."""
+    bns = bn_layers(mod)
+    dev = bns[0].running_mean.device
+    for bn in bns:
+        for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError("FaceLoss: BatchNorm parameters and buffers must be contiguous fp32 on the loss's device")
+    key = (dev.index,) + tuple((bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps))
+                               for bn in bns)
+    offs, off = {}, 0
+    for bn in bns:
+        offs[id(bn)] = off
+        off += bn.num_features
+    table = _bn_tables.get(key)
+    if table is None:
+        items = (FaceBnItem * len(bns))()
+        for i, bn in enumerate(bns):
+            items[i] = FaceBnItem(bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.num_features,
+                                  offs[id(bn)], float(bn.eps), 0)
+        host = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8)
+        table = host.to(dev)
+        _bn_tables.clear()                      # one live module layout at a time is the common case; stale addresses are never reused
+        _bn_tables[key] = table
+    ss = torch.empty((off, 2), dtype=torch.float32, device=dev)
+    check(lib().mas_face_bn_fold(C.c_void_p(table.data_ptr()), len(bns), C.c_void_p(ss.data_ptr()), ops._stream()), "face_bn_fold")
+    return ss, offs
+
+
+def _ssp(ss, offs, bn):
+    return C.c_void_p(ss.data_ptr() + 8 * offs[id(bn)]) if bn is not None else None
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _conv1x1(x, w, cout, residual=None, transpose=False):
+    n, cin, h, wd = x.shape
+    return ops.conv_fwd_raw(x, None, ops.ConvWeight(w, transpose), None, residual, n, h, wd, cin, h, wd, cout, 1, 1, 0, 0, ACT_NONE, False, x.dtype)
+
+
+def _conv3x3(x, w, cout, transpose=False):
+    n, cin, h, wd = x.shape
+    return ops.conv_fwd_raw(x, None, ops.ConvWeight(w, transpose), None, None, n, h, wd, cin, h, wd, cout, 3, 1, 1, 1, ACT_NONE, False, x.dtype)
+
+
+def _bn_relu(y, ss, offs, bn):
+    n, c, h, w = y.shape
+    out = torch.empty_like(y)
+    check(lib().mas_bn_apply_act(_p(y), _ssp(ss, offs, bn), _p(out), 0.0, _DT[y.dtype], n * h * w, c, ops._stream()), "bn_apply_act")
+    return out
+
+
+def _subsample(x):
+    n, c, h, w = x.shape
+    y = torch.empty((n, c, (h + 1) // 2, (w + 1) // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    check(lib().mas_face_subsample2x(_p(x), _p(y), _DT[x.dtype], n, h, w, c, ops._stream()), "face_subsample2x")
+    return y
+
+
+def _block_fwd(blk, x, ss, offs):
+    """-> (out, saved (a1, a2)).  The stride sits on the first 1x1 (and the downsample 1x1): both read x[:, :, ::2, ::2]."""
+    planes = blk.conv1.out_channels
+    xs = _subsample(x) if blk.stride == 2 else x
+    a1 = _bn_relu(_conv1x1(xs, blk.conv1.weight, planes), ss, offs, blk.bn1)
+    a2 = _bn_relu(_conv3x3(a1, blk.conv2.weight, planes), ss, offs, blk.bn2)
+    y3 = _conv1x1(a2, blk.conv3.weight, 4 * planes)
+    if blk.downsample is not None:
+        r, bnr = _conv1x1(xs, blk.downsample[0].weight, 4 * planes), blk.downsample[1]
+    else:
+        r, bnr = x, None
+    out = torch.empty_like(y3)
+    n, c, h, w = y3.shape
+    check(lib().mas_face_join_fwd(_p(y3), _ssp(ss, offs, blk.bn3), _p(r), _ssp(ss, offs, bnr), _p(out), _DT[out.dtype], n * h * w, c,
+                                  ops._stream()), "face_join_fwd")
+    return out, (a1, a2)
+
+
+def _block_bwd(blk, x_shape, dout, dadd, out, a1, a2, ss, offs):
+    """data gradient of one Bottleneck for the rows of ``out``; x_shape: its input's (C, H, W)"""
+    planes = blk.conv1.out_channels
+    n, c, h, w = out.shape
+    m = n * h * w
+    dt = _DT[out.dtype]
+    dy3 = torch.empty_like(out)
+    dr = torch.empty_like(out)
+    bnr = blk.downsample[1] if blk.downsample is not None else None
+    check(lib().mas_face_join_bwd(_p(dout), _p(dadd), _p(out), _ssp(ss, offs, blk.bn3), _ssp(ss, offs, bnr), _p(dy3), _p(dr), dt, m, c,
+                                  ops._stream()), "face_join_bwd")
+    da2 = _conv1x1(dy3, blk.conv3.weight, planes, transpose=True)
+    dy2 = torch.empty_like(da2)
+    check(lib().mas_face_relu_bn_bwd(_p(da2), _p(a2), _ssp(ss, offs, blk.bn2), _p(dy2), dt, m, planes, ops._stream()), "face_relu_bn_bwd")
+    da1 = _conv3x3(dy2, blk.conv2.weight, planes, transpose=True)
+    dy1 = torch.empty_like(da1)
+    check(lib().mas_face_relu_bn_bwd(_p(da1), _p(a1), _ssp(ss, offs, blk.bn1), _p(dy1), dt, m, planes, ops._stream()), "face_relu_bn_bwd")
+    cin, hin, win = x_shape
+    dres = _conv1x1(dr, blk.downsample[0].weight, cin, transpose=True) if blk.downsample is not None else dr
+    dxs = _conv1x1(dy1, blk.conv1.weight, cin, residual=dres, transpose=True)        # the shortcut's gradient in the epilogue
+    if blk.stride == 2:
+        return ops.zero_stuff2x(dxs, hin, win)
+    return dxs
+
+
+def network_forward(mod, faces, ss, offs):
+    """faces [R, 3, 254, 254] NHWC -> (five features, saved tensors for the backward)"""
+    r = faces.shape[0]
+    dt = faces.dtype
+    y0 = torch.empty((r, 64, 127, 127), dtype=dt, device=faces.device, memory_format=torch.channels_last)
+    w0 = mod.conv1.weight.detach().float().contiguous()
+    check(lib().mas_face_stem_fwd(_p(faces), _p(w0), _p(y0), _DT[dt], r, ops._stream()), "face_stem_fwd")
+    z = torch.empty((r, 64, 63, 63), dtype=dt, device=faces.device, memory_format=torch.channels_last)
+    idx = torch.empty(r * 63 * 63 * 64, dtype=torch.uint8, device=faces.device)
+    check(lib().mas_face_pool_fwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(z), _p(idx), _DT[dt], r, 127, 127, 64, ops._stream()), "face_pool_fwd")
+    feats, saved, h = [y0], [], z
+    for li, blk in blocks_of(mod):
+        shape_in = tuple(h.shape[1:])
+        h, (a1, a2) = _block_fwd(blk, h, ss, offs)
+        saved.append((shape_in, a1, a2, h))
+        if blk is getattr(mod, f"layer{li}")[-1]:
+            feats.append(h)
+    return feats, (w0, idx, saved)
+
+
+def _feats_table(feats, half):
+    f = FaceFeats()
+    for i, t in enumerate(feats):
+        f.p[i] = t.data_ptr()
+        f.chw[i] = t[0].numel()
+        f.alpha[i] = ALPHAS[i]
+    f.half, f.dtype = half, _DT[feats[0].dtype]
+    return f
+
+
+def l1_forward(feats, half):
+    """[6] fp32: alpha_i * mean over (C, H, W) of the pair-summed |p0 - p1|, i = 0..4, and their sum"""
+    f = _feats_table(feats, half)
+    nws = lib().mas_face_l1_workspace(C.byref(f))
+    if nws < 0:
+        check(nws, "face_l1_workspace")
+    ws = torch.empty(max(nws, 1), dtype=torch.float32, device=feats[0].device)
+    out = torch.empty(6, dtype=torch.float32, device=feats[0].device)
+    check(lib().mas_face_l1_fwd(C.byref(f), _p(ws), _p(out), ops._stream()), "face_l1_fwd")
+    return out
+
+
+class _FaceLoss(torch.autograd.Function):
+    """img, rec -> [d_0 .. d_4, loss]: crop, stem, bn1 + ReLU + pool, 16 Bottlenecks, L1 -- ~105 launches.  Backward: the seeds of
+    the five L1 terms for the rec rows, the Bottlenecks in reverse (join, conv3^T, ReLU-BN, conv2^T, ReLU-BN, [downsample^T],
+    conv1^T with the shortcut gradient in its epilogue, [zero-stuff]), pool, stem, crop adjoint."""
+
+    @staticmethod
+    def forward(ctx, img, rec, mod, rows, n_faces, dtype):
+        faces = crop_faces(img, rec, rows, dtype)
+        ss, offs = fold_bn(mod)
+        feats, (w0, idx, saved) = network_forward(mod, faces, ss, offs)
+        half = len(rows) // 2
+        out = l1_forward(feats, half)
+        ctx.mod, ctx.rows, ctx.n, ctx.half = mod, rows, n_faces, half
+        ctx.rec_like = (rec.shape, rec.dtype)
+        ctx.idx, ctx.ss, ctx.offs, ctx.w0, ctx.feats, ctx.saved = idx, ss, offs, w0, feats, saved
+        ctx.save_for_backward(rec)
+        return out
+
+    @staticmethod
+    def backward(ctx, dl6):
+        (rec,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        row0 = ctx.n                               # the rec rows: [n, len(rows)) -- the tail
+        nb = len(ctx.rows) - row0
+        if nb <= 0:                                # n >= 6: every surviving row is a gt row
+            return None, torch.zeros_like(rec), None, None, None, None
+        mod, ss, offs, feats = ctx.mod, ctx.ss, ctx.offs, ctx.feats
+        dl6 = dl6.float().contiguous()
+        seeds = [torch.empty((nb,) + tuple(f.shape[1:]), dtype=f.dtype, device=f.device, memory_format=torch.channels_last) for f in feats]
+        f = _feats_table(feats, ctx.half)
+        sp = (C.c_void_p * 5)(*[s.data_ptr() for s in seeds])
+        check(lib().mas_face_l1_bwd(C.byref(f), row0, nb, _p(dl6), sp, ops._stream()), "face_l1_bwd")
+        blocks = blocks_of(mod)
+        d = None
+        for k in range(len(blocks) - 1, -1, -1):
+            li, blk = blocks[k]
+            shape_in, a1, a2, out = ctx.saved[k]
+            last = blk is getattr(mod, f"layer{li}")[-1]
+            d = _block_bwd(blk, shape_in, d, seeds[li] if last else None, out[row0:], a1[row0:], a2[row0:], ss, offs)
+        y0 = feats[0][row0:]
+        dy0 = torch.empty_like(y0)
+        idx = ctx.idx[row0 * 63 * 63 * 64:]
+        dt = _DT[y0.dtype]
+        check(lib().mas_face_pool_bwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(d), _p(idx), _p(seeds[0]), _p(dy0), dt, nb, 127, 127, 64, ops._stream()),
+              "face_pool_bwd")
+        dfaces = torch.empty((nb, FACE, FACE, 3), dtype=torch.float32, device=y0.device)
+        check(lib().mas_face_stem_dgrad(_p(dy0), _p(ctx.w0), _p(dfaces), dt, nb, ops._stream()), "face_stem_dgrad")
+        drec = crop_faces_bwd(dfaces, ctx.rows[row0:], rec)
+        return None, drec, None, None, None, None
+
+
+def face_loss(mod, img, rec, bbox, dtype=None):
+    """The evaluation-mode FaceLoss on the HIP path: -> [6] fp32 (five weighted feature distances and the loss), or None without
+    faces (nothing launched)."""
+    ops._require_cuda(img, "FaceLoss")
+    ops._require_cuda(rec, "FaceLoss")
+    n, rows = plan(bbox, min(img.shape[0], rec.shape[0]))
+    if n == 0:
+        return None
+    return _FaceLoss.apply(img, rec, mod, rows, n, dtype or ops.compute_dtype())

@@ -305,6 +305,39 @@ int mas_attn_decode(const void* q, const void* k_cache, const void* v_cache, voi
                     int past, int hd, int ld_q, int ld_k, int ld_v, int ld_o, long long q_bs, long long k_bs,
                     long long v_bs, long long o_bs, float scale, void* stream);
 
+/* ---- one decode step with device-resident state (MakeAScene.generate(graph=True), models/decode_graph.py): every per-token value is read
+ * from device memory, so a captured graph of the step is replayed once per token.  Step counters: int32 ctr[2] = {k, past}, k the image
+ * token the step samples, past = (prompt length) + k - 1 the cache row it appends; mas_decode_advance adds 1 to both after the step.
+ * mas_attn_decode_dev: mas_attn_decode with nq = 1 whose cache length is *past (device) and which appends the new row itself: q, k_new,
+ *   v_new are the new row's projections (element (b, h, d) at ptr[b*new_bs + h*hd + d]), the block of (b, h) writes k_new / v_new into
+ *   cache row *past and attends to rows 0 .. *past.  Same key-to-lane assignment and merge order as mas_attn_decode: the output is bit
+ *   for bit that of mas_attn_decode on a cache where the row was appended beforehand.  The grid is B*H, independent of *past; when
+ *   *past is outside [0, capacity) the kernel reads and writes nothing (o is left as it was).  hd in {16,32,64,128}; rows 16-byte aligned.
+ * mas_decode_embed: out[r, :] (fp32 [rows, D], rows = B or 2B under guidance) = img_emb[t] + (row_emb[i / n] + col_emb[i % n]),
+ *   i = *step - 1, t = tokens[(r % B) * ld_tok + i] (int64): the eager image embedding of the previous step's token.  A token outside
+ *   [0, vocab) or i outside [0, n*n) writes a NaN row and reads nothing else.  Embedding tables fp32 [*, D].
+ * mas_sample_tokens: one work-group per output row r < B, step k = *step (nothing when k is outside [0, L)).  logits fp32, row r at
+ *   logits + r*ld_logits (ld_logits may be 0: every row reads the same logits); with guided != 0 the unconditional row is uncond_off
+ *   elements further and the row is l = lu + s*(lc - lu) (fp32, no contraction; params = {temperature, s} on the device).  logits_out
+ *   (may be NULL): l goes to logits_out[r*ld_logits_out + k*V + j].  mode 2: tokens[r, k] = forced[r*ld_forced + k]; mode 0: the first
+ *   index of max l (torch.argmax); mode 1: lg = l / temperature, kth = the top_k-th largest lg (top_k <= 0 or >= V: no cut), and the
+ *   token is argmax over {j : lg_j >= kth} of lg_j - log(-log u_j) (Gumbel-max: an exact draw from softmax(lg) restricted to the kept
+ *   entries; ties at kth are kept; lowest index on equal scores), u_j from the Sampling mapping below.  tokens int64, row stride ld_tokens.
+ * Sampling mapping: seed = DEVICE pointer to int64 {seed, offset} (as for Dropout), key = (lo32(seed), hi32(seed));  u_j of row r at
+ *   step k:  counter = (j >> 2, k, r, lo32(offset)),  32-bit slot j & 3 (words x, y, z, w),  u = ((bits >> 9) + 0.5) * 2^-23
+ *   (exact in float32, in [2^-24, 1 - 2^-24]: never 0 or 1, so every score is finite).
+ *   (make-a-scene_amd/csrc/mas_philox.h: mas_sample_bits4, mas_sample_uniform.)
+ * mas_decode_advance: counters[0 .. n-1] += 1 (one thread, n <= 8), ordered after the step's kernels by the stream.                  */
+int mas_attn_decode_dev(const void* q, const void* k_new, const void* v_new, long long new_bs, void* k_cache, void* v_cache, int ld_c,
+                        long long c_bs, int capacity, void* o, long long o_bs, int dtype, int B, int H, int hd, const int32_t* past,
+                        float scale, void* stream);
+int mas_decode_embed(const int64_t* tokens, long long ld_tok, const int32_t* step, const float* img_emb, int vocab, const float* row_emb,
+                     const float* col_emb, int n, float* out, int B, int rows, int D, void* stream);
+int mas_sample_tokens(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode, int top_k,
+                      const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced, long long ld_forced,
+                      int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out, void* stream);
+int mas_decode_advance(int32_t* counters, int n, void* stream);
+
 /* ---- small NHWC helpers on the path -------------------------------------------------
  * nearest x2 upsample (F.interpolate, modules.py:56) and its adjoint (2x2 sum);
  * zero-stuffing used by the stride-2 data gradient (adjoint of modules.py:76-78).      */

@@ -72,3 +72,13 @@ MAS_HD uint32_t mas_ew_keep8(uint32_t s0, uint32_t s1, uint32_t off, uint64_t gr
     const MasU32x4 r = mas_philox4x32_10(MasU32x4{(uint32_t)group, (uint32_t)(group >> 32), 0u, off}, s0, s1);
     return mas_keep2(r.x, t) | (mas_keep2(r.y, t) << 2) | (mas_keep2(r.z, t) << 4) | (mas_keep2(r.w, t) << 6);
 }
+
+// ---- sampling mapping (mas_sample_tokens): vocabulary entry j of output row r at decode step k uses
+//        counter = (j >> 2, k, r, lo32(offset)),  key = (lo32(seed), hi32(seed)),  32-bit slot j & 3 (word x, y, z, w);
+//      u = ((bits >> 9) + 0.5) * 2^-23: 23 random bits, every step exact in float32 ((bits >> 9) + 0.5 < 2^23 needs at most 24
+//      significant bits), so u lies in [2^-24, 1 - 2^-24], strictly inside (0, 1), and -log(-log u) is finite at both ends.  (With 24
+//      bits, (2^24 - 1) + 0.5 rounds to 2^24 in float32 and u = 1 gives a +inf score.)
+MAS_HD MasU32x4 mas_sample_bits4(uint32_t s0, uint32_t s1, uint32_t off, uint32_t row, uint32_t step, uint32_t j4) {
+    return mas_philox4x32_10(MasU32x4{j4, step, row, off}, s0, s1);
+}
+MAS_HD float mas_sample_uniform(uint32_t bits) { return ((float)(bits >> 9) + 0.5f) * 1.1920928955078125e-7f; }

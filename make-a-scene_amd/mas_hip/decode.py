@@ -1,0 +1,101 @@
+"""Wrappers of the device-state decode entries (``make-a-scene_amd/csrc/decode_step.hip``; C contract in include/mas_hip.h): the kernels
+of one captured token step of ``MakeAScene.generate(graph=True)``.  Every per-token value (step, cache length, temperature, guidance
+scale, seed) is a device tensor the kernels read, so the calls below capture into a graph that is valid for every token."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import check, lib
+from .ops import _ATTN_HEAD_DIMS, _DT, _ptr, _require_cuda, _stream
+
+GREEDY, SAMPLE, FORCED = 0, 1, 2
+
+
+def attention_decode_dev(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor, n_heads: int,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qkv [B, 1, 3D] (the new row's projection, q | k | v), caches [B, cap, D], ``past`` a device int32 (one element): appends k / v of
+    the new row at cache row ``past`` and returns the context [B, 1, D] of the query over rows 0 .. past (``mas_attn_decode_dev``)."""
+    _require_cuda(qkv, "attention_decode_dev")
+    b, nq, d3 = qkv.shape
+    d = d3 // 3
+    hd = d // n_heads
+    if nq != 1 or qkv.dtype not in _DT or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
+        raise RuntimeError("attention_decode_dev: one new row; q / k / v and the caches share a dtype in {float32, bfloat16}")
+    if k_cache.shape != v_cache.shape or k_cache.shape[0] != b or k_cache.shape[2] != d or not k_cache.is_contiguous() \
+            or not v_cache.is_contiguous() or qkv.stride(2) != 1:
+        raise RuntimeError(f"attention_decode_dev: caches {tuple(k_cache.shape)} must be contiguous [B, cap, {d}]")
+    if hd not in _ATTN_HEAD_DIMS:
+        raise RuntimeError(f"attention_decode_dev: head width {hd} not in {_ATTN_HEAD_DIMS}")
+    if past.dtype != torch.int32 or past.device != qkv.device:
+        raise RuntimeError("attention_decode_dev: past is a device int32")
+    if out is None:
+        out = torch.empty((b, 1, d), dtype=qkv.dtype, device=qkv.device)
+    q = qkv[..., :d]
+    check(lib().mas_attn_decode_dev(_ptr(q), _ptr(qkv[..., d:2 * d]), _ptr(qkv[..., 2 * d:]), qkv.stride(0), _ptr(k_cache), _ptr(v_cache),
+                                    k_cache.stride(1), k_cache.stride(0), k_cache.shape[1], _ptr(out), out.stride(0), _DT[qkv.dtype], b,
+                                    n_heads, hd, _ptr(past), float(hd) ** -0.5, _stream()), "attn_decode_dev")
+    return out
+
+
+def decode_embed(tokens: torch.Tensor, step: torch.Tensor, img_emb: torch.Tensor, row_emb: torch.Tensor, col_emb: torch.Tensor,
+                 out: torch.Tensor) -> torch.Tensor:
+    """out [rows, ..., D] fp32 (rows = B, or 2B under guidance) = the embedding of tokens[r % B, step - 1] at image position step - 1
+    (``mas_decode_embed``); tokens int64 [B, n*n], step a device int32."""
+    _require_cuda(tokens, "decode_embed")
+    b, length = tokens.shape
+    d = img_emb.shape[1]
+    n = row_emb.shape[0]
+    if tokens.dtype != torch.int64 or tokens.stride(1) != 1 or length != n * n or step.dtype != torch.int32:
+        raise RuntimeError("decode_embed: tokens int64 [B, n*n] (row-major), step int32")
+    for t in (img_emb, row_emb, col_emb, out):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != d:
+            raise RuntimeError("decode_embed: fp32 contiguous embedding tables and output of width D")
+    rows = out.numel() // d
+    check(lib().mas_decode_embed(_ptr(tokens), tokens.stride(0), _ptr(step), _ptr(img_emb), img_emb.shape[0], _ptr(row_emb),
+                                 _ptr(col_emb), n, _ptr(out), b, rows, d, _stream()), "decode_embed")
+    return out
+
+
+def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, params: torch.Tensor, mode: int, *, top_k: int = 0,
+                  guided: bool = False, seed: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
+                  logits_out: Optional[torch.Tensor] = None, rows: Optional[int] = None) -> torch.Tensor:
+    """One token per row into tokens[r, *step] (``mas_sample_tokens``).  logits fp32 [R, V] with R = 2B under guidance (conditional rows
+    first, as ``generate`` stacks them) or B, or a single [1, V] / [2, V] row shared by ``rows`` output rows (row stride 0: the statistics
+    tests).  params fp32 {temperature, cond_scale}; seed int64 {seed, offset}; forced int64 [B, L] (teacher forcing); logits_out fp32
+    [B, L, V] receives the mixed row."""
+    _require_cuda(logits, "sample_tokens")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("sample_tokens: fp32 logits [R, V] with contiguous rows")
+    nb, length = tokens.shape
+    v = logits.shape[1]
+    shared = rows is not None
+    if tokens.dtype != torch.int64 or tokens.stride(1) != 1 or step.dtype != torch.int32 or params.dtype != torch.float32 or params.numel() < 2:
+        raise RuntimeError("sample_tokens: tokens int64 [B, L], step int32, params fp32 {temperature, cond_scale}")
+    if shared:
+        if rows != nb or logits.shape[0] != (2 if guided else 1):
+            raise RuntimeError("sample_tokens: a shared logits row (and its unconditional row) for every output row")
+        ld, uoff = 0, v
+    else:
+        if logits.shape[0] != (2 * nb if guided else nb):
+            raise RuntimeError(f"sample_tokens: {logits.shape[0]} logits rows for {nb} output rows (guided={guided})")
+        ld, uoff = logits.stride(0), nb * logits.stride(0)
+    if mode == SAMPLE and (seed is None or seed.dtype != torch.int64 or seed.numel() < 2):
+        raise RuntimeError("sample_tokens: sampling needs the int64 {seed, offset} tensor")
+    if mode == FORCED and (forced is None or forced.dtype != torch.int64 or forced.shape != tokens.shape or forced.stride(1) != 1):
+        raise RuntimeError("sample_tokens: teacher forcing needs int64 tokens shaped like the output")
+    if logits_out is not None and (logits_out.dtype != torch.float32 or logits_out.shape != (nb, length, v) or not logits_out.is_contiguous()):
+        raise RuntimeError("sample_tokens: logits_out fp32 contiguous [B, L, V]")
+    check(lib().mas_sample_tokens(_ptr(logits), ld, uoff, nb, v, int(guided), int(mode), int(top_k or 0), _ptr(params), _ptr(seed),
+                                  _ptr(step), length, _ptr(forced), forced.stride(0) if forced is not None else 0, _ptr(tokens),
+                                  tokens.stride(0), _ptr(logits_out), logits_out.stride(0) if logits_out is not None else 0, _stream()),
+          "sample_tokens")
+    return tokens
+
+
+def advance(counters: torch.Tensor) -> None:
+    """counters (device int32, contiguous) += 1, one thread, ordered after the step's kernels (``mas_decode_advance``)"""
+    if counters.dtype != torch.int32 or not counters.is_contiguous():
+        raise RuntimeError("decode advance: contiguous int32 counters")
+    check(lib().mas_decode_advance(_ptr(counters), counters.numel(), _stream()), "decode_advance")

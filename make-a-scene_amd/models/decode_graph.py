@@ -1,0 +1,217 @@
+"""``MakeAScene.generate(graph=True)``: KV-cached sampling as one captured graph replay per image token.
+
+The eager sampler (``MakeAScene.generate``) spends ~350 launches of host time on every token.  Here the prompt is prefilled eagerly as
+there, its keys / values are copied into static per-layer caches [rows, total_length, D], the first token is drawn eagerly by the
+sampler kernel, and every later token k = 1 .. L-1 is one replay of a graph captured once per configuration:
+
+    embed tokens[:, k-1] at image position k-1 (``mas_decode_embed``)
+    per layer: ln_in, qkv, decode attention that appends the row at past = plen + k - 1 (``mas_attn_decode_dev``), out_proj,
+               first sandwich LayerNorm + residual, ln_out, lin1, GELU, lin2, second sandwich LayerNorm + residual
+    final LayerNorm, to_logits, sampler (``mas_sample_tokens``: tokens[:, k] and the logits row k), step counters + 1
+
+The modules' own forward calls build the step (the same HIP LayerNorm / GELU kernels and library GEMMs the eager decode runs on the same
+row shapes), so teacher-forced logits equal the eager ones.  The step, the cache length, temperature, guidance scale and seed live in
+device buffers: one capture serves every token and every call with the same key (rows, guidance, sampling mode, top_k, return_logits,
+compute dtype, autocast state, device).  The graph reads the parameters and their bf16 shadows in place; an entry whose pointers moved
+(``load_state_dict`` into new storage, ``.to()``, ``invalidate_weight_cache()``) is recaptured.
+
+Tokens are drawn by Gumbel-max from Philox4x32-10 (include/mas_hip.h, "Sampling"): reproducible under ``torch.manual_seed`` or a seeded
+``generator``, but not the tokens ``torch.multinomial`` would draw (the eager path's)."""
+import warnings
+
+import torch
+
+from mas_hip import decode, ops
+
+_GEN_SEED_HIGH = 2 ** 63 - 1
+
+
+def _envelope_reason(model):
+    """why the graph path cannot run this model (None: it can); the eager path then runs, warned once per module and reason"""
+    layers = model.transformer.layers
+    attn = layers[0].attn
+    hd, rem = divmod(attn.hidden_dim, attn.num_attn_heads)
+    if rem or hd not in ops._ATTN_HEAD_DIMS:
+        return f"head width {attn.hidden_dim}/{attn.num_attn_heads} is not one of {ops._ATTN_HEAD_DIMS}"
+    for layer in layers:
+        if layer.cogview_layernorm_prescale:
+            return "cogview_layernorm_prescale layers"
+        if layer.rudalle_relax or layer.attn.rudalle_relax:
+            return "rudalle_relax layers"
+        if layer.training and max(layer.attn.attn_drop.p, layer.attn.out_drop.p, layer.mlp.dropout.p) > 0:
+            return "training mode with nonzero dropout"
+    emb = (model.image_token_embedding, model.image_row_embeddings, model.image_col_embeddings)
+    if not all(e.weight.is_cuda and e.weight.dtype == torch.float32 for e in emb):
+        return "image embeddings are not fp32 tensors on a GPU"
+    return None
+
+
+def _param_pointers(model):
+    return tuple(p.data_ptr() for p in model.parameters())
+
+
+def _pointer_signature(model, bf16_autocast):
+    """data_ptr of every parameter and, under bf16 autocast, of the bf16 shadow of every Linear whose forward reads one (the layer's own
+    dispatch rule, ``Linear.uses_bf16_shadow``, on the device the step runs on).  Fetching the shadows is the eager path's staleness
+    check: a stale shadow is recast into its own storage before anything is replayed."""
+    from .transformer import Linear
+    ptrs = list(_param_pointers(model))
+    if bf16_autocast:
+        for m in model.modules():
+            if isinstance(m, Linear) and m.uses_bf16_shadow(m.weight.is_cuda):
+                ptrs.append(ops._bf16_shadows.get(m.weight).data_ptr())
+                ptrs.append(ops._bf16_shadows.get(m.bias).data_ptr())
+    return tuple(ptrs)
+
+
+class _Entry:
+    """static buffers and the captured graph of one key"""
+
+    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig):
+        dev = model.device
+        d = model.transformer.layers[0].attn.hidden_dim
+        s, length = model.total_length, model.image_length
+        v = model.to_logits[1].out_features
+        self.b, self.rows, self.guided, self.mode, self.top_k = b, rows, guided, mode, top_k
+        self.plen = model.text_length + model.seg_length
+        self.kc = [torch.empty((rows, s, d), dtype=kv_dtype, device=dev) for _ in model.transformer.layers]
+        self.vc = [torch.empty_like(t) for t in self.kc]
+        self.x = torch.empty((rows, 1, d), dtype=torch.float32, device=dev)
+        self.tokens = torch.zeros((b, length), dtype=torch.long, device=dev)
+        self.forced = torch.zeros((b, length), dtype=torch.long, device=dev) if mode == decode.FORCED else None
+        self.logits_out = torch.empty((b, length, v), dtype=torch.float32, device=dev) if return_logits else None
+        self.params = torch.ones(2, dtype=torch.float32, device=dev)       # {temperature, cond_scale}
+        self.seed = torch.zeros(2, dtype=torch.int64, device=dev)          # {seed, offset}
+        self.ctr = torch.zeros(2, dtype=torch.int32, device=dev)           # {k, past}
+        self.sig = sig
+        self.graph = None
+
+    def rewind(self, k):
+        """counters for step k: the token k is sampled, the row plen + k - 1 appended"""
+        self.ctr[0].fill_(k)
+        self.ctr[1].fill_(self.plen + k - 1)
+
+    def sample(self, logits):
+        decode.sample_tokens(logits, self.tokens, self.ctr[0:1], self.params, self.mode, top_k=self.top_k, guided=self.guided,
+                             seed=self.seed, forced=self.forced, logits_out=self.logits_out)
+        decode.advance(self.ctr)
+
+
+def _step(model, e):
+    """one token: everything the graph holds.  Every call below is the module call the eager cached decode makes on the new row."""
+    decode.decode_embed(e.tokens, e.ctr[0:1], model.image_token_embedding.weight, model.image_row_embeddings.weight,
+                        model.image_col_embeddings.weight, e.x)
+    x = e.x
+    for li, layer in enumerate(model.transformer.layers):
+        attn = layer.attn
+        qkv = attn.qkv(layer.ln_in(x))
+        a = attn.out_drop(attn.out_proj(decode.attention_decode_dev(qkv, e.kc[li], e.vc[li], e.ctr[1:2], attn.num_attn_heads)))
+        h = layer.first_ln_sandwich(a, residual=x) if layer.cogview_sandwich_layernorm else x + a
+        m = layer.mlp(layer.ln_out(h))
+        x = layer.second_ln_sandwich(m, residual=h) if layer.cogview_sandwich_layernorm else h + m
+    e.sample(model.to_logits(model.transformer.final_ln(x))[:, 0, :].float())
+
+
+def _autocast_without_cache():
+    """the caller's autocast state with autocast's weight-cast cache off: nothing cast during the capture outlives it"""
+    if torch.is_autocast_enabled():
+        return torch.autocast("cuda", dtype=torch.get_autocast_gpu_dtype(), cache_enabled=False)
+    return torch.autocast("cuda", enabled=False, cache_enabled=False)
+
+
+def _capture(model, e):
+    """one eager warm-up step on a side stream (settles the GEMM choices and any allocation), rewind, capture the step on that stream"""
+    main = torch.cuda.current_stream()
+    side = torch.cuda.Stream(device=main.device)
+    side.wait_stream(main)
+    with torch.cuda.stream(side), _autocast_without_cache():
+        _step(model, e)
+        e.rewind(1)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side), _autocast_without_cache():
+        _step(model, e)
+    main.wait_stream(side)
+    e.graph = g
+    model.__dict__["_decode_graph_captures"] = model.__dict__.get("_decode_graph_captures", 0) + 1
+
+
+def _replay(e, n):
+    """tokens 1 .. n: the replay calls and nothing else on the host"""
+    for _ in range(n):
+        e.graph.replay()
+
+
+def _draw_seed(generator, device):
+    """{seed, offset} for the sampler, drawn from ``generator`` (any device) or torch's default CUDA generator -- on the device when
+    the generator is a CUDA one, so no host synchronisation"""
+    if generator is None:
+        return ops.drop_seed(device)
+    s = torch.randint(0, _GEN_SEED_HIGH, (2,), dtype=torch.int64, device=generator.device, generator=generator)
+    return s.to(device)
+
+
+def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits):
+    """``MakeAScene.generate(..., graph=True)``; returns None outside the envelope (the caller then runs the eager path)"""
+    reason = _envelope_reason(model)
+    if reason is not None:
+        warned = model.__dict__.setdefault("_decode_graph_warned", set())
+        if reason not in warned:
+            warned.add(reason)
+            warnings.warn(f"MakeAScene.generate(graph=True): {reason}; sampling eagerly instead", RuntimeWarning, stacklevel=3)
+        return None
+    b = text_tokens.shape[0]
+    guided = cond_scale is not None
+    rows = 2 * b if guided else b
+    mode = decode.FORCED if img_tokens is not None else (decode.GREEDY if temperature == 0 else decode.SAMPLE)
+    top_k = int(top_k) if (mode == decode.SAMPLE and top_k is not None) else 0
+    autocast = torch.is_autocast_enabled()
+    ac_dtype = torch.get_autocast_gpu_dtype() if autocast else None
+    dev = model.device
+    key = (b, guided, mode, top_k, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev))
+    sig = _pointer_signature(model, autocast and ac_dtype == torch.bfloat16)
+    graphs = model.__dict__.setdefault("_decode_graphs", {})
+    params = _param_pointers(model)
+    for k in [k for k, g in graphs.items() if g.sig[:len(params)] != params]:
+        del graphs[k]                                   # parameters moved (.to(), new storage): every entry that read the old ones goes
+    e = graphs.get(key)
+    if e is not None and e.sig != sig:                  # a buffer the graph reads has moved: never replay it
+        del graphs[key]
+        e = None
+
+    # ---- prefill: the eager path's (the training attention kernel over the prompt) ----
+    if guided:
+        text_tokens = torch.cat([text_tokens, torch.zeros_like(text_tokens)], dim=0)
+        seg_tokens = torch.cat([seg_tokens, seg_tokens], dim=0)
+    prompt = model._prompt_embeddings(text_tokens, seg_tokens)
+    bb, plen, d = prompt.shape
+    for layer in model.transformer.layers:
+        layer.attn.cache_capacity = model.total_length
+    hidden, cache = model.transformer(prompt, None, cache={}, use_cache=True)
+    logits0 = model.to_logits(hidden[:, -1:, :])[:, 0, :].float()
+    kv = [(cache[i][0], cache[i][1]) for i in range(len(model.transformer.layers))]
+    if e is None:
+        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig)
+        graphs[key] = e
+
+    # ---- per-call device state, then the static caches ----
+    e.rewind(0)
+    e.params[0].fill_(float(temperature) if mode == decode.SAMPLE else 1.0)
+    e.params[1].fill_(float(cond_scale) if guided else 0.0)
+    if mode == decode.SAMPLE:
+        e.seed.copy_(_draw_seed(generator, dev))
+    if mode == decode.FORCED:
+        e.forced.copy_(img_tokens)
+    from .transformer import _kv_backing
+    for li, (k, v) in enumerate(kv):
+        e.kc[li][:, :plen].copy_(_kv_backing(k, bb, d)[:, :plen])
+        e.vc[li][:, :plen].copy_(_kv_backing(v, bb, d)[:, :plen])
+    del cache, kv, hidden
+
+    # ---- token 0 from the prefill (eager, the same sampler kernel), tokens 1 .. L-1 by replay ----
+    e.sample(logits0)
+    if model.image_length > 1:
+        if e.graph is None:
+            _capture(model, e)
+        _replay(e, model.image_length - 1)
+    tokens = e.tokens.clone()
+    return (tokens, e.logits_out.clone()) if return_logits else tokens

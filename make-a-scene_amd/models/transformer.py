@@ -66,9 +66,14 @@ class Linear(nn.Linear):
         super()._load_from_state_dict(*args, **kwargs)
         ops.drop_weight_cache_of(self.weight, self.bias)
 
+    def uses_bf16_shadow(self, on_gpu):
+        """whether ``forward`` on an input that is (``on_gpu``) or is not on the GPU takes ``ops.linear_bf16``, which reads the bf16
+        shadows of the weight and bias, under the current autocast state (the captured decode step keys its graphs on those shadows)"""
+        return (on_gpu and self.bias is not None and torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.bfloat16
+                and self.weight.dtype == torch.float32 and self.in_features % 8 == 0 and self.out_features % 8 == 0)
+
     def forward(self, x):
-        if (x.is_cuda and self.bias is not None and torch.is_autocast_enabled() and torch.get_autocast_gpu_dtype() == torch.bfloat16
-                and self.weight.dtype == torch.float32 and self.in_features % 8 == 0 and self.out_features % 8 == 0):
+        if self.uses_bf16_shadow(x.is_cuda):
             return ops.linear_bf16(x, self.weight, self.bias)
         return super().forward(x)
 
@@ -375,9 +380,18 @@ class MakeAScene(nn.Module):
         return torch.cat((self.text_token_embedding(text_tokens) + text_pos,
                           self.seg_token_embedding(seg_tokens) + self.get_seg_pos_embeddings(seg_tokens)), dim=1)
 
+    @property
+    def decode_graph_captures(self):
+        """how many decode-step graphs ``generate(graph=True)`` has captured on this module"""
+        return self.__dict__.get("_decode_graph_captures", 0)
+
+    def release_decode_graphs(self):
+        """frees the captured decode-step graphs of ``generate(graph=True)`` and their static buffers (K/V caches, tokens, logits)"""
+        self.__dict__.pop("_decode_graphs", None)
+
     @torch.no_grad()
     def generate(self, text_tokens, seg_tokens, temperature=1.0, top_k=None, cond_scale=None, generator=None, img_tokens=None,
-                 return_logits=False):
+                 return_logits=False, *, graph=False):
         """Autoregressive sampling of the ``image_length`` image tokens given text + segmentation tokens, KV-cached: one prefill
         over the prompt (the training attention kernel), then one ``mas_attn_decode`` pass per layer and token.
         ``temperature`` 0 -> greedy; ``top_k`` keeps the k most likely tokens; ``cond_scale`` s -> classifier-free guidance
@@ -385,7 +399,16 @@ class MakeAScene(nn.Module):
         logits = l_uncond + s * (l_cond - l_uncond).  ``img_tokens`` [B, image_length]: teacher forcing (the given tokens are fed
         instead of the sampled ones -- used by the tests to compare every step's logits with the uncached forward).
         Returns the tokens [B, image_length] (int64) -- ``VQBASE.decode_code`` turns them into an image -- and, with
-        ``return_logits``, the logits [B, image_length, vocab] they were drawn from."""
+        ``return_logits``, the logits [B, image_length, vocab] they were drawn from.
+        ``graph=True``: the same sampling with every token after the first one replay of a captured decode step (models/decode_graph.py);
+        teacher-forced and greedy tokens and the logits are those of ``graph=False``, sampled tokens come from an on-device Gumbel-max
+        draw (Philox, reproducible under the same seed / ``generator``) instead of ``torch.multinomial``.  Outside its envelope (head
+        widths without a kernel, training-mode dropout, prescale / rudalle layers) it warns once and samples eagerly."""
+        if graph:
+            from .decode_graph import generate_graph
+            out = generate_graph(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits)
+            if out is not None:
+                return out
         b = text_tokens.shape[0]
         guided = cond_scale is not None
         if guided:

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""Image-token sampling on the MI355X: ``MakeAScene.generate`` eager against ``graph=True`` (one captured decode step replayed per
+token, models/decode_graph.py) at config-4 width -- 24 layers, hidden 1024, 16 heads, 256 text + 16x16 seg + 32x32 image tokens, image
+vocabulary 8192, random weights -- under bf16 autocast, B in {1, 8}, with and without classifier-free guidance (cond_scale 3.0).
+Temperature 1, top_k 256.  One JSON line.
+
+    python tools/sample_bench.py [--batch 1 8] [--runs 2] [--skip-eager]
+    python tools/sample_bench.py --profile          # one graph-path call after a warm one: run it under rocprofv3 --kernel-trace --stats
+
+ms per token = wall time of a whole call (prefill, first token and the 1023 replays, synchronised) / 1024; capture = first graph call
+minus a steady one (warm-up step, capture, graph instantiation)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "make-a-scene_amd"), ROOT):
+    sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+CFG = dict(num_layers=24, hidden_dim=1024, num_attn_heads=16, image_vocab_size=8192, seg_vocab_size=256, text_vocab_size=16384,
+           image_tokens_per_dim=32, seg_tokens_per_dim=16, text_length=256)
+
+
+def build(dev):
+    from models.transformer import MakeAScene
+    torch.manual_seed(0)
+    m = MakeAScene(**CFG).to(dev).eval()
+    return m
+
+
+def prompt(b, dev):
+    g = torch.Generator().manual_seed(b)
+    text = torch.randint(1, CFG["text_vocab_size"] - CFG["text_length"], (b, CFG["text_length"]), generator=g)
+    text[:, 200:] = 0
+    seg = torch.randint(0, CFG["seg_vocab_size"], (b, CFG["seg_tokens_per_dim"] ** 2), generator=g)
+    return text.to(dev), seg.to(dev)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--skip-eager", action="store_true")
+    ap.add_argument("--profile", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    m = build(dev)
+    L = CFG["image_tokens_per_dim"] ** 2
+    kw = dict(temperature=1.0, top_k=256)
+    if a.profile:
+        text, seg = prompt(1, dev)
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            m.generate(text, seg, cond_scale=3.0, graph=True, **kw)
+            dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, **kw))
+        print(json.dumps({"profile_call_s": round(dt, 4), "B": 1, "cond_scale": 3.0}))
+        return
+    rows = []
+    for b in a.batch:
+        text, seg = prompt(b, dev)
+        for cs in (None, 3.0):
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                first, _ = timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, **kw))
+                g = min(timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, **kw))[0] for _ in range(a.runs))
+                e = None if a.skip_eager else min(timed(lambda: m.generate(text, seg, cond_scale=cs, **kw))[0] for _ in range(max(1, a.runs - 1)))
+            r = {"B": b, "cond_scale": cs, "graph_ms_per_token": round(1e3 * g / L, 4), "graph_images_per_min": round(60 * b / g, 2),
+                 "capture_s": round(first - g, 3)}
+            if e is not None:
+                r.update(eager_ms_per_token=round(1e3 * e / L, 4), eager_images_per_min=round(60 * b / e, 2), speedup=round(e / g, 2))
+            rows.append(r)
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            m.release_decode_graphs()
+    print(json.dumps({"metric": "MakeAScene.generate, config-4 width, bf16 autocast", "tokens_per_image": L, "top_k": kw["top_k"],
+                      "device": torch.cuda.get_device_name(0), "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()

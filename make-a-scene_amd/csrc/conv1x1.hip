@@ -331,7 +331,7 @@ static bool pw_wgrad_setup(const MasConvDesc* d, PwWgradParams& p) {
     p.M = (int)M; p.Cout = d->Cout; p.Cin = d->Cin; p.n_co_t = d->Cout / 128; p.n_ci_t = d->Cin / 128;
     p.n_chunks = (int)((M + 63) / 64);
     const int tiles = p.n_co_t * p.n_ci_t;
-    int ns = mas_cdiv(2 * mas_num_cus(), tiles);                               // two work-groups per CU
+    int ns = mas_wgrad_split_start(mas_cdiv(2 * mas_num_cus(), tiles));        // two work-groups per CU
     if (ns > p.n_chunks / 2) ns = p.n_chunks / 2;                                 // at least two chunks per work-group
     if (ns > 256) ns = 256;
     if (ns < 1) ns = 1;
@@ -409,7 +409,7 @@ bool pw_f32_setup(const MasConvDesc* d, PwF32Params& p) {
     if (M <= 0 || M >= 0x7fffffffLL) return false;
     p.M = (int)M; p.Cout = d->Cout; p.Cin = d->Cin; p.n_co_t = mas_cdiv(d->Cout, PF_T); p.n_ci_t = mas_cdiv(d->Cin, PF_T);
     const int tiles = p.n_co_t * p.n_ci_t;
-    int ns = mas_cdiv(2 * mas_num_cus(), tiles);                               // ~two work-groups per CU
+    int ns = mas_wgrad_split_start(mas_cdiv(2 * mas_num_cus(), tiles));        // ~two work-groups per CU
     const int max_ns = mas_cdiv(p.M, 4 * PF_PX);                                  // at least four LDS stages per work-group
     if (ns > max_ns) ns = max_ns;
     if (ns > 256) ns = 256;

@@ -500,7 +500,7 @@ static bool s2_wgrad_setup(const MasConvDesc* d, S2WgradParams& p) {
     p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
     p.tiles_h = mas_cdiv(d->Ho, S2_TH); p.tiles_w = mas_cdiv(d->Wo, S2_TW); p.n_tiles = d->N * p.tiles_h * p.tiles_w;
     p.n_co_t = d->Cout / 128; p.n_ci_t = d->Cin / 64;
-    int ns = mas_cdiv(mas_num_cus(), p.n_co_t * p.n_ci_t);                      // one 108-KiB work-group per CU
+    int ns = mas_wgrad_split_start(mas_cdiv(mas_num_cus(), p.n_co_t * p.n_ci_t));      // one 108-KiB work-group per CU
     if (ns > p.n_tiles) ns = p.n_tiles;
     if (ns < 1) ns = 1;
     p.nsplit = ns;

@@ -744,7 +744,7 @@ int launch_tr(WgradParams p, hipStream_t s, int* splits_only) {
     p.n_pt = p.N * p.tiles_h * p.tiles_w;
     p.n_co_t = mas_cdiv(p.Cout, BCO); p.n_ci_t = mas_cdiv(p.Cin, BCI_);
     const int out_tiles = p.n_co_t * p.n_ci_t;
-    int nsplit = mas_cdiv(mas_num_cus(), out_tiles);
+    int nsplit = mas_wgrad_split_start(mas_cdiv(mas_num_cus(), out_tiles));
     if (nsplit > p.n_pt) nsplit = p.n_pt;
     if (nsplit < 1) nsplit = 1;
     p.nsplit = nsplit;
@@ -769,7 +769,7 @@ int launch(WgradParams p, hipStream_t s, int* splits_only) {
     p.n_pt = p.N * p.tiles_h * p.tiles_w;
     p.n_co_t = mas_cdiv(p.Cout, BCO); p.n_ci_t = mas_cdiv(p.Cin, BCI);
     const int out_tiles = p.n_co_t * p.n_ci_t;
-    int nsplit = mas_cdiv(mas_num_cus(), out_tiles);   // one (8- or 16-wave) work-group per CU
+    int nsplit = mas_wgrad_split_start(mas_cdiv(mas_num_cus(), out_tiles));   // one (8- or 16-wave) work-group per CU
     if (nsplit > p.n_pt) nsplit = p.n_pt;
     if (nsplit < 1) nsplit = 1;
     p.nsplit = nsplit;

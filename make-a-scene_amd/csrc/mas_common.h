@@ -27,6 +27,10 @@ void mas_note_kernel(const char* name);      // which kernel the last successful
 #define MAS_ENTER() do { (void)hipGetLastError(); } while (0)
 
 int mas_num_cus();   // compute units of the CURRENT device (cached per device)
+// Split-K count a weight-gradient setup starts from: `occupancy` (its CU-based estimate), or MAS_WGRAD_SPLITS=k when k > 0 (tests: the
+// split count as an input).  Each setup's own clamps still follow (tile count, minimum work per work-group, 256), so k never yields a
+// split count the kernel does not already accept.
+int mas_wgrad_split_start(int occupancy);
 
 // One process per GPU is the contract (include/mas_hip.h), but a second device in the same process (nn.DataParallel,
 // reference train.py:177) must still launch correctly: per-function attributes such as the dynamic-LDS limit are set

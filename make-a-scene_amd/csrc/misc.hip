@@ -24,6 +24,11 @@ int mas_num_cus() {
     return c;
 }
 
+int mas_wgrad_split_start(int occupancy) {
+    static const int k = mas_env_int("MAS_WGRAD_SPLITS", 0);            // read once per process; unset or <= 0: no override
+    return k > 0 ? k : occupancy;
+}
+
 extern "C" const char* mas_last_error(void) { return g_err; }
 static std::atomic<const char*> g_last_kernel{""};          // process-wide: the backward's launches come from autograd's own threads
 void mas_note_kernel(const char* name) { g_last_kernel.store(name, std::memory_order_relaxed); }

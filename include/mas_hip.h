@@ -490,6 +490,58 @@ int mas_face_l1_workspace(const MasFaceFeats* f);
 int mas_face_l1_fwd(const MasFaceFeats* f, float* workspace, float* out6, void* stream);
 int mas_face_l1_bwd(const MasFaceFeats* f, int row0, int nb, const float* dl6, void* const* seeds, void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * The object-aware term of the VQ-IMG objective (Make-A-Scene section 3.2): LPIPS-VGG16 on every object crop of a batch AT ONCE
+ * (object.hip).  Every used crop (both sides >= 16 px) sits at a 16-aligned origin of one of n_canvas NHWC canvases, with a zero
+ * gutter of >= 16 px after it; the real crops and the rec crops share their places in two canvas images, so one canvas batch is
+ * [2 * n_canvas, H, W, C]: real canvases first.  The thirteen convolutions run through mas_conv_fwd; after each one a ReLU + mask
+ * pass zeroes everything outside the crops' valid rectangles of that level l (origin >> l, size h >> l, w >> l), so each crop's
+ * values are those of an isolated LPIPS on it.  Activations in `dtype` (MAS_BF16 / MAS_F32), arithmetic and sums in fp32, in a fixed
+ * order (no float atomics).  Tensors of the backward are the rec half only: [n_canvas, ...].
+ *   MasObjCell: one crop: canvas n, origin (oy, ox), size h x w, image b, box corner (top, left) in the image.
+ *   MasObjPlan: DEVICE tables -- cells in (image, box) order; img_cell0 [n_images + 1] (the cells of image b are
+ *     [img_cell0[b], img_cell0[b + 1])); tiles [n_canvas][H / 16][W / 16]: the cell whose rectangle meets the 16 x 16 tile, or -1
+ *     (one at most: origins are 16-aligned and gutters >= 16 px); blk0 [5][n_cells + 1]: the first head block of every cell per
+ *     level (MAS_OBJ_HEAD_PIX(C) pixels per block).  H and W are multiples of 16.
+ *   mas_obj_canvas_fwd : canvas [2 * n_canvas, H, W, 8] = ScalingLayer(crop(img | rec)) inside the cells ((v - shift) / scale; a
+ *                        pixel of the box outside the image is v = 0), channels 3..7 and everything outside the cells 0.
+ *   mas_obj_canvas_bwd : the adjoint as a gather: drec (written in full, its own strides) = sum over the image's cells in table
+ *                        order of dcanvas [n_canvas, H, W, 8] (rec side, channels 0..2) / scale.
+ *   mas_obj_relu_fwd   : in place on y [N, H >> l, W >> l, C] (canvas index n % n_canvas): y = inside ? max(y, 0) : 0.
+ *   mas_obj_relu_bwd   : dy = a > 0 ? da : 0 over n elements (n % 8 == 0; dy may alias da).
+ *   mas_obj_pool_fwd   : y [N, H >> (l+1), W >> (l+1), C] = the 2 x 2 / stride-2 max of x [N, H >> l, W >> l, C] inside the level-(l+1)
+ *                        rectangles, 0 outside.
+ *   mas_obj_pool_bwd   : dy [N, H >> l, W >> l, C] = a > 0 ? seed + (dz at the pooled pixel if that pixel is inside and this one
+ *                        is its window's first maximum, else 0) : 0; seed and dz may be NULL.
+ *   mas_obj_head_fwd   : feat [2 * n_canvas, H >> l, W >> l, C] -> partial[blk0[l][k] .. blk0[l][k + 1]) = fixed-order partial sums
+ *                        over cell k's pixels of sum_c w_c (f_c / (|f| + 1e-10) - g_c / (|g| + 1e-10))^2 (f real, g rec).
+ *   mas_obj_finalize   : partial (the five levels one after the other) -> out[1 + k] = sum_l (cell k's sum at l) / (h_l w_l), the
+ *                        crop's LPIPS, and out[0] = sum_b (sum of its crops' values) / (n_b + 1).  One block.
+ *   mas_obj_head_bwd   : seed [n_canvas, H >> l, W >> l, C] = d out / d g at level l for dout [1 + n_cells] (device), 0 outside the
+ *                        cells.                                                                                                   */
+#define MAS_OBJ_ALIGN 16
+#define MAS_OBJ_MIN_SIDE 16
+#define MAS_OBJ_CANVAS_C 8
+#define MAS_OBJ_HEAD_PIX(C) (8192 / (C))
+typedef struct { int32_t n, oy, ox, h, w, b, top, left; } MasObjCell;
+typedef struct {
+    const MasObjCell* cells; const int32_t* img_cell0; const int32_t* tiles; const int32_t* blk0;
+    int32_t n_cells, n_images, n_canvas, H, W, pad_;
+} MasObjPlan;
+int mas_obj_canvas_fwd(const MasFaceImage* img, const MasFaceImage* rec, const MasObjPlan* p, const float* shift, const float* scale,
+                       void* canvas, int dtype, void* stream);
+int mas_obj_canvas_bwd(const void* dcanvas, int dtype, const MasObjPlan* p, const float* scale, const MasFaceImage* drec, void* stream);
+int mas_obj_relu_fwd(void* y, const MasObjPlan* p, int level, int N, int C, int dtype, void* stream);
+int mas_obj_relu_bwd(const void* da, const void* a, void* dy, long long n, int dtype, void* stream);
+int mas_obj_pool_fwd(const void* x, void* y, const MasObjPlan* p, int level, int N, int C, int dtype, void* stream);
+int mas_obj_pool_bwd(const void* a, const void* seed, const void* dz, void* dy, const MasObjPlan* p, int level, int N, int C, int dtype,
+                     void* stream);
+int mas_obj_head_fwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, int n_blocks, float* partial,
+                     void* stream);
+int mas_obj_finalize(const float* partial, const MasObjPlan* p, float* out, void* stream);
+int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, const float* dout, void* seed,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

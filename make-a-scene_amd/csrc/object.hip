@@ -1,0 +1,482 @@
+// The object-aware term of the VQ-IMG loss (Make-A-Scene section 3.2) on gfx950: LPIPS-VGG16 on every object crop of the batch at
+// once, laid out as an "atlas".
+//
+// Every used crop sits at a 16-aligned origin of an NHWC canvas with a zero gutter of >= 16 px after it; real and rec crops take the
+// same places in two canvas images.  Each 3x3 convolution of VGG16 then runs ONCE per layer for the whole batch on the library's
+// convolution kernels (mas_conv_fwd); this file holds everything else:
+//   crop -> canvas with the ScalingLayer applied (a box pixel outside the image is (0 - shift) / scale, as torchvision's zero-padding
+//     crop feeds it to the ScalingLayer), and its adjoint as a gather into d rec (overlapping boxes summed in box order);
+//   the ReLU + mask pass after every convolution: outside the valid rectangle of each crop at level l (origin >> l, size h >> l) the
+//     map is 0, so the gutter supplies exactly the zero padding an isolated crop would see and the extra pooled row / column of odd
+//     sizes disappears (16-alignment keeps every 2x2 window of a valid output inside one crop); its backward;
+//   the masked 2x2 / stride-2 max-pool and its backward (first maximum of the window, torch's tie rule; the ReLU mask of the level
+//     below and the head's gradient seed folded in);
+//   the LPIPS head per level (channel normalisation of both sides, squared difference, lin<k> weights, per-crop fixed-order partial
+//     sums), one finalize launch for the crops' values and the loss, and the head's backward for the rec side.
+// Activations are bf16 or fp32; arithmetic in fp32; no float atomics anywhere (bitwise repeatable).
+#include "mas_common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int CP = MAS_OBJ_CANVAS_C;       // canvas channels: RGB + zeros (one 16-byte vector in bf16)
+constexpr int LEVELS = 5;
+constexpr int HEAD_PASSES = 4;             // pixel passes of one head block: MAS_OBJ_HEAD_PIX(C) = HEAD_PASSES * NT / (C / 8)
+
+template <typename T> using V8 = typename Vec8<T>::type;
+
+__device__ __forceinline__ float ld_img(const MasFaceImage& im, long long off) {
+    return im.dtype == MAS_BF16 ? (float)reinterpret_cast<const bf16_t*>(im.data)[off] : reinterpret_cast<const float*>(im.data)[off];
+}
+
+// the cell whose level-l valid rectangle holds pixel (y, x) of canvas n, or -1
+__device__ __forceinline__ int cell_at(const MasObjPlan& p, int n, int y, int x, int l) {
+    const int sh = 4 - l;
+    const int t = p.tiles[((long long)n * (p.H >> 4) + (y >> sh)) * (p.W >> 4) + (x >> sh)];
+    if (t < 0) return -1;
+    const MasObjCell c = p.cells[t];
+    const int cy = y - (c.oy >> l), cx = x - (c.ox >> l);
+    return (cy >= 0 && cy < (c.h >> l) && cx >= 0 && cx < (c.w >> l)) ? t : -1;
+}
+
+__device__ __forceinline__ long long gsize() { return (long long)gridDim.x * NT; }
+__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * NT + threadIdx.x; }
+
+// one thread per canvas pixel: CP channels
+template <typename T>
+__global__ __launch_bounds__(NT) void canvas_fwd_kernel(MasFaceImage img, MasFaceImage rec, MasObjPlan p, const float* __restrict__ shift,
+                                                        const float* __restrict__ scale, T* __restrict__ out) {
+    const long long hw = (long long)p.H * p.W;
+    const long long total = 2LL * p.n_canvas * hw;
+    const float s0 = shift[0], s1 = shift[1], s2 = shift[2], k0 = scale[0], k1 = scale[1], k2 = scale[2];
+    for (long long i = gtid(); i < total; i += gsize()) {
+        const int n = (int)(i / hw);
+        const int side = n >= p.n_canvas ? 1 : 0;
+        const int y = (int)((i % hw) / p.W), x = (int)(i % p.W);
+        V8<T> v = zero8<T>();
+        const int t = cell_at(p, n - side * p.n_canvas, y, x, 0);
+        if (t >= 0) {
+            const MasObjCell c = p.cells[t];
+            const MasFaceImage& im = side ? rec : img;
+            const int iy = c.top + y - c.oy, ix = c.left + x - c.ox;
+            float px[3] = {0.0f, 0.0f, 0.0f};
+            if (c.b < im.N && iy >= 0 && iy < im.H && ix >= 0 && ix < im.W) {
+                const long long base = (long long)c.b * im.sn + (long long)iy * im.sh + (long long)ix * im.sw;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) px[ch] = ld_img(im, base + ch * im.sc);
+            }
+            v[0] = (T)((px[0] - s0) / k0);
+            v[1] = (T)((px[1] - s1) / k1);
+            v[2] = (T)((px[2] - s2) / k2);
+        }
+        st8(out + i * CP, v);
+    }
+}
+
+// one thread per pixel of d rec: the cells of its image in table order
+template <typename TD, typename TR>
+__global__ __launch_bounds__(NT) void canvas_bwd_kernel(const TD* __restrict__ dcan, MasObjPlan p, const float* __restrict__ scale,
+                                                        MasFaceImage drec) {
+    const long long hw = (long long)drec.H * drec.W;
+    const long long total = (long long)drec.N * hw;
+    const float k[3] = {scale[0], scale[1], scale[2]};
+    for (long long i = gtid(); i < total; i += gsize()) {
+        const int b = (int)(i / hw);
+        const int y = (int)((i % hw) / drec.W), x = (int)(i % drec.W);
+        float acc[3] = {0.0f, 0.0f, 0.0f};
+        if (b < p.n_images) {
+            for (int t = p.img_cell0[b]; t < p.img_cell0[b + 1]; ++t) {
+                const MasObjCell c = p.cells[t];
+                const int cy = y - c.top, cx = x - c.left;
+                if (cy < 0 || cy >= c.h || cx < 0 || cx >= c.w) continue;
+                const int py = c.oy + cy, px = c.ox + cx;
+                if (c.n < 0 || c.n >= p.n_canvas || py >= p.H || px >= p.W) continue;       // a malformed table reads nothing
+                const TD* g = dcan + (((long long)c.n * p.H + py) * p.W + px) * CP;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) acc[ch] += (float)g[ch] / k[ch];
+            }
+        }
+        TR* o = reinterpret_cast<TR*>(drec.data);
+        const long long base = (long long)b * drec.sn + (long long)y * drec.sh + (long long)x * drec.sw;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) o[base + ch * drec.sc] = (TR)acc[ch];
+    }
+}
+
+// 8 channels per thread
+template <typename T>
+__global__ __launch_bounds__(NT) void relu_fwd_kernel(T* __restrict__ y, MasObjPlan p, int l, int N, int C) {
+    const int hl = p.H >> l, wl = p.W >> l, c8 = C / 8;
+    const long long total = (long long)N * hl * wl * c8;
+    for (long long i = gtid(); i < total; i += gsize()) {
+        const long long pix = i / c8;
+        const int n = (int)(pix / ((long long)hl * wl));
+        const int yy = (int)((pix / wl) % hl), xx = (int)(pix % wl);
+        const bool in = cell_at(p, n % p.n_canvas, yy, xx, l) >= 0;
+        V8<T> v = ld8(y + i * 8);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float f = (float)v[k];
+            v[k] = (T)(in && f > 0.0f ? f : 0.0f);
+        }
+        st8(y + i * 8, v);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void relu_bwd_kernel(const T* da, const T* __restrict__ a, T* dy, long long n8) {
+    for (long long i = gtid(); i < n8; i += gsize()) {
+        const V8<T> av = ld8(a + i * 8);
+        V8<T> g = ld8(da + i * 8);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) g[k] = (float)av[k] > 0.0f ? g[k] : (T)0.0f;
+        st8(dy + i * 8, g);
+    }
+}
+
+// x at level l -> y at level l + 1; 8 channels of one output pixel per thread
+template <typename T>
+__global__ __launch_bounds__(NT) void pool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, MasObjPlan p, int l, int N, int C) {
+    const int hi = p.H >> l, wi = p.W >> l, ho = hi >> 1, wo = wi >> 1, c8 = C / 8;
+    const long long total = (long long)N * ho * wo * c8;
+    for (long long i = gtid(); i < total; i += gsize()) {
+        const int cv = (int)(i % c8);
+        const long long pix = i / c8;
+        const int n = (int)(pix / ((long long)ho * wo));
+        const int oy = (int)((pix / wo) % ho), ox = (int)(pix % wo);
+        V8<T> v = zero8<T>();
+        if (cell_at(p, n % p.n_canvas, oy, ox, l + 1) >= 0) {
+            const T* src = x + (((long long)n * hi + 2 * oy) * wi + 2 * ox) * C + cv * 8;
+            const V8<T> a = ld8(src), b = ld8(src + C), c = ld8(src + (long long)wi * C), d = ld8(src + (long long)wi * C + C);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = (T)fmaxf(fmaxf((float)a[k], (float)b[k]), fmaxf((float)c[k], (float)d[k]));
+        }
+        st8(y + i * 8, v);
+    }
+}
+
+// dy at level l (8 channels of one pixel per thread): a > 0 ? seed + routed dz : 0
+template <typename T>
+__global__ __launch_bounds__(NT) void pool_bwd_kernel(const T* __restrict__ a, const T* __restrict__ seed, const T* __restrict__ dz,
+                                                      T* __restrict__ dy, MasObjPlan p, int l, int N, int C) {
+    const int hi = p.H >> l, wi = p.W >> l, ho = hi >> 1, wo = wi >> 1, c8 = C / 8;
+    const long long total = (long long)N * hi * wi * c8;
+    for (long long i = gtid(); i < total; i += gsize()) {
+        const int cv = (int)(i % c8);
+        const long long pix = i / c8;
+        const int n = (int)(pix / ((long long)hi * wi));
+        const int yy = (int)((pix / wi) % hi), xx = (int)(pix % wi);
+        const V8<T> av = ld8(a + i * 8);
+        float g[8];
+        if (seed) {
+            const V8<T> s = ld8(seed + i * 8);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) g[k] = (float)s[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) g[k] = 0.0f;
+        }
+        const int py = yy >> 1, px = xx >> 1;
+        if (dz && py < ho && px < wo && cell_at(p, n % p.n_canvas, py, px, l + 1) >= 0) {
+            const int me = (yy & 1) * 2 + (xx & 1);
+            const T* w0 = a + (((long long)n * hi + 2 * py) * wi + 2 * px) * C + cv * 8;
+            const V8<T> q0 = ld8(w0), q1 = ld8(w0 + C), q2 = ld8(w0 + (long long)wi * C), q3 = ld8(w0 + (long long)wi * C + C);
+            const V8<T> dv = ld8(dz + (((long long)n * ho + py) * wo + px) * C + cv * 8);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                int arg = 0;
+                float m = (float)q0[k];
+                if ((float)q1[k] > m) { m = (float)q1[k]; arg = 1; }
+                if ((float)q2[k] > m) { m = (float)q2[k]; arg = 2; }
+                if ((float)q3[k] > m) { arg = 3; }
+                if (arg == me) g[k] += (float)dv[k];
+            }
+        }
+        V8<T> o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = (T)((float)av[k] > 0.0f ? g[k] : 0.0f);
+        st8(dy + i * 8, o);
+    }
+}
+
+// sum over the G lanes of one pixel group (G a power of two <= 64, groups aligned inside the wave)
+__device__ __forceinline__ float group_sum(float v, int G) {
+    for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// per pixel of one cell: the LPIPS head's value; G = C / 8 lanes per pixel, 8 channels each
+template <typename T>
+__global__ __launch_bounds__(NT) void head_fwd_kernel(const T* __restrict__ feat, const float* __restrict__ w, MasObjPlan p, int l, int C,
+                                                      float* __restrict__ partial) {
+    __shared__ float red[NT];
+    const int G = C / 8, NG = NT / G, ppb = HEAD_PASSES * NG;
+    const int* blk = p.blk0 + l * (p.n_cells + 1);
+    const int bid = blockIdx.x;
+    int lo = 0, hi = p.n_cells - 1;                 // the cell k with blk[k] <= bid < blk[k + 1]
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (blk[mid] <= bid) lo = mid; else hi = mid - 1;
+    }
+    const MasObjCell c = p.cells[lo];
+    const int hl = p.H >> l, wl = p.W >> l;
+    const int ch = c.h >> l, cw = c.w >> l, P = ch * cw;
+    const int gi = threadIdx.x / G, li = threadIdx.x % G;
+    const long long side = (long long)p.n_canvas * hl * wl * C;
+    float wv[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wv[k] = w[li * 8 + k];
+    float acc = 0.0f;
+    for (int pass = 0; pass < HEAD_PASSES; ++pass) {
+        const int q = (bid - blk[lo]) * ppb + pass * NG + gi;
+        if (q >= P) break;                          // uniform per group
+        const int yy = (c.oy >> l) + q / cw, xx = (c.ox >> l) + q % cw;
+        if (yy >= hl || xx >= wl || c.n < 0 || c.n >= p.n_canvas) break;
+        const long long off = (((long long)c.n * hl + yy) * wl + xx) * C + li * 8;
+        const V8<T> fr = ld8(feat + off), ff = ld8(feat + side + off);
+        float sr = 0.0f, sf = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { sr += (float)fr[k] * (float)fr[k]; sf += (float)ff[k] * (float)ff[k]; }
+        const float nr = sqrtf(group_sum(sr, G)) + 1e-10f, nf = sqrtf(group_sum(sf, G)) + 1e-10f;
+        float d = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float e = (float)fr[k] / nr - (float)ff[k] / nf;
+            d += e * e * wv[k];
+        }
+        acc += group_sum(d, G);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.0f;
+        for (int g = 0; g < NG; ++g) s += red[g * G];
+        partial[bid] = s;
+    }
+}
+
+__global__ __launch_bounds__(NT) void finalize_kernel(const float* __restrict__ partial, MasObjPlan p, float* __restrict__ out) {
+    __shared__ int off[LEVELS];
+    if (threadIdx.x == 0) {
+        int o = 0;
+        for (int l = 0; l < LEVELS; ++l) { off[l] = o; o += p.blk0[l * (p.n_cells + 1) + p.n_cells]; }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < p.n_cells; k += NT) {
+        const MasObjCell c = p.cells[k];
+        float v = 0.0f;
+        for (int l = 0; l < LEVELS; ++l) {
+            const int* blk = p.blk0 + l * (p.n_cells + 1);
+            float s = 0.0f;
+            for (int j = blk[k]; j < blk[k + 1]; ++j) s += partial[off[l] + j];
+            v += s / (float)((c.h >> l) * (c.w >> l));
+        }
+        out[1 + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float loss = 0.0f;
+        for (int b = 0; b < p.n_images; ++b) {
+            float s = 0.0f;
+            const int k0 = p.img_cell0[b], k1 = p.img_cell0[b + 1];
+            for (int k = k0; k < k1; ++k) s += out[1 + k];
+            loss += s / (float)(k1 - k0 + 1);
+        }
+        out[0] = loss;
+    }
+}
+
+// seed = d out / d (rec feature) at level l, every rec-side pixel of the level (0 outside the cells); G lanes per pixel
+template <typename T>
+__global__ __launch_bounds__(NT) void head_bwd_kernel(const T* __restrict__ feat, const float* __restrict__ w, MasObjPlan p, int l, int C,
+                                                      const float* __restrict__ dout, T* __restrict__ seed) {
+    const int G = C / 8, NG = NT / G;
+    const int hl = p.H >> l, wl = p.W >> l;
+    const long long npix = (long long)p.n_canvas * hl * wl;
+    const long long side = npix * C;
+    const int gi = threadIdx.x / G, li = threadIdx.x % G;
+    float wv[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wv[k] = w[li * 8 + k];
+    const float d0 = dout[0];
+    for (long long pix = (long long)blockIdx.x * NG + gi; pix < npix; pix += (long long)gridDim.x * NG) {
+        const int n = (int)(pix / ((long long)hl * wl));
+        const int yy = (int)((pix / wl) % hl), xx = (int)(pix % wl);
+        const long long off = pix * C + li * 8;
+        const int t = cell_at(p, n, yy, xx, l);
+        V8<T> o = zero8<T>();
+        if (t >= 0) {
+            const MasObjCell c = p.cells[t];
+            const int nb = p.img_cell0[c.b + 1] - p.img_cell0[c.b];
+            const float coef = (d0 / (float)(nb + 1) + dout[1 + t]) / (float)((c.h >> l) * (c.w >> l));
+            const V8<T> fr = ld8(feat + off), ff = ld8(feat + side + off);
+            float sr = 0.0f, sf = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { sr += (float)fr[k] * (float)fr[k]; sf += (float)ff[k] * (float)ff[k]; }
+            const float s = sqrtf(group_sum(sf, G));
+            const float nr = sqrtf(group_sum(sr, G)) + 1e-10f, nf = s + 1e-10f;
+            float g[8], gf = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                g[k] = -2.0f * coef * wv[k] * ((float)fr[k] / nr - (float)ff[k] / nf);         // d / d (g_c / (|g| + eps))
+                gf += g[k] * (float)ff[k];
+            }
+            gf = group_sum(gf, G);
+            const float rad = s > 0.0f ? gf / (nf * nf * s) : 0.0f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o[k] = (T)(g[k] / nf - (float)ff[k] * rad);
+        }
+        st8(seed + off, o);
+    }
+}
+
+int grid_for(long long n) {
+    long long g = (n + NT - 1) / NT;
+    const long long cap = 16LL * mas_num_cus();
+    return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
+
+bool dt_ok(int dt) { return dt == MAS_F32 || dt == MAS_BF16; }
+
+int check_plan(const MasObjPlan* p, const char* what) {
+    if (!p || !p->cells || !p->img_cell0 || !p->tiles || !p->blk0) MAS_FAIL(MAS_EINVAL, "%s: null plan table", what);
+    if (p->n_cells <= 0 || p->n_images <= 0 || p->n_canvas <= 0 || p->H <= 0 || p->W <= 0 || p->H % MAS_OBJ_ALIGN || p->W % MAS_OBJ_ALIGN)
+        MAS_FAIL(MAS_EINVAL, "%s: bad plan (%d cells, %d images, %d canvases of %d x %d)", what, p->n_cells, p->n_images, p->n_canvas, p->H, p->W);
+    return MAS_OK;
+}
+
+int check_img(const MasFaceImage* im, const char* what) {
+    if (!im || !im->data) MAS_FAIL(MAS_EINVAL, "%s: null image", what);
+    if (!dt_ok(im->dtype)) MAS_FAIL(MAS_EINVAL, "%s: dtype %d", what, im->dtype);
+    if (im->C != 3 || im->N <= 0 || im->H <= 0 || im->W <= 0) MAS_FAIL(MAS_EINVAL, "%s: need [N>0, 3, H>0, W>0], got C=%d", what, im->C);
+    return MAS_OK;
+}
+
+int check_map(const MasObjPlan* p, int level, int N, int C, int dtype, int max_level, const char* what) {
+    if (int rc = check_plan(p, what)) return rc;
+    if (level < 0 || level > max_level || N <= 0 || C <= 0 || C % 8 || !dt_ok(dtype))
+        MAS_FAIL(MAS_EINVAL, "%s: level %d, N %d, C %d, dtype %d", what, level, N, C, dtype);
+    return MAS_OK;
+}
+
+}  // namespace
+
+extern "C" int mas_obj_canvas_fwd(const MasFaceImage* img, const MasFaceImage* rec, const MasObjPlan* p, const float* shift, const float* scale,
+                                  void* canvas, int dtype, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_img(img, "obj_canvas_fwd")) return rc;
+    if (int rc = check_img(rec, "obj_canvas_fwd")) return rc;
+    if (int rc = check_plan(p, "obj_canvas_fwd")) return rc;
+    if (!shift || !scale || !canvas || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_canvas_fwd: null argument or dtype %d", dtype);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for(2LL * p->n_canvas * p->H * p->W));
+    if (dtype == MAS_F32) hipLaunchKernelGGL(canvas_fwd_kernel<float>, grid, dim3(NT), 0, s, *img, *rec, *p, shift, scale, (float*)canvas);
+    else hipLaunchKernelGGL(canvas_fwd_kernel<bf16_t>, grid, dim3(NT), 0, s, *img, *rec, *p, shift, scale, (bf16_t*)canvas);
+    MAS_CHECK_LAUNCH("obj_canvas_fwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_canvas_bwd(const void* dcanvas, int dtype, const MasObjPlan* p, const float* scale, const MasFaceImage* drec, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_img(drec, "obj_canvas_bwd")) return rc;
+    if (int rc = check_plan(p, "obj_canvas_bwd")) return rc;
+    if (!dcanvas || !scale || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_canvas_bwd: null argument or dtype %d", dtype);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for((long long)drec->N * drec->H * drec->W));
+    if (dtype == MAS_F32) {
+        if (drec->dtype == MAS_F32) hipLaunchKernelGGL((canvas_bwd_kernel<float, float>), grid, dim3(NT), 0, s, (const float*)dcanvas, *p, scale, *drec);
+        else hipLaunchKernelGGL((canvas_bwd_kernel<float, bf16_t>), grid, dim3(NT), 0, s, (const float*)dcanvas, *p, scale, *drec);
+    } else {
+        if (drec->dtype == MAS_F32) hipLaunchKernelGGL((canvas_bwd_kernel<bf16_t, float>), grid, dim3(NT), 0, s, (const bf16_t*)dcanvas, *p, scale, *drec);
+        else hipLaunchKernelGGL((canvas_bwd_kernel<bf16_t, bf16_t>), grid, dim3(NT), 0, s, (const bf16_t*)dcanvas, *p, scale, *drec);
+    }
+    MAS_CHECK_LAUNCH("obj_canvas_bwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_relu_fwd(void* y, const MasObjPlan* p, int level, int N, int C, int dtype, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_map(p, level, N, C, dtype, LEVELS - 1, "obj_relu_fwd")) return rc;
+    if (!y) MAS_FAIL(MAS_EINVAL, "obj_relu_fwd: null tensor");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for((long long)N * (p->H >> level) * (p->W >> level) * (C / 8)));
+    if (dtype == MAS_F32) hipLaunchKernelGGL(relu_fwd_kernel<float>, grid, dim3(NT), 0, s, (float*)y, *p, level, N, C);
+    else hipLaunchKernelGGL(relu_fwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (bf16_t*)y, *p, level, N, C);
+    MAS_CHECK_LAUNCH("obj_relu_fwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_relu_bwd(const void* da, const void* a, void* dy, long long n, int dtype, void* stream) {
+    MAS_ENTER();
+    if (!da || !a || !dy || n <= 0 || n % 8 || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_relu_bwd: bad argument (n %lld, dtype %d)", n, dtype);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for(n / 8));
+    if (dtype == MAS_F32) hipLaunchKernelGGL(relu_bwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)da, (const float*)a, (float*)dy, n / 8);
+    else hipLaunchKernelGGL(relu_bwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)da, (const bf16_t*)a, (bf16_t*)dy, n / 8);
+    MAS_CHECK_LAUNCH("obj_relu_bwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_pool_fwd(const void* x, void* y, const MasObjPlan* p, int level, int N, int C, int dtype, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_map(p, level, N, C, dtype, LEVELS - 2, "obj_pool_fwd")) return rc;
+    if (!x || !y) MAS_FAIL(MAS_EINVAL, "obj_pool_fwd: null tensor");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for((long long)N * (p->H >> (level + 1)) * (p->W >> (level + 1)) * (C / 8)));
+    if (dtype == MAS_F32) hipLaunchKernelGGL(pool_fwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)x, (float*)y, *p, level, N, C);
+    else hipLaunchKernelGGL(pool_fwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)x, (bf16_t*)y, *p, level, N, C);
+    MAS_CHECK_LAUNCH("obj_pool_fwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_pool_bwd(const void* a, const void* seed, const void* dz, void* dy, const MasObjPlan* p, int level, int N, int C, int dtype,
+                                void* stream) {
+    MAS_ENTER();
+    if (int rc = check_map(p, level, N, C, dtype, LEVELS - 1, "obj_pool_bwd")) return rc;
+    if (!a || !dy || (dz && level == LEVELS - 1)) MAS_FAIL(MAS_EINVAL, "obj_pool_bwd: null tensor, or a pooled gradient at the top level");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(grid_for((long long)N * (p->H >> level) * (p->W >> level) * (C / 8)));
+    if (dtype == MAS_F32)
+        hipLaunchKernelGGL(pool_bwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)a, (const float*)seed, (const float*)dz, (float*)dy, *p, level, N, C);
+    else
+        hipLaunchKernelGGL(pool_bwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)a, (const bf16_t*)seed, (const bf16_t*)dz, (bf16_t*)dy, *p,
+                           level, N, C);
+    MAS_CHECK_LAUNCH("obj_pool_bwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_head_fwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, int n_blocks, float* partial,
+                                void* stream) {
+    MAS_ENTER();
+    if (int rc = check_map(p, level, 1, C, dtype, LEVELS - 1, "obj_head_fwd")) return rc;
+    if (!feat || !w || !partial || C < 64 || C > 512 || (C & (C - 1)) || n_blocks < p->n_cells)
+        MAS_FAIL(MAS_EINVAL, "obj_head_fwd: null argument, C %d or %d blocks for %d cells", C, n_blocks, p->n_cells);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == MAS_F32) hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(n_blocks), dim3(NT), 0, s, (const float*)feat, w, *p, level, C, partial);
+    else hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(n_blocks), dim3(NT), 0, s, (const bf16_t*)feat, w, *p, level, C, partial);
+    MAS_CHECK_LAUNCH("obj_head_fwd");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_finalize(const float* partial, const MasObjPlan* p, float* out, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_plan(p, "obj_finalize")) return rc;
+    if (!partial || !out) MAS_FAIL(MAS_EINVAL, "obj_finalize: null argument");
+    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), partial, *p, out);
+    MAS_CHECK_LAUNCH("obj_finalize");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, const float* dout, void* seed,
+                                void* stream) {
+    MAS_ENTER();
+    if (int rc = check_map(p, level, 1, C, dtype, LEVELS - 1, "obj_head_bwd")) return rc;
+    if (!feat || !w || !dout || !seed || C < 64 || C > 512 || (C & (C - 1))) MAS_FAIL(MAS_EINVAL, "obj_head_bwd: null argument or C %d", C);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long npix = (long long)p->n_canvas * (p->H >> level) * (p->W >> level);
+    const dim3 grid(grid_for(npix * (C / 8)));
+    if (dtype == MAS_F32) hipLaunchKernelGGL(head_bwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)feat, w, *p, level, C, dout, (float*)seed);
+    else hipLaunchKernelGGL(head_bwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)feat, w, *p, level, C, dout, (bf16_t*)seed);
+    MAS_CHECK_LAUNCH("obj_head_bwd");
+    return MAS_OK;
+}

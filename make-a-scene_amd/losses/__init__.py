@@ -6,3 +6,4 @@ from .loss_img import VQLPIPSWithDiscriminator
 from .loss_seg import BCELossWithQuant, VQVAEWithBCELoss
 from .lpips import LPIPS
 from .lpips_with_object import LPIPSWithObject
+from .object_loss import ObjectLoss

@@ -11,8 +11,11 @@ explicit ``None`` opts out.  ``face_loss``: the reference always builds ``FaceLo
 face-embedding network whose weights are not part of this repository.  The default here (``"reference"``) builds
 ``losses.face_loss.FaceLoss`` (HIP, evaluation mode) when its checkpoint exists (``MAS_FACE_CKPT``, or the reference's path);
 otherwise it logs ONCE that the face term is absent from the objective and contributes 0.  A callable is used as given, ``None``
-opts out silently.  The arithmetic below is the reference's line for line.  ``forward`` keeps the reference's signature and return shapes
-(optimizer_idx 0 -> ``loss, (nll_loss, object_loss, face_loss)``; 1 -> ``d_loss``)."""
+opts out silently.  ``object_loss``: the object-aware term the reference left commented out (loss_img.py:49,91-106).  ``None`` (the
+default, as in the reference) keeps it a constant 0; ``"lpips"`` is ``losses.object_loss.ObjectLoss`` sharing the perceptual term's
+LPIPS weights; a callable(images, reconstructions, bbox_obj) is used as given.  The arithmetic below is the reference's line for
+line.  ``forward`` keeps the reference's signature and return shapes (optimizer_idx 0 -> ``loss, (nll_loss, object_loss,
+face_loss)``; 1 -> ``d_loss``)."""
 import warnings
 
 import torch
@@ -42,7 +45,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
     _face_warned = False
 
     def __init__(self, disc_start, codebook_weight=1.0, pixelloss_weight=1.0, disc_factor=1.0, disc_weight=1.0, perceptual_weight=1.0,
-                 perceptual_loss="lpips", face_loss="reference"):
+                 perceptual_loss="lpips", face_loss="reference", object_loss=None):
         super().__init__()
         self.codebook_weight = codebook_weight
         self.pixel_weight = pixelloss_weight
@@ -67,6 +70,14 @@ class VQLPIPSWithDiscriminator(nn.Module):
                                   "bbox_face)> to supply another, face_loss=None to silence this message")
                 face_loss = None
         self.face_loss = face_loss                    # callable(images, reconstructions, bbox_face) -> scalar, or None
+        if isinstance(object_loss, str):
+            if object_loss != "lpips":
+                raise ValueError("object_loss: None (the default), 'lpips', or a callable")
+            from .lpips import LPIPS
+            from .object_loss import ObjectLoss
+            # loss_img.py:49 of the reference: the object term shares the perceptual term's network
+            object_loss = ObjectLoss(self.perceptual_loss if isinstance(self.perceptual_loss, LPIPS) else None)
+        self.object_loss = object_loss                # callable(images, reconstructions, bbox_obj) -> scalar, or None
         self.discriminator = Discriminator().apply(weights_init)
         self.discriminator_iter_start = disc_start
         self.disc_factor = disc_factor
@@ -87,7 +98,12 @@ class VQLPIPSWithDiscriminator(nn.Module):
                 rec_loss = rec_loss + self.perceptual_weight * self.perceptual_loss(images.contiguous(), reconstructions.contiguous(), bbox_obj)
             nll_loss = torch.mean(rec_loss)
             face_loss = self.face_loss(images, reconstructions, bbox_face) if self.face_loss is not None else images.new_tensor(0)
-            object_loss = images.new_tensor(0)
+            if self.object_loss is not None:
+                if bbox_obj is None:
+                    raise ValueError("VQLPIPSWithDiscriminator: the object term needs bbox_obj (one list of boxes per image)")
+                object_loss = self.object_loss(images, reconstructions, bbox_obj)
+            else:
+                object_loss = images.new_tensor(0)
             logits_fake = self.discriminator(reconstructions.contiguous())
             g_loss = -torch.mean(logits_fake)
             d_weight = self.calculate_adaptive_weight(nll_loss, g_loss, last_layer=last_layer)

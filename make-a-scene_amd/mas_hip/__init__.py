@@ -75,6 +75,17 @@ class FaceFeats(C.Structure):
     _fields_ = [("p", C.c_void_p * 5), ("chw", C.c_int32 * 5), ("half", C.c_int32), ("dtype", C.c_int32), ("alpha", C.c_float * 5)]
 
 
+class ObjCell(C.Structure):
+    """Mirror of ``MasObjCell`` (include/mas_hip.h): one object crop of the atlas: canvas, origin, size, image, box corner."""
+    _fields_ = [(n, C.c_int32) for n in ("n", "oy", "ox", "h", "w", "b", "top", "left")]
+
+
+class ObjPlan(C.Structure):
+    """Mirror of ``MasObjPlan`` (include/mas_hip.h): the atlas's device tables and canvas geometry."""
+    _fields_ = [("cells", C.c_void_p), ("img_cell0", C.c_void_p), ("tiles", C.c_void_p), ("blk0", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("n_cells", "n_images", "n_canvas", "H", "W", "pad_")]
+
+
 _p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _SIGNATURES = {
     "mas_abi_version": (C.c_int, []),
@@ -172,6 +183,15 @@ _SIGNATURES = {
     "mas_face_l1_workspace": (_i, [C.POINTER(FaceFeats)]),
     "mas_face_l1_fwd": (_i, [C.POINTER(FaceFeats), _p, _p, _p]),
     "mas_face_l1_bwd": (_i, [C.POINTER(FaceFeats), _i, _i, _p, C.POINTER(_p), _p]),
+    "mas_obj_canvas_fwd": (_i, [C.POINTER(FaceImage), C.POINTER(FaceImage), C.POINTER(ObjPlan), _p, _p, _p, _i, _p]),
+    "mas_obj_canvas_bwd": (_i, [_p, _i, C.POINTER(ObjPlan), _p, C.POINTER(FaceImage), _p]),
+    "mas_obj_relu_fwd": (_i, [_p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p]),
+    "mas_obj_relu_bwd": (_i, [_p, _p, _p, C.c_longlong, _i, _p]),
+    "mas_obj_pool_fwd": (_i, [_p, _p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p]),
+    "mas_obj_pool_bwd": (_i, [_p, _p, _p, _p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p]),
+    "mas_obj_head_fwd": (_i, [_p, _p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p, _p]),
+    "mas_obj_finalize": (_i, [_p, C.POINTER(ObjPlan), _p, _p]),
+    "mas_obj_head_bwd": (_i, [_p, _p, C.POINTER(ObjPlan), _i, _i, _i, _p, _p, _p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

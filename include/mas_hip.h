@@ -338,6 +338,30 @@ int mas_sample_tokens(const float* logits, long long ld_logits, long long uncond
                       int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out, void* stream);
 int mas_decode_advance(int32_t* counters, int n, void* stream);
 
+/* ---- decode attention split over keys (low batch * heads: make-a-scene_amd/csrc/attn_decode_split.hip).  mas_attn_decode /
+ * mas_attn_decode_dev run one work-group per (row, head); these run nsplit of them over contiguous key ranges and a second small launch
+ * that merges their states, nq = 1 only.  With L = past + 1 visible keys, split s owns keys [s*chunk, min(L, (s+1)*chunk)), chunk =
+ * ceil(L / nsplit) rounded up to 32 keys (computed on the device); it writes its un-normalised online-softmax state {o[hd], m, l} (fp32;
+ * m = -1e30, l = 0, o = 0 when it has no key) to workspace[((b*H + h)*nsplit + s)*(hd + 2)], and the combine launch takes the common
+ * maximum, rescales and adds in split order, divides and writes o.  Fixed orders throughout: the same inputs give the same bits; the
+ * bits are not those of the unsplit kernels (another summation order, within the same tolerance).
+ * workspace: device fp32, at least B*H*nsplit*(hd + 2) floats (workspace_floats is checked: MAS_EWORKSPACE), owned by the caller, free
+ *   to reuse once the call's work on `stream` is done (calls on one stream may share it).  1 <= nsplit <= MAS_ATTN_DECODE_MAX_SPLITS;
+ *   B*H <= 65535; hd in {16,32,64,128}; rows 16-byte aligned.
+ * mas_attn_decode_split: the arguments and layout of mas_attn_decode (rows 0 .. past valid: the caller appends the new row BEFORE the
+ *   call); nq must be 1 (MAS_EINVAL otherwise).
+ * mas_attn_decode_split_dev: the arguments and contract of mas_attn_decode_dev: *past on the device, the new k / v row appended to cache
+ *   row *past by the one work-group of each (b, h) whose key range holds it, before that work-group loads any key; *past outside
+ *   [0, capacity): nothing read or written, workspace and o included.  Bit for bit the output of mas_attn_decode_split with the same
+ *   nsplit on a cache where the row was appended beforehand (the same two kernels).                                                  */
+#define MAS_ATTN_DECODE_MAX_SPLITS 32
+int mas_attn_decode_split(const void* q, const void* k_cache, const void* v_cache, void* o, int dtype, int B, int H, int nq, int past,
+                          int hd, int ld_q, int ld_k, int ld_v, int ld_o, long long q_bs, long long k_bs, long long v_bs, long long o_bs,
+                          float scale, int nsplit, float* workspace, size_t workspace_floats, void* stream);
+int mas_attn_decode_split_dev(const void* q, const void* k_new, const void* v_new, long long new_bs, void* k_cache, void* v_cache,
+                              int ld_c, long long c_bs, int capacity, void* o, long long o_bs, int dtype, int B, int H, int hd,
+                              const int32_t* past, float scale, int nsplit, float* workspace, size_t workspace_floats, void* stream);
+
 /* ---- small NHWC helpers on the path -------------------------------------------------
  * nearest x2 upsample (F.interpolate, modules.py:56) and its adjoint (2x2 sum);
  * zero-stuffing used by the stride-2 data gradient (adjoint of modules.py:76-78).      */

@@ -26,6 +26,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_AFFINE, ACT_AFFINE_SILU = 0, 1, 2
 ABI_VERSION = 9
 WLAYOUT_K64, WLAYOUT_K32, WLAYOUT_UP2 = 0, 1, 2
+ATTN_DECODE_MAX_SPLITS = 32   # MAS_ATTN_DECODE_MAX_SPLITS
 
 
 class ConvDesc(C.Structure):
@@ -145,6 +146,10 @@ _SIGNATURES = {
     "mas_sample_tokens": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _p,
                                C.c_longlong, _p]),
     "mas_decode_advance": (_i, [_p, _i, _p]),
+    "mas_attn_decode_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong,
+                                   C.c_longlong, _f, _i, _p, _sz, _p]),
+    "mas_attn_decode_split_dev": (_i, [_p, _p, _p, C.c_longlong, _p, _p, _i, C.c_longlong, _i, _p, C.c_longlong, _i, _i, _i, _i, _p, _f,
+                                       _i, _p, _sz, _p]),
     "mas_upsample2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "mas_sumpool2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "mas_zero_stuff2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),

@@ -7,20 +7,57 @@ from typing import Optional
 
 import torch
 
-from . import check, lib
+from . import ATTN_DECODE_MAX_SPLITS, check, lib
 from .ops import _ATTN_HEAD_DIMS, _DT, _ptr, _require_cuda, _stream
 
 GREEDY, SAMPLE, FORCED = 0, 1, 2
+AUTO_MAX_SPLITS = 8   # resolve_kv_splits("auto") never goes beyond: more splits measured slower
+
+
+def resolve_kv_splits(kv_splits, rows: int, n_heads: int, n_cus: int) -> int:
+    """The split count of the decode attention for ``kv_splits`` = None (1: the one-work-group kernel), an integer in
+    [1, ATTN_DECODE_MAX_SPLITS] (itself) or ``"auto"``: the largest power of two n with rows * n_heads * n <= 2 * n_cus, clamped to
+    [1, AUTO_MAX_SPLITS = 8] -- the rule the measured table of DESIGN 2.6 gives (rows * heads 16 ... 256 on 256 compute units: the best
+    or within the run-to-run spread of the best column in every row; 16 splits lost to 8 everywhere; beyond rows * heads = 2 * n_cus,
+    which nobody has measured, it is 1).  Anything else raises ValueError."""
+    if kv_splits is None:
+        return 1
+    if isinstance(kv_splits, str):
+        if kv_splits != "auto":
+            raise ValueError(f"kv_splits: {kv_splits!r} is neither an integer nor 'auto'")
+        if rows < 1 or n_heads < 1 or n_cus < 1:
+            raise ValueError(f"kv_splits='auto': rows={rows}, n_heads={n_heads}, n_cus={n_cus} must be positive")
+        n = 1
+        while 2 * n <= AUTO_MAX_SPLITS and rows * n_heads * 2 * n <= 2 * n_cus:
+            n *= 2
+        return n
+    if isinstance(kv_splits, bool) or not isinstance(kv_splits, int):
+        raise ValueError(f"kv_splits: {kv_splits!r} is neither an integer nor 'auto'")
+    if not 1 <= kv_splits <= ATTN_DECODE_MAX_SPLITS:
+        raise ValueError(f"kv_splits: {kv_splits} outside [1, {ATTN_DECODE_MAX_SPLITS}]")
+    return kv_splits
+
+
+def split_workspace_floats(rows: int, n_heads: int, head_dim: int, n_split: int) -> int:
+    """fp32 elements of the split decode attention's workspace: one {o[hd], m, l} state per (row, head, split)"""
+    return rows * n_heads * n_split * (head_dim + 2)
 
 
 def attention_decode_dev(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor, n_heads: int,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None, *, kv_splits: Optional[int] = None,
+                         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """qkv [B, 1, 3D] (the new row's projection, q | k | v), caches [B, cap, D], ``past`` a device int32 (one element): appends k / v of
-    the new row at cache row ``past`` and returns the context [B, 1, D] of the query over rows 0 .. past (``mas_attn_decode_dev``)."""
+    the new row at cache row ``past`` and returns the context [B, 1, D] of the query over rows 0 .. past (``mas_attn_decode_dev``).
+    ``kv_splits`` n > 1: the keys of every (row, head) are shared by n work-groups and merged by a second launch
+    (``mas_attn_decode_split_dev``); ``workspace``: fp32, at least ``split_workspace_floats(B, n_heads, hd, n)`` elements (a capture
+    passes a static one; allocated here when None)."""
     _require_cuda(qkv, "attention_decode_dev")
     b, nq, d3 = qkv.shape
     d = d3 // 3
     hd = d // n_heads
+    n_split = 1 if kv_splits is None else int(kv_splits)
+    if not 1 <= n_split <= ATTN_DECODE_MAX_SPLITS:
+        raise RuntimeError(f"attention_decode_dev: kv_splits {kv_splits} outside [1, {ATTN_DECODE_MAX_SPLITS}]")
     if nq != 1 or qkv.dtype not in _DT or k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype:
         raise RuntimeError("attention_decode_dev: one new row; q / k / v and the caches share a dtype in {float32, bfloat16}")
     if k_cache.shape != v_cache.shape or k_cache.shape[0] != b or k_cache.shape[2] != d or not k_cache.is_contiguous() \
@@ -33,6 +70,17 @@ def attention_decode_dev(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torc
     if out is None:
         out = torch.empty((b, 1, d), dtype=qkv.dtype, device=qkv.device)
     q = qkv[..., :d]
+    if n_split > 1:
+        need = split_workspace_floats(b, n_heads, hd, n_split)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+        elif workspace.dtype != torch.float32 or workspace.device != qkv.device or not workspace.is_contiguous() or workspace.numel() < need:
+            raise RuntimeError(f"attention_decode_dev: the workspace is a contiguous device fp32 tensor of at least {need} elements")
+        check(lib().mas_attn_decode_split_dev(_ptr(q), _ptr(qkv[..., d:2 * d]), _ptr(qkv[..., 2 * d:]), qkv.stride(0), _ptr(k_cache),
+                                              _ptr(v_cache), k_cache.stride(1), k_cache.stride(0), k_cache.shape[1], _ptr(out),
+                                              out.stride(0), _DT[qkv.dtype], b, n_heads, hd, _ptr(past), float(hd) ** -0.5, n_split,
+                                              _ptr(workspace), workspace.numel(), _stream()), "attn_decode_split_dev")
+        return out
     check(lib().mas_attn_decode_dev(_ptr(q), _ptr(qkv[..., d:2 * d]), _ptr(qkv[..., 2 * d:]), qkv.stride(0), _ptr(k_cache), _ptr(v_cache),
                                     k_cache.stride(1), k_cache.stride(0), k_cache.shape[1], _ptr(out), out.stride(0), _DT[qkv.dtype], b,
                                     n_heads, hd, _ptr(past), float(hd) ** -0.5, _stream()), "attn_decode_dev")

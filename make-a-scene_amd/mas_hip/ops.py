@@ -14,7 +14,8 @@ from typing import Optional
 
 import torch
 
-from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, BF16, F32, WLAYOUT_K64, WLAYOUT_UP2, ConvDesc, PackItem, PackTileItem, check, lib
+from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, WLAYOUT_K64, WLAYOUT_UP2, ConvDesc, PackItem, \
+    PackTileItem, check, lib
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 _state = {"compute_dtype": torch.bfloat16 if os.environ.get("MAS_COMPUTE_DTYPE", "bf16") == "bf16" else torch.float32}
@@ -1542,10 +1543,12 @@ def group_norm_act(x: torch.Tensor, norm, act: int = ACT_AFFINE_SILU, dtype: Opt
     return _GroupNormAct.apply(nhwc(x, dtype or compute_dtype()), norm.weight, norm.bias, norm.num_groups, norm.eps, act)
 
 
-def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: int, n_heads: int) -> torch.Tensor:
+def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: int, n_heads: int, *,
+                     kv_splits: Optional[int] = None) -> torch.Tensor:
     """Inference-only cached attention (``mas_attn_decode``): q [B,nq,H*hd] (the new positions), k_cache / v_cache [B,S_max,H*hd]
     whose rows 0 .. past+nq-1 are valid (the new keys / values already appended).  Query i attends to keys 0 .. past+i.
-    Returns the context [B,nq,H*hd]."""
+    Returns the context [B,nq,H*hd].  ``kv_splits`` n > 1 (nq = 1 only): the keys of every (row, head) are shared by n work-groups and
+    merged by a second launch (``mas_attn_decode_split``) -- for low B * heads; None or 1 is the one-work-group kernel."""
     _require_cuda(q, "attention_decode")
     if q.dtype not in _DT or k_cache.dtype != q.dtype or v_cache.dtype != q.dtype:
         raise RuntimeError("attention_decode: q / k / v must share a dtype in {float32, bfloat16}")
@@ -1555,6 +1558,12 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         raise RuntimeError(f"attention_decode: cache {tuple(k_cache.shape)} does not hold past={past} + nq={nq} rows of width {d}")
     if q.stride(2) != 1 or k_cache.stride(2) != 1 or v_cache.stride(2) != 1:
         raise RuntimeError("attention_decode: the last dimension must be contiguous")
+    n_split = 1 if kv_splits is None else int(kv_splits)
+    if n_split != 1:
+        if not 1 <= n_split <= ATTN_DECODE_MAX_SPLITS:
+            raise RuntimeError(f"attention_decode: kv_splits {kv_splits} outside [1, {ATTN_DECODE_MAX_SPLITS}]")
+        if nq != 1 or hd not in _ATTN_HEAD_DIMS:
+            raise RuntimeError(f"attention_decode: kv_splits > 1 takes one query row (nq = {nq}) of a head width in {_ATTN_HEAD_DIMS} (hd = {hd})")
     if hd not in _ATTN_HEAD_DIMS:
         # head widths the decode kernel does not have (see ``causal_attention``): the same arithmetic from ATen ops on the GPU (inference only)
         L = past + nq
@@ -1566,6 +1575,13 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         pr = torch.softmax(sc.masked_fill(~allowed, float("-inf")), dim=-1)
         return torch.matmul(pr, vh).transpose(1, 2).reshape(b, nq, d).to(q.dtype)
     o = torch.empty((b, nq, d), dtype=q.dtype, device=q.device)
+    if n_split > 1:
+        ws = torch.empty(b * n_heads * n_split * (hd + 2), dtype=torch.float32, device=q.device)
+        check(lib().mas_attn_decode_split(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(o), _DT[q.dtype], b, n_heads, nq, int(past), hd,
+                                          q.stride(1), k_cache.stride(1), v_cache.stride(1), o.stride(1), q.stride(0), k_cache.stride(0),
+                                          v_cache.stride(0), o.stride(0), float(hd) ** -0.5, n_split, _ptr(ws), ws.numel(), _stream()),
+              "attn_decode_split")
+        return o
     check(lib().mas_attn_decode(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(o), _DT[q.dtype], b, n_heads, nq, int(past), hd,
                                 q.stride(1), k_cache.stride(1), v_cache.stride(1), o.stride(1), q.stride(0), k_cache.stride(0),
                                 v_cache.stride(0), o.stride(0), float(hd) ** -0.5, _stream()), "attn_decode")

@@ -5,15 +5,16 @@ there, its keys / values are copied into static per-layer caches [rows, total_le
 sampler kernel, and every later token k = 1 .. L-1 is one replay of a graph captured once per configuration:
 
     embed tokens[:, k-1] at image position k-1 (``mas_decode_embed``)
-    per layer: ln_in, qkv, decode attention that appends the row at past = plen + k - 1 (``mas_attn_decode_dev``), out_proj,
+    per layer: ln_in, qkv, decode attention that appends the row at past = plen + k - 1 (``mas_attn_decode_dev``, or with
+               ``generate(kv_splits=n)`` its split-key pair ``mas_attn_decode_split_dev``), out_proj,
                first sandwich LayerNorm + residual, ln_out, lin1, GELU, lin2, second sandwich LayerNorm + residual
     final LayerNorm, to_logits, sampler (``mas_sample_tokens``: tokens[:, k] and the logits row k), step counters + 1
 
 The modules' own forward calls build the step (the same HIP LayerNorm / GELU kernels and library GEMMs the eager decode runs on the same
 row shapes), so teacher-forced logits equal the eager ones.  The step, the cache length, temperature, guidance scale and seed live in
 device buffers: one capture serves every token and every call with the same key (rows, guidance, sampling mode, top_k, return_logits,
-compute dtype, autocast state, device).  The graph reads the parameters and their bf16 shadows in place; an entry whose pointers moved
-(``load_state_dict`` into new storage, ``.to()``, ``invalidate_weight_cache()``) is recaptured.
+compute dtype, autocast state, device, decode-attention split count).  The graph reads the parameters and their bf16 shadows in place; an
+entry whose pointers moved (``load_state_dict`` into new storage, ``.to()``, ``invalidate_weight_cache()``) is recaptured.
 
 Tokens are drawn by Gumbel-max from Philox4x32-10 (include/mas_hip.h, "Sampling"): reproducible under ``torch.manual_seed`` or a seeded
 ``generator``, but not the tokens ``torch.multinomial`` would draw (the eager path's)."""
@@ -67,9 +68,14 @@ def _pointer_signature(model, bf16_autocast):
 class _Entry:
     """static buffers and the captured graph of one key"""
 
-    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig):
+    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1):
         dev = model.device
         d = model.transformer.layers[0].attn.hidden_dim
+        heads = model.transformer.layers[0].attn.num_attn_heads
+        # split decode attention (kv_splits > 1): one workspace for every layer -- they run one after the other on the graph's stream
+        self.kv_splits = kv_splits
+        self.split_ws = torch.empty(decode.split_workspace_floats(rows, heads, d // heads, kv_splits), dtype=torch.float32,
+                                    device=dev) if kv_splits > 1 else None
         s, length = model.total_length, model.image_length
         v = model.to_logits[1].out_features
         self.b, self.rows, self.guided, self.mode, self.top_k = b, rows, guided, mode, top_k
@@ -105,7 +111,8 @@ def _step(model, e):
     for li, layer in enumerate(model.transformer.layers):
         attn = layer.attn
         qkv = attn.qkv(layer.ln_in(x))
-        a = attn.out_drop(attn.out_proj(decode.attention_decode_dev(qkv, e.kc[li], e.vc[li], e.ctr[1:2], attn.num_attn_heads)))
+        a = attn.out_drop(attn.out_proj(decode.attention_decode_dev(qkv, e.kc[li], e.vc[li], e.ctr[1:2], attn.num_attn_heads,
+                                                                    kv_splits=e.kv_splits, workspace=e.split_ws)))
         h = layer.first_ln_sandwich(a, residual=x) if layer.cogview_sandwich_layernorm else x + a
         m = layer.mlp(layer.ln_out(h))
         x = layer.second_ln_sandwich(m, residual=h) if layer.cogview_sandwich_layernorm else h + m
@@ -150,8 +157,9 @@ def _draw_seed(generator, device):
     return s.to(device)
 
 
-def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits):
-    """``MakeAScene.generate(..., graph=True)``; returns None outside the envelope (the caller then runs the eager path)"""
+def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, kv_splits=1):
+    """``MakeAScene.generate(..., graph=True)``; returns None outside the envelope (the caller then runs the eager path).  ``kv_splits``:
+    the resolved split count of the decode attention (1: ``mas_attn_decode_dev``; n > 1: ``mas_attn_decode_split_dev``), part of the key"""
     reason = _envelope_reason(model)
     if reason is not None:
         warned = model.__dict__.setdefault("_decode_graph_warned", set())
@@ -167,7 +175,7 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     autocast = torch.is_autocast_enabled()
     ac_dtype = torch.get_autocast_gpu_dtype() if autocast else None
     dev = model.device
-    key = (b, guided, mode, top_k, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev))
+    key = (b, guided, mode, top_k, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev), int(kv_splits))
     sig = _pointer_signature(model, autocast and ac_dtype == torch.bfloat16)
     graphs = model.__dict__.setdefault("_decode_graphs", {})
     params = _param_pointers(model)
@@ -190,7 +198,7 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     logits0 = model.to_logits(hidden[:, -1:, :])[:, 0, :].float()
     kv = [(cache[i][0], cache[i][1]) for i in range(len(model.transformer.layers))]
     if e is None:
-        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig)
+        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits))
         graphs[key] = e
 
     # ---- per-call device state, then the static caches ----

@@ -168,7 +168,11 @@ class SelfAttention(nn.Module):
         elif cache is None and nq > 1:
             context = ops.causal_attention(qkv, h)                  # prefill: the training kernel on the whole prompt
         else:
-            context = ops.attention_decode(q, kbuf, vbuf, past, h)  # decode: one pass over the cached rows
+            n_split = getattr(self, "decode_kv_splits", None) if nq == 1 else None
+            if n_split is not None and n_split > 1:                 # generate(kv_splits=n): the cached rows shared by n work-groups
+                context = ops.attention_decode(q, kbuf, vbuf, past, h, kv_splits=n_split)
+            else:
+                context = ops.attention_decode(q, kbuf, vbuf, past, h)  # decode: one pass over the cached rows
         obuf[:, past:s_tot] = self.out_proj(context)
         hd = d // h
         view = lambda t: t[:, :s_tot].view(b, s_tot, h, hd).permute(0, 2, 1, 3)
@@ -391,7 +395,7 @@ class MakeAScene(nn.Module):
 
     @torch.no_grad()
     def generate(self, text_tokens, seg_tokens, temperature=1.0, top_k=None, cond_scale=None, generator=None, img_tokens=None,
-                 return_logits=False, *, graph=False):
+                 return_logits=False, *, graph=False, kv_splits=None):
         """Autoregressive sampling of the ``image_length`` image tokens given text + segmentation tokens, KV-cached: one prefill
         over the prompt (the training attention kernel), then one ``mas_attn_decode`` pass per layer and token.
         ``temperature`` 0 -> greedy; ``top_k`` keeps the k most likely tokens; ``cond_scale`` s -> classifier-free guidance
@@ -403,12 +407,49 @@ class MakeAScene(nn.Module):
         ``graph=True``: the same sampling with every token after the first one replay of a captured decode step (models/decode_graph.py);
         teacher-forced and greedy tokens and the logits are those of ``graph=False``, sampled tokens come from an on-device Gumbel-max
         draw (Philox, reproducible under the same seed / ``generator``) instead of ``torch.multinomial``.  Outside its envelope (head
-        widths without a kernel, training-mode dropout, prescale / rudalle layers) it warns once and samples eagerly."""
+        widths without a kernel, training-mode dropout, prescale / rudalle layers) it warns once and samples eagerly.
+        ``kv_splits``: the decode attention of the one-row steps with the keys of every (row, head) split over n work-groups and merged
+        by a second launch (``mas_attn_decode_split``), for small batches where rows * heads leaves most of the chip idle: an integer in
+        [1, 32], or "auto" (the largest power of two n <= 8 with rows * heads * n <= twice the device's compute units; rows = 2B under
+        guidance; the measured rule of DESIGN 2.6).
+        None or 1: the one-work-group kernels, the bits of every earlier release.  n > 1 changes the summation order, so logits move
+        within the kernels' tolerance and a near-tie may sample another token; at equal ``kv_splits`` the eager and the graph path
+        still agree bit for bit.  The prefill is not affected.  Integers > 1 need a head width with a decode kernel (16 / 32 / 64 / 128)."""
+        n_split = self._resolve_kv_splits(kv_splits, text_tokens.shape[0] * (2 if cond_scale is not None else 1))
         if graph:
             from .decode_graph import generate_graph
-            out = generate_graph(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits)
+            out = generate_graph(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits,
+                                 kv_splits=n_split)
             if out is not None:
                 return out
+        attns = [layer.attn for layer in self.transformer.layers]
+        saved = [a.__dict__.get("decode_kv_splits") for a in attns]
+        for a in attns:
+            a.decode_kv_splits = n_split
+        try:
+            return self._generate_eager(text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits)
+        finally:
+            for a, old in zip(attns, saved):
+                if old is None:
+                    a.__dict__.pop("decode_kv_splits", None)
+                else:
+                    a.decode_kv_splits = old
+
+    def _resolve_kv_splits(self, kv_splits, rows):
+        """``generate``'s ``kv_splits`` as a split count for ``rows`` cache rows on this model's device ("auto" on a head width without a
+        decode kernel: 1)"""
+        from mas_hip import decode, ops
+        attn = self.transformer.layers[0].attn
+        heads = attn.num_attn_heads
+        if kv_splits == "auto":
+            dev = self.device
+            if attn.hidden_dim % heads or attn.hidden_dim // heads not in ops._ATTN_HEAD_DIMS or torch.device(dev).type != "cuda":
+                return 1
+            return decode.resolve_kv_splits("auto", rows, heads, torch.cuda.get_device_properties(dev).multi_processor_count)
+        return decode.resolve_kv_splits(kv_splits, rows, heads, 1)
+
+    def _generate_eager(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits):
+        """the token loop of ``generate(graph=False)``"""
         b = text_tokens.shape[0]
         guided = cond_scale is not None
         if guided:

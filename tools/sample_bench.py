@@ -4,8 +4,14 @@ token, models/decode_graph.py) at config-4 width -- 24 layers, hidden 1024, 16 h
 vocabulary 8192, random weights -- under bf16 autocast, B in {1, 8}, with and without classifier-free guidance (cond_scale 3.0).
 Temperature 1, top_k 256.  One JSON line.
 
-    python tools/sample_bench.py [--batch 1 8] [--runs 2] [--skip-eager]
-    python tools/sample_bench.py --profile          # one graph-path call after a warm one: run it under rocprofv3 --kernel-trace --stats
+    python tools/sample_bench.py [--batch 1 8] [--runs 2] [--skip-eager] [--kv-splits 2 4 8 16 auto]
+    python tools/sample_bench.py --profile [--kv-splits 8]   # one graph-path call per split count after a warm one: run it under
+                                                             # rocprofv3 --kernel-trace --stats
+
+``--kv-splits``: beside the unsplit decode attention, the graph path with ``generate(kv_splits=n)`` for every n given (integers or
+"auto"): ``graph_ms_per_token_kv<n>`` columns, measured in the same process, every run alternating over the columns.  With
+``--profile`` the unsplit call and one call per n run back to back, so one trace holds ``attn_decode_dev_kernel`` beside
+``attn_decode_split_partial_kernel`` / ``attn_decode_split_combine_kernel`` with 24 * 1023 calls each.
 
 ms per token = wall time of a whole call (prefill, first token and the 1023 replays, synchronised) / 1024; capture = first graph call
 minus a steady one (warm-up step, capture, graph instantiation)."""
@@ -54,6 +60,8 @@ def main():
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--skip-eager", action="store_true")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--kv-splits", nargs="+", default=[], type=lambda v: v if v == "auto" else int(v),
+                    help="also time generate(graph=True, kv_splits=n) for every n given (integers or 'auto')")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = build(dev)
@@ -61,10 +69,13 @@ def main():
     kw = dict(temperature=1.0, top_k=256)
     if a.profile:
         text, seg = prompt(1, dev)
+        res = {"B": 1, "cond_scale": 3.0}
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-            m.generate(text, seg, cond_scale=3.0, graph=True, **kw)
-            dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, **kw))
-        print(json.dumps({"profile_call_s": round(dt, 4), "B": 1, "cond_scale": 3.0}))
+            for n in [None] + a.kv_splits:
+                m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, **kw)
+                dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, **kw))
+                res["profile_call_s" if n is None else f"profile_call_s_kv{n}"] = round(dt, 4)
+        print(json.dumps(res))
         return
     rows = []
     for b in a.batch:
@@ -76,6 +87,21 @@ def main():
                 e = None if a.skip_eager else min(timed(lambda: m.generate(text, seg, cond_scale=cs, **kw))[0] for _ in range(max(1, a.runs - 1)))
             r = {"B": b, "cond_scale": cs, "graph_ms_per_token": round(1e3 * g / L, 4), "graph_images_per_min": round(60 * b / g, 2),
                  "capture_s": round(first - g, 3)}
+            if a.kv_splits:
+                # every column twice (more with --runs), alternating over the columns: the spread of the repeats is the noise to beat
+                cols = [None] + a.kv_splits
+                with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                    for n in a.kv_splits:
+                        m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, **kw)          # capture
+                    times = {n: [] for n in cols}
+                    for _ in range(max(2, a.runs)):
+                        for n in cols:
+                            times[n].append(timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, **kw))[0])
+                for n in cols:
+                    tag = "none" if n is None else str(n)
+                    r[f"graph_ms_per_token_kv{tag}"] = round(1e3 * min(times[n]) / L, 4)
+                    r[f"spread_ms_per_token_kv{tag}"] = round(1e3 * (max(times[n]) - min(times[n])) / L, 4)
+                r["kv_auto_resolves_to"] = m._resolve_kv_splits("auto", 2 * b if cs is not None else b)
             if e is not None:
                 r.update(eager_ms_per_token=round(1e3 * e / L, 4), eager_images_per_min=round(60 * b / e, 2), speedup=round(e / g, 2))
             rows.append(r)

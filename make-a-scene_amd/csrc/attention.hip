@@ -11,7 +11,7 @@
 //   O^T[d][query]  += V^T . P^T         (MFMA A = V^T from a transposed LDS image, B = P^T straight from the
 //                                        score accumulators: lane = query, registers = keys)
 // fp32 online softmax (running max / sum per query), bf16 or exact-fp32 MFMA operands (template T).
-#include "mas_common.h"
+#include "mas_lds.h"
 #include "mas_philox.h"
 #include <math.h>
 #include <stdint.h>
@@ -212,13 +212,6 @@ __global__ __launch_bounds__(NT) void attn_causal_fwd_kernel(FaFwdArgs<DROP> p) 
 //   * heaviest (last) query blocks are launched first.
 // Row strides: K 2*HD+16 B (16 consecutive keys x 16 B tile the 64 banks for ds_read_b128), V 2*HD+64 B (4
 // consecutive keys x 64 B tile the 256-byte bank row for the transpose read).
-typedef __attribute__((ext_vector_type(4))) short fa_s16x4;
-__device__ __forceinline__ bf16x8 fa_tr_frag(const unsigned char* a0, const unsigned char* a1) {
-    const fa_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fa_s16x4*)a0);
-    const fa_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fa_s16x4*)a1);
-    const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return *reinterpret_cast<const bf16x8*>(&v);
-}
 
 // value of the lane 32 away (the other half of an MFMA column), through v_permlane32_swap: no LDS round trip
 __device__ __forceinline__ float fa_other_half(float x) {
@@ -366,7 +359,7 @@ __global__ __launch_bounds__(NT, 2) void attn_causal_fwd_bf16_kernel(AttnParams 
                     for (int i = 0; i < NMI; ++i) {
                         // lane s of a 16-lane group addresses key row base + (s>>2), head dims 4(s&3)..+3 of this 16-dim block
                         const unsigned char* a0 = vt + (sub * 32 + 16 * t + 4 * g + (sl >> 2)) * RSV + (i * 32 + 16 * G16 + 4 * (sl & 3)) * 2;
-                        mma16(oacc[i], fa_tr_frag(a0, a0 + 8 * RSV), pf);
+                        mma16(oacc[i], tr_frag(a0, a0 + 8 * RSV), pf);
                     }
                 }
         }
@@ -402,21 +395,9 @@ __global__ __launch_bounds__(NT, 2) void attn_causal_fwd_bf16_kernel(AttnParams 
 //     conv kernels; V: 64-byte block ^ ((key >> 1) & 1), the transpose-read pattern of conv_wgrad_dma.hip): 32 KB per work-group;
 //   * __launch_bounds__(256, 4): <= 128 VGPRs, 4 work-groups per CU.
 // The key loop is unrolled by two so that the stage offset is an immediate of every LDS read.
-typedef __attribute__((ext_vector_type(4))) int fa_i32x4;
-__device__ __forceinline__ void fa_dma16(fa_i32x4 rs, unsigned lds, int vo) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(vo), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ fa_i32x4 fa_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    fa_i32x4 r = {(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)bytes, 0x00020000};
-    r[0] = __builtin_amdgcn_readfirstlane(r[0]); r[1] = __builtin_amdgcn_readfirstlane(r[1]);
-    r[2] = __builtin_amdgcn_readfirstlane(r[2]); r[3] = __builtin_amdgcn_readfirstlane(r[3]);
-    return r;
-}
 constexpr int F2_TILE = 64 * 128;                 // one 64-key x 64-dim bf16 tile
 constexpr int F2_STAGE = 2 * F2_TILE;             // K then V
 constexpr int F2_LDS = 2 * F2_STAGE;              // 32 KB
-constexpr int F2_OOB = (int)0x80000000;
 
 // -DFA_TRACE (tools/build_file_variant.sh, never the shipped build): lane 0 of wave 3 of the heaviest work-group of (batch 0, head 0) sums
 // the 100 MHz wall clock over the phases of its key tiles (each phase closed by a read of its last result, so MFMA / LDS / VALU
@@ -455,8 +436,8 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
     const T* __restrict__ K = reinterpret_cast<const T*>(p.k) + (size_t)b * p.k_bs + (size_t)h * HD;
     const T* __restrict__ V = reinterpret_cast<const T*>(p.v) + (size_t)b * p.v_bs + (size_t)h * HD;
     // one descriptor per tensor over this (batch, head)'s rows: a key >= S lands past the end and reads as zeros
-    const fa_i32x4 rs_k = fa_rsrc(K, (unsigned)((size_t)(p.S - 1) * p.ld_k * 2 + HD * 2));
-    const fa_i32x4 rs_v = fa_rsrc(V, (unsigned)((size_t)(p.S - 1) * p.ld_v * 2 + HD * 2));
+    const i32x4 rs_k = rsrc(K, (unsigned)((size_t)(p.S - 1) * p.ld_k * 2 + HD * 2));
+    const i32x4 rs_v = rsrc(V, (unsigned)((size_t)(p.S - 1) * p.ld_v * 2 + HD * 2));
 
     bf16x8 qf[NKK];                                  // Q^T fragments (B operand): lane = query, 8 consecutive head dims
 #pragma unroll
@@ -490,8 +471,8 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
             const int key = k0 + (wave + 4 * j) * 8 + (lane >> 3);
             const bool ok = full || key < p.S;
             const unsigned dst = lds0 + stage * F2_STAGE + (wave + 4 * j) * 1024;
-            fa_dma16(rs_k, __builtin_amdgcn_readfirstlane(dst), ok ? vk[j] + uk : F2_OOB);
-            fa_dma16(rs_v, __builtin_amdgcn_readfirstlane(dst + F2_TILE), ok ? vv[j] + uv : F2_OOB);
+            dma16(rs_k, __builtin_amdgcn_readfirstlane(dst), ok ? vk[j] + uk : OOB_VOFFSET);
+            dma16(rs_v, __builtin_amdgcn_readfirstlane(dst + F2_TILE), ok ? vv[j] + uv : OOB_VOFFSET);
         }
     };
     // ---- fragment addresses (lane parts; the stage, sub-tile and k-step offsets are immediates)
@@ -642,7 +623,7 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
 #pragma unroll
                     for (int i = 0; i < NMI; ++i) {
                         const unsigned char* a0 = vt + va[i] + (sub * 32 + 16 * t) * 128;
-                        mma16(oacc[i], fa_tr_frag(a0, a0 + 8 * 128), pf);
+                        mma16(oacc[i], tr_frag(a0, a0 + 8 * 128), pf);
                     }
 #endif
                 }
@@ -1053,7 +1034,7 @@ __device__ __forceinline__ bf16x8 fa_row_frag(const unsigned char* tile, int row
 __device__ __forceinline__ bf16x8 fa_tr_tile_frag(const unsigned char* tile, int rb, int i, int g, int G16, int sl) {
     const int slot = i * 4 + G16 * 2 + ((sl & 3) >> 1), within = (sl & 1) * 8;
     const int r0 = rb + 4 * g + (sl >> 2);
-    return fa_tr_frag(tile + fa_phys(r0, slot) + within, tile + fa_phys(r0 + 8, slot) + within);
+    return tr_frag(tile + fa_phys(r0, slot) + within, tile + fa_phys(r0 + 8, slot) + within);
 }
 
 // LDS-DMA staging of a swizzled 64 x 64 tile (round 3, as in the v2 forward): 8 pieces of 8 rows; wave w moves pieces w and w + 4.
@@ -1065,13 +1046,13 @@ __device__ __forceinline__ void fa_dma_plan(int wave, int lane, int ld, int (&vo
         vo[j] = row_l * ld * 2 + (((lane & 7) ^ fa_swz(row_l)) << 4);
     }
 }
-__device__ __forceinline__ void fa_dma_tile(fa_i32x4 rs, unsigned lds_tile, int row0, int S, int ld, int wave, int lane, const int (&vo)[2]) {
+__device__ __forceinline__ void fa_dma_tile(i32x4 rs, unsigned lds_tile, int row0, int S, int ld, int wave, int lane, const int (&vo)[2]) {
     const int u0 = row0 * ld * 2;
     const bool full = row0 + 64 <= S;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const bool ok = full || (row0 + (wave + 4 * j) * 8 + (lane >> 3) < S);
-        fa_dma16(rs, __builtin_amdgcn_readfirstlane(lds_tile + (wave + 4 * j) * 1024), ok ? vo[j] + u0 : F2_OOB);
+        dma16(rs, __builtin_amdgcn_readfirstlane(lds_tile + (wave + 4 * j) * 1024), ok ? vo[j] + u0 : OOB_VOFFSET);
     }
 }
 
@@ -1119,8 +1100,8 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
     const float c2 = p.scale * 1.4426950408889634f;
 
     // Q / dO tiles: global -> LDS by DMA (round 3; no staging registers); the lse / delta rows of the tile ride through two registers
-    const fa_i32x4 rs_q = fa_rsrc(Q, (unsigned)((size_t)(p.S - 1) * p.ld * 2 + HD * 2));
-    const fa_i32x4 rs_g = fa_rsrc(G, (unsigned)((size_t)(p.S - 1) * g_stride * 2 + HD * 2));
+    const i32x4 rs_q = rsrc(Q, (unsigned)((size_t)(p.S - 1) * p.ld * 2 + HD * 2));
+    const i32x4 rs_g = rsrc(G, (unsigned)((size_t)(p.S - 1) * g_stride * 2 + HD * 2));
     int voq[2], vog[2];
     fa_dma_plan(wave, lane, p.ld, voq);
     fa_dma_plan(wave, lane, (int)g_stride, vog);
@@ -1313,8 +1294,8 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdAr
         for (int r = 0; r < 16; ++r) dq[i][r] = 0.0f;
 
     // K / V tiles: global -> LDS by DMA (no staging registers); a row >= S reads as zeros through the descriptor's bounds check
-    const fa_i32x4 rs_k = fa_rsrc(K, (unsigned)((size_t)(p.S - 1) * p.ld * 2 + HD * 2));
-    const fa_i32x4 rs_v = fa_rsrc(V, (unsigned)((size_t)(p.S - 1) * p.ld * 2 + HD * 2));
+    const i32x4 rs_k = rsrc(K, (unsigned)((size_t)(p.S - 1) * p.ld * 2 + HD * 2));
+    const i32x4 rs_v = rsrc(V, (unsigned)((size_t)(p.S - 1) * p.ld * 2 + HD * 2));
     int vo[2];
     fa_dma_plan(wave, lane, p.ld, vo);
     const int q_last = min(q0 + QT, p.S) - 1;

@@ -10,12 +10,9 @@
 // it reads the key's contiguous hd-element row (whole 128-byte lines at hd = 64 bf16), keeps an online-softmax partial
 // (m, l, o[hd]) over its keys in registers, and the 256 partials are merged once at the end (wave shuffles, then LDS).
 // Query i of the block (0 <= i < nq) sees keys 0 .. past + i (causal inside the block, transformer.py:260-263,366-370).
-#include "mas_common.h"
-#include <math.h>
+#include "attn_decode_core.h"
 
 namespace {
-
-constexpr int DNT = 256;
 
 struct DecodeParams {
     const void* q; const void* k; const void* v; void* o;
@@ -26,102 +23,22 @@ struct DecodeParams {
 };
 
 template <typename T, int HD>
-__global__ __launch_bounds__(DNT) void attn_decode_kernel(DecodeParams p) {
-    constexpr int EPU = 16 / (int)sizeof(T);
-    constexpr int NU = HD / EPU;                 // 16-byte units per row
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(DECODE_NT) void attn_decode_kernel(DecodeParams p) {
     const int iq = blockIdx.x, bh = blockIdx.y, b = bh / p.H, h = bh % p.H;
-    const int L = p.past + iq + 1;               // keys visible to this query
-
-    const T* __restrict__ Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.q_bs + (size_t)iq * p.ld_q + (size_t)h * HD;
-    const T* __restrict__ K = reinterpret_cast<const T*>(p.k) + (size_t)b * p.k_bs + (size_t)h * HD;
-    const T* __restrict__ V = reinterpret_cast<const T*>(p.v) + (size_t)b * p.v_bs + (size_t)h * HD;
-
-    float qf[HD];                                // the query, pre-scaled (transformer.py:56: q / sqrt(hd))
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(Q + u * EPU);
-        const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-        for (int j = 0; j < EPU; ++j) qf[u * EPU + j] = (float)e[j] * p.scale;
-    }
-
-    float m = -1e30f, l = 0.0f, o[HD];
-#pragma unroll
-    for (int d = 0; d < HD; ++d) o[d] = 0.0f;
-
-    for (int key = tid; key < L; key += DNT) {
-        const T* kr = K + (size_t)key * p.ld_k;
-        const T* vr = V + (size_t)key * p.ld_v;
-        float s = 0.0f;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(kr + u * EPU);
-            const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-            for (int j = 0; j < EPU; ++j) s += qf[u * EPU + j] * (float)e[j];
-        }
-        const float m_new = fmaxf(m, s);
-        const float a = __expf(m - m_new), pv = __expf(s - m_new);
-        l = l * a + pv;
-        m = m_new;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(vr + u * EPU);
-            const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-            for (int j = 0; j < EPU; ++j) o[u * EPU + j] = o[u * EPU + j] * a + pv * (float)e[j];
-        }
-    }
-
-    // ---- merge the 64 lanes of a wave: common maximum, rescale, butterfly sums (fixed order: deterministic) ----
-    float mw = m;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mw = fmaxf(mw, __shfl_xor(mw, off));
-    const float f = __expf(m - mw);              // lanes without a key: m = -1e30 -> f = 0 (or 1 when the whole wave is empty: l = o = 0)
-    l *= f;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) l += __shfl_xor(l, off);
-#pragma unroll
-    for (int d = 0; d < HD; ++d) {
-        float x = o[d] * f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-        o[d] = x;
-    }
-    // ---- merge the 4 waves through LDS ----
-    __shared__ float red[4][HD + 2];
-    if (lane == 0) {
-        red[wave][HD] = mw; red[wave][HD + 1] = l;
-    }
-    if (lane < HD / 1 && lane < 64) {
-        // lane d (and d + 64 for hd = 128) publishes o[d]: every lane holds the full sums, pick by a static unrolled select
-#pragma unroll
-        for (int d = 0; d < HD; ++d) if ((d & 63) == lane) red[wave][d] = o[d];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const float m0 = red[0][HD], m1 = red[1][HD], m2 = red[2][HD], m3 = red[3][HD];
-        const float mt = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-        const float f0 = __expf(m0 - mt), f1 = __expf(m1 - mt), f2 = __expf(m2 - mt), f3 = __expf(m3 - mt);
-        const float lt = red[0][HD + 1] * f0 + red[1][HD + 1] * f1 + red[2][HD + 1] * f2 + red[3][HD + 1] * f3;
-        const float inv = 1.0f / lt;
-        T* dst = reinterpret_cast<T*>(p.o) + (size_t)b * p.o_bs + (size_t)iq * p.ld_o + (size_t)h * HD;
-        for (int d = lane; d < HD; d += 64)
-            dst[d] = (T)((red[0][d] * f0 + red[1][d] * f1 + red[2][d] * f2 + red[3][d] * f3) * inv);
-    }
+    const T* Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.q_bs + (size_t)iq * p.ld_q + (size_t)h * HD;
+    const T* K = reinterpret_cast<const T*>(p.k) + (size_t)b * p.k_bs + (size_t)h * HD;
+    const T* V = reinterpret_cast<const T*>(p.v) + (size_t)b * p.v_bs + (size_t)h * HD;
+    T* dst = reinterpret_cast<T*>(p.o) + (size_t)b * p.o_bs + (size_t)iq * p.ld_o + (size_t)h * HD;
+    attn_decode_body<T, HD>(Q, K, V, dst, p.ld_k, p.ld_v, p.past + iq + 1, p.scale);   // query iq sees keys 0 .. past + iq
 }
 
 template <typename T>
 int launch_decode(const DecodeParams& p, int hd, hipStream_t s) {
     const dim3 grid((unsigned)p.nq, (unsigned)(p.B * p.H));
-    switch (hd) {
-        case 16: hipLaunchKernelGGL((attn_decode_kernel<T, 16>), grid, dim3(DNT), 0, s, p); break;
-        case 32: hipLaunchKernelGGL((attn_decode_kernel<T, 32>), grid, dim3(DNT), 0, s, p); break;
-        case 64: hipLaunchKernelGGL((attn_decode_kernel<T, 64>), grid, dim3(DNT), 0, s, p); break;
-        case 128: hipLaunchKernelGGL((attn_decode_kernel<T, 128>), grid, dim3(DNT), 0, s, p); break;
-        default: MAS_FAIL(MAS_EUNSUPPORTED, "attn_decode: head_dim %d not in {16,32,64,128}", hd);
-    }
+    if (!decode_dispatch_hd(hd, [&](auto hd_c) {
+            hipLaunchKernelGGL((attn_decode_kernel<T, decltype(hd_c)::value>), grid, dim3(DECODE_NT), 0, s, p);
+        }))
+        MAS_FAIL(MAS_EUNSUPPORTED, "attn_decode: head_dim %d not in {16,32,64,128}", hd);
     MAS_CHECK_LAUNCH("attn_decode");
     return MAS_OK;
 }

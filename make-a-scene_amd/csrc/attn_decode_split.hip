@@ -23,7 +23,7 @@
 // a key, so the row is read back from the cache like every other key.  No other work-group of the launch loads those bytes: the other
 // splits of the head stop before key `past`, the other heads read other columns.  When *past is outside [0, capacity) both kernels
 // return at once: nothing is read or written, the workspace and o included.
-#include "mas_common.h"
+#include "attn_decode_core.h"
 #include <limits.h>
 #include <math.h>
 
@@ -184,13 +184,8 @@ void launch_pair(const SplitParams& p, hipStream_t s) {
 
 template <typename T>
 int launch_split(const SplitParams& p, int hd, hipStream_t s, const char* name) {
-    switch (hd) {
-        case 16: launch_pair<T, 16>(p, s); break;
-        case 32: launch_pair<T, 32>(p, s); break;
-        case 64: launch_pair<T, 64>(p, s); break;
-        case 128: launch_pair<T, 128>(p, s); break;
-        default: MAS_FAIL(MAS_EUNSUPPORTED, "%s: head_dim %d not in {16,32,64,128}", name, hd);
-    }
+    if (!decode_dispatch_hd(hd, [&](auto hd_c) { launch_pair<T, decltype(hd_c)::value>(p, s); }))
+        MAS_FAIL(MAS_EUNSUPPORTED, "%s: head_dim %d not in {16,32,64,128}", name, hd);
     MAS_CHECK_LAUNCH(name);
     return MAS_OK;
 }

@@ -24,20 +24,6 @@ constexpr int BN_MAX_BLOCKS = 1024;
 // lanes in a fixed order.  C % 4 == 0, C <= 4 * NT.
 // T = float or bf16 storage.  slope != 1 (backward sums only): the gradient first goes through the derivative of the LeakyReLU that
 // follows the normalisation, g = dy * (u > 0 ? 1 : slope) with u = x * scale + shift recomputed from scale_shift.
-template <typename T> struct Quad;
-template <> struct Quad<float> {
-    static __device__ __forceinline__ f32x4 ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void st(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-};
-template <> struct Quad<bf16_t> {
-    static __device__ __forceinline__ f32x4 ld(const bf16_t* p) {
-        const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
-        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    }
-    static __device__ __forceinline__ void st(bf16_t* p, f32x4 v) {
-        *reinterpret_cast<bf16x4*>(p) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    }
-};
 
 template <typename T>
 __global__ __launch_bounds__(NT) void bn_partial_kernel(const T* __restrict__ x, const T* __restrict__ dy,

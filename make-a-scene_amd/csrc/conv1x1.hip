@@ -14,22 +14,11 @@
 //   * epilogue as in conv3x3_stream.hip: lanes l / l + 32 swap accumulator quads so that a lane owns 8 consecutive couts of its pixel:
 //     16-byte bias / residual loads and stores.
 // LDS 64 KiB, <= 128 VGPRs: two work-groups per CU.
-#include "mas_common.h"
+#include "mas_lds.h"
+#include "mas_tilewalk.h"
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) int pw_i32x4;
-__device__ __forceinline__ void pw_dma16(pw_i32x4 rs, unsigned lds, int vo) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(vo), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ pw_i32x4 pw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    pw_i32x4 r = {(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)bytes, 0x00020000};
-    r[0] = __builtin_amdgcn_readfirstlane(r[0]); r[1] = __builtin_amdgcn_readfirstlane(r[1]);
-    r[2] = __builtin_amdgcn_readfirstlane(r[2]); r[3] = __builtin_amdgcn_readfirstlane(r[3]);
-    return r;
-}
 
 struct PwParams {
     const unsigned char* a; const unsigned char* w; const float* bias; const unsigned char* res; unsigned char* y;
@@ -42,7 +31,6 @@ constexpr int PW_NT = 256;
 constexpr int PW_TILE = 128 * 128;             // 128 rows x 128 B
 constexpr int PW_STAGE = 2 * PW_TILE;          // pixel rows, then weight rows
 constexpr int PW_LDS = 2 * PW_STAGE;
-constexpr int PW_OOB = (int)0x80000000;
 
 __global__ __launch_bounds__(PW_NT, 2) void conv1x1_kernel(PwParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pw_smem[];
@@ -58,8 +46,8 @@ __global__ __launch_bounds__(PW_NT, 2) void conv1x1_kernel(PwParams p) {
     const int nt = tile % p.n_nt, mt = tile / p.n_nt;
     const int m0 = mt * 128, n0 = nt * 128;
 
-    const pw_i32x4 rs_a = pw_rsrc(p.a, (unsigned)((size_t)p.M * p.K * 2));
-    const pw_i32x4 rs_w = pw_rsrc(p.w, (unsigned)((size_t)p.n_chunks * p.rows_pad * 128));
+    const i32x4 rs_a = rsrc(p.a, (unsigned)((size_t)p.M * p.K * 2));
+    const i32x4 rs_w = rsrc(p.w, (unsigned)((size_t)p.n_chunks * p.rows_pad * 128));
 
     // ---- DMA plan: a tile is 16 pieces of 8 rows x 128 B; wave w moves pieces 4 w .. 4 w + 3 of both tiles.  LDS image lane-linear
     //      (row 8 piece + (lane >> 3), physical slot lane & 7); the pixel rows carry the swizzle on the SOURCE slot, the weight image
@@ -68,7 +56,7 @@ __global__ __launch_bounds__(PW_NT, 2) void conv1x1_kernel(PwParams p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int row = (wave * 4 + j) * 8 + (lane >> 3), ps = lane & 7;
-        va[j] = (m0 + row < p.M) ? (m0 + row) * p.K * 2 + ((ps ^ ((row >> 1) & 7)) << 4) : PW_OOB;
+        va[j] = (m0 + row < p.M) ? (m0 + row) * p.K * 2 + ((ps ^ ((row >> 1) & 7)) << 4) : OOB_VOFFSET;
     }
     const int vw = n0 * 128 + wave * 4096 + lane * 16;
     auto issue = [&](int c, int stage) {
@@ -76,8 +64,8 @@ __global__ __launch_bounds__(PW_NT, 2) void conv1x1_kernel(PwParams p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const unsigned dst = lds0 + stage * PW_STAGE + (wave * 4 + j) * 1024;
-            pw_dma16(rs_a, __builtin_amdgcn_readfirstlane(dst), va[j] + c * 128);          // (PW_OOB + c * 128 stays out of range)
-            pw_dma16(rs_w, __builtin_amdgcn_readfirstlane(dst + PW_TILE), vw + wc + j * 1024);
+            dma16(rs_a, __builtin_amdgcn_readfirstlane(dst), va[j] + c * 128);          // (OOB_VOFFSET + c * 128 stays out of range)
+            dma16(rs_w, __builtin_amdgcn_readfirstlane(dst + PW_TILE), vw + wc + j * 1024);
         }
     };
 
@@ -130,9 +118,9 @@ __global__ __launch_bounds__(PW_NT, 2) void conv1x1_kernel(PwParams p) {
 
     // ---- epilogue (bias and residual by UNCONDITIONAL buffer loads: a null pointer is a zero-length descriptor that returns zeros)
     const unsigned out_bytes = (unsigned)((size_t)p.M * p.N * 2);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.res ? p.res : p.y), 0, p.res ? out_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? (unsigned)(p.N * 4) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.res ? p.res : p.y), 0, p.res ? out_bytes : 0u, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? (unsigned)(p.N * 4) : 0u, BUFFER_RSRC_FLAGS);
     f32x4 bv[2][2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -145,7 +133,7 @@ __global__ __launch_bounds__(PW_NT, 2) void conv1x1_kernel(PwParams p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int pix = m0 + wave_m * 64 + j * 32 + l31;
-        const int obase = pix < p.M ? (pix * p.N + n0 + wave_n * 64 + 8 * g) * 2 : PW_OOB;   // the stores add (i * 32 + qp * 16) * 2
+        const int obase = pix < p.M ? (pix * p.N + n0 + wave_n * 64 + 8 * g) * 2 : OOB_VOFFSET;   // the stores add (i * 32 + qp * 16) * 2
         u32x4 rv[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -195,8 +183,8 @@ __global__ __launch_bounds__(PW_NT, 2) void wgrad1x1_kernel(PwWgradParams p) {
     const int ci_t = bid % p.n_ci_t, co_t = bid / p.n_ci_t;
     const int co0 = co_t * 128, ci0 = ci_t * 128;
 
-    const pw_i32x4 rs_dy = pw_rsrc(p.dy, (unsigned)((size_t)p.M * p.Cout * 2));
-    const pw_i32x4 rs_x = pw_rsrc(p.x, (unsigned)((size_t)p.M * p.Cin * 2));
+    const i32x4 rs_dy = rsrc(p.dy, (unsigned)((size_t)p.M * p.Cout * 2));
+    const i32x4 rs_x = rsrc(p.x, (unsigned)((size_t)p.M * p.Cin * 2));
 
     // ---- DMA plan: a chunk tile = 16 pieces of 4 pixel rows x 256 B; wave w moves pieces 4 w .. 4 w + 3 of both tensors.  Lane: pixel
     //      lane >> 4 of the piece, physical 64-byte block (lane >> 2) & 3 holding LOGICAL block ^ (pixel & 3), 16-byte slot lane & 3
@@ -208,8 +196,8 @@ __global__ __launch_bounds__(PW_NT, 2) void wgrad1x1_kernel(PwWgradParams p) {
             const int pix = c * 64 + (wave * 4 + j) * 4 + lp;
             const bool ok = pix < p.M;
             const unsigned dst = lds0 + stage * PW_STAGE + (wave * 4 + j) * 1024;
-            pw_dma16(rs_dy, __builtin_amdgcn_readfirstlane(dst), ok ? (pix * p.Cout + co0) * 2 + lsrc : PW_OOB);
-            pw_dma16(rs_x, __builtin_amdgcn_readfirstlane(dst + PW_TILE), ok ? (pix * p.Cin + ci0) * 2 + lsrc : PW_OOB);
+            dma16(rs_dy, __builtin_amdgcn_readfirstlane(dst), ok ? (pix * p.Cout + co0) * 2 + lsrc : OOB_VOFFSET);
+            dma16(rs_x, __builtin_amdgcn_readfirstlane(dst + PW_TILE), ok ? (pix * p.Cin + ci0) * 2 + lsrc : OOB_VOFFSET);
         }
     };
     // ---- transpose-read lane addressing: pixel 8 g + (sl >> 2) (+ 4 for the second read) of a 16-pixel k-step, channels
@@ -221,13 +209,7 @@ __global__ __launch_bounds__(PW_NT, 2) void wgrad1x1_kernel(PwWgradParams p) {
         a_off[i] = (8 * g + t4) * 256 + (((wave_co * 2 + i) ^ t4) << 6) + 32 * G16 + 8 * (sl & 3);
         b_off[i] = PW_TILE + (8 * g + t4) * 256 + (((wave_ci * 2 + i) ^ t4) << 6) + 32 * G16 + 8 * (sl & 3);
     }
-    auto tr = [](const unsigned char* a0) {
-        typedef __attribute__((ext_vector_type(4))) short s16x4_;
-        const s16x4_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)a0);
-        const s16x4_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_*)(a0 + 4 * 256));
-        const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        return *reinterpret_cast<const bf16x8*>(&v);
-    };
+    auto tr = [](const unsigned char* a0) { return tr_frag(a0, a0 + 4 * 256); };
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -314,8 +296,7 @@ int mas_conv1x1_try(const MasConvDesc* d, const void* x, const void* w_packed, c
         mas_attr_done(attr, attr_bit);
     }
     const long long grid = (M + 127) / 128 * p.n_nt;
-    static const int bands = mas_env_int("MAS_CONV_XCD_BANDS", 1);
-    p.xcd_bands = (bands && p.n_nt > 1 && grid % 8 == 0) ? 1 : 0;
+    p.xcd_bands = (mas_xcd_bands_enabled() && p.n_nt > 1 && grid % 8 == 0) ? 1 : 0;
     hipLaunchKernelGGL(conv1x1_kernel, dim3((unsigned)grid), dim3(PW_NT), PW_LDS, s, p);
     MAS_CHECK_LAUNCH("conv1x1");
     return 1;

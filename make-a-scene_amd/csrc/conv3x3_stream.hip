@@ -18,13 +18,11 @@
 // All waits are COUNTED (`s_waitcnt vmcnt(N)` + raw `s_barrier`): in-order VMEM retirement finishes the weight DMA of the
 // next stage and leaves the N younger patch / store operations in flight across the barrier.
 // LDS: 2 x 41 KiB patch + 2 x 32 KiB weights = 146 KiB, one 512-thread work-group per CU, 2 waves per SIMD.
-#include "mas_common.h"
+#include "mas_lds.h"
+#include "mas_tilewalk.h"
 #include <utility>
 
 namespace {
-
-template <int... I, typename F>
-__device__ __forceinline__ void s_static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 struct StreamParams {
     unsigned long long* dbg;                   // -DS_TIMELINE builds only (tools/timeline_stream.py): s_memtime stamps of one work-group
@@ -32,7 +30,7 @@ struct StreamParams {
     int N, H, W, Cin, Ho, Wo, Cout;
     int Hl, Wl, pad_top, pad_left, upsample, act;
     int n_chunks, Cout_pad, tiles_h, tiles_w, n_ct;
-    int xcd_bands;                             // 1: every XCD walks its own contiguous eighth of the tile list (conv3x3_wide.hip has the reasoning)
+    int xcd_bands;                             // 1: every XCD walks its own contiguous eighth of the tile list (mas_tilewalk.h)
 };
 
 constexpr int S_PWL = 18;                      // patch pitch in pixels ((16-1)+3)
@@ -50,11 +48,9 @@ template <int TH> struct SGeo {
 };
 constexpr int S_WT = 128 * 128;                // one tap-step weight tile: 128 couts x 128 B
 constexpr int S_WSTAGE = 2 * S_WT;
-constexpr int S_OOB = (int)0x80000000;         // voffset beyond any descriptor's num_records
 
 #ifndef S_ABL_NOBARRIER
-#define S_WAIT_BARRIER(N) do { asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                               asm volatile("" ::: "memory"); } while (0)
+#define S_WAIT_BARRIER(N) WAIT_BARRIER(N)
 #else   // timing experiment only (races): what do the 9 work-group barriers per pair cost?
 #define S_WAIT_BARRIER(N) do { asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); asm volatile("" ::: "memory"); } while (0)
 #endif
@@ -104,9 +100,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
 
     const size_t img_bytes = (size_t)p.H * p.W * p.Cin * 2;
     const unsigned out_bytes = (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.res ? p.res : p.y), 0, p.res ? out_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? (unsigned)(p.Cout * 4) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.res ? p.res : p.y), 0, p.res ? out_bytes : 0u, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? (unsigned)(p.Cout * 4) : 0u, BUFFER_RSRC_FLAGS);
 
     // ---- tiles: persistent work-group, static stride -------------------------------------------------------------
     const int total_tiles = p.N * p.tiles_h * p.tiles_w * p.n_ct;
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
             const bool inb = live && (ih >= 0) && (ih < p.Hl) && (iw >= 0) && (iw < p.Wl);
             if (p.upsample) { ih >>= 1; iw >>= 1; }
             const int sl = (lane & 7) ^ ((pc >> 1) & 7);
-            vo[i] = inb ? ((ih * p.W + iw) * p.Cin + sl * 8) * 2 : S_OOB;
+            vo[i] = inb ? ((ih * p.W + iw) * p.Cin + sl * 8) * 2 : OOB_VOFFSET;
             inb_mask |= inb ? (1u << i) : 0u;
         }
     };
@@ -153,7 +149,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
     //  "pending flat", and from then on every `s_waitcnt lgkmcnt` in front of an MFMA becomes lgkmcnt(0) -- the
     //  software-pipelined fragment reads stop overlapping.  `buffer_load ... lds` only touches vmcnt.)
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.w), 0,
-                                                                           (unsigned)(9 * p.n_chunks * p.Cout_pad * 128), 0x00020000);
+                                                                           (unsigned)(9 * p.n_chunks * p.Cout_pad * 128), BUFFER_RSRC_FLAGS);
     const int wlane = lane * 16;
     const int wstride = p.Cout_pad * 128;                  // one tap-step of the packed image ([chunk][tap][Cout_pad][128 B])
     const int wpiece = (wave >> 2) * wstride + (wave & 3) * 4096;   // this wave's 4 pieces: step t0 + (wave >> 2), rows (wave & 3)*32..+31
@@ -239,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
     u32x4 outp[G::NST];
     int ooff[G::NJ];
 #pragma unroll
-    for (int j = 0; j < G::NJ; ++j) ooff[j] = S_OOB;
+    for (int j = 0; j < G::NJ; ++j) ooff[j] = OOB_VOFFSET;
     bool pending_out = false;
     bool imm_stores = false;                    // the previous tile's epilogue issued its 8 stores directly (they may stay in flight)
 #pragma unroll
@@ -254,14 +250,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
     };
 
     // ---- prologue -----------------------------------------------------------------------------------------------------
-    int tile = blockIdx.x;                      // grid <= total_tiles
-    int step = (int)gridDim.x, tile_end = total_tiles;
-    if (p.xcd_bands && (gridDim.x & 7) == 0) {  // work-group b runs on XCD b % 8: the cout tiles that share a patch (consecutive tile ids) on ONE XCD
-        const int xcd = blockIdx.x & 7;
-        step = (int)(gridDim.x >> 3);
-        tile = (int)(((long long)total_tiles * xcd) >> 3) + (int)(blockIdx.x >> 3);
-        tile_end = (int)(((long long)total_tiles * (xcd + 1)) >> 3);
-    }
+    int tile, step, tile_end;                   // plain or banded tile walk (mas_tilewalk.h); grid <= total_tiles
+    xcd_band_walk(total_tiles, p.xcd_bands, tile, step, tile_end);
     Tile cur = decode(tile);
     int vo_cur[G::NSLOT], vo_nxt[G::NSLOT];
     unsigned inb_cur, inb_nxt;
@@ -270,7 +260,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
     for (int i = 0; i < G::NSLOT; ++i) vo_nxt[i] = vo_cur[i];
     inb_nxt = inb_cur;
     __amdgpu_buffer_rsrc_t rs_cur = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)cur.n * img_bytes, 0,
-                                                                      (unsigned)img_bytes, 0x00020000);
+                                                                      (unsigned)img_bytes, BUFFER_RSRC_FLAGS);
     __amdgpu_buffer_rsrc_t rs_nxt = rs_cur;
     int wsel = 0;
     w_issue(0, cur.c0, 0);
@@ -318,9 +308,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
             if (last_pair) {                                  // the next tile's staging plan (used from stage 5 on)
                 make_plan(nxt, vo_nxt, inb_nxt);
                 rs_nxt = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)nxt.n * img_bytes, 0,
-                                                           (unsigned)img_bytes, 0x00020000);
+                                                           (unsigned)img_bytes, BUFFER_RSRC_FLAGS);
             }
-            s_static_for(std::make_integer_sequence<int, 9>{}, [&](auto s_c) {
+            static_for(std::make_integer_sequence<int, 9>{}, [&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
                 // ---- barrier(s): stage s's weights, and every patch chunk it reads, are visible; stage s-1's buffers are free.
                 //      vmcnt allowance = the VMEM operations issued AFTER the weight DMA in stage s-1 (they may stay in flight)
@@ -455,7 +445,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
                 const int ho = cur.h0 + (pix >> 4), wo = cur.w0 + (pix & 15);
                 const bool pix_ok = (ho < p.Ho) && (wo < p.Wo);
                 // byte offset of (n, ho, wo, c0 + wave_c*64 + 8*g) -- the stores add (i*32 + qp*16)*2
-                const int obase = pix_ok ? (int)((((size_t)(cur.n * p.Ho + ho) * p.Wo + wo) * p.Cout + cur.c0 + wave_c * 64 + 8 * g) * 2) : S_OOB;
+                const int obase = pix_ok ? (int)((((size_t)(cur.n * p.Ho + ho) * p.Wo + wo) * p.Cout + cur.c0 + wave_c * 64 + 8 * g) * 2) : OOB_VOFFSET;
                 u32x4 rv[2][2];
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -522,9 +512,8 @@ int launch_stream(const StreamParams& p, hipStream_t s) {
     static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
     if (wgs_per_cu > 0) resident = (long long)wgs_per_cu * mas_num_cus();
     const unsigned blocks = (unsigned)(tiles < resident ? tiles : resident);
-    static const int bands = mas_env_int("MAS_CONV_XCD_BANDS", 1);
     StreamParams pb = p;
-    pb.xcd_bands = (bands && blocks % 8 == 0 && tiles / 8 >= blocks / 8) ? 1 : 0;
+    pb.xcd_bands = mas_xcd_band_walk_ok(blocks, tiles) ? 1 : 0;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), S_LDS, s, pb);
     MAS_CHECK_LAUNCH("conv3x3_stream");
     return MAS_OK;

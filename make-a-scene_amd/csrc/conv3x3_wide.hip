@@ -19,14 +19,12 @@
 // Everything HBM-facing is LDS-DMA (`buffer_load_dwordx4 ... lds`) issued inside a stage for a later one, with COUNTED waits
 // (in-order VMEM retirement), as in the stream kernel; the GroupNorm(+SiLU) prologue is applied in place to the raw patch.
 // LDS: 2 x 24 KiB weights + 2 x 39 KiB patch = 126 KiB, one 512-thread work-group per CU, 2 waves per SIMD, 256 VGPRs.
-#include "mas_common.h"
+#include "mas_lds.h"
+#include "mas_tilewalk.h"
 #include <algorithm>
 #include <utility>
 
 namespace {
-
-template <int... I, typename F>
-__device__ __forceinline__ void w_static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 struct WideParams {
     unsigned long long* dbg;                   // -DW_TIMELINE builds only
@@ -36,7 +34,7 @@ struct WideParams {
     int Hl, Wl, pad_top, pad_left, upsample, act;
     int n_chunks, Cout_pad, tiles_h, tiles_w, n_ct;
     unsigned m_ct, m_tw, m_th;                 // ceil(2^32 / d) for d = n_ct, tiles_w, tiles_h: t / d == umulhi(t, m) (host checks t * d < 2^32)
-    int xcd_bands;                             // 1: every XCD walks its own contiguous eighth of the tile list (see the prologue)
+    int xcd_bands;                             // 1: every XCD walks its own contiguous eighth of the tile list (mas_tilewalk.h)
 };
 
 constexpr int W_PWL = 34;                      // patch pitch in pixels (32 + 2)
@@ -55,10 +53,6 @@ constexpr int W_SS = W_NEXT + 512 * 16;        // [2][Cin <= 512][2] fp32 GroupN
 constexpr int W_MAXCIN = 512;
 constexpr int W_LDS = W_SS + 2 * W_MAXCIN * 8;   // + {table row, cout offset} of the pending statistics flush
 constexpr int W_NSLOT = 5;                     // patch DMA pieces (and 16-byte activation slots) per wave (thread) per chunk
-constexpr int W_OOB = (int)0x80000000;
-
-#define W_WAIT_BARRIER(N) do { asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                               asm volatile("" ::: "memory"); } while (0)
 
 #ifdef W_TIMELINE
 #define WTS(id) do { __builtin_amdgcn_sched_barrier(0); if (lane == 0 && blockIdx.x == 100 && tl_iter >= 1 && tl_iter < 3 && p.dbg) \
@@ -69,13 +63,13 @@ constexpr int W_OOB = (int)0x80000000;
 
 __device__ __forceinline__ void w_wait_barrier(int n) {   // n is a compile-time constant after unrolling, or selected by a uniform branch
     switch (n) {
-        case 0: W_WAIT_BARRIER(0); break;
-        case 2: W_WAIT_BARRIER(2); break;
-        case 3: W_WAIT_BARRIER(3); break;
-        case 5: W_WAIT_BARRIER(5); break;
-        case 7: W_WAIT_BARRIER(7); break;
-        case 32: W_WAIT_BARRIER(32); break;
-        default: W_WAIT_BARRIER(0); break;
+        case 0: WAIT_BARRIER(0); break;
+        case 2: WAIT_BARRIER(2); break;
+        case 3: WAIT_BARRIER(3); break;
+        case 5: WAIT_BARRIER(5); break;
+        case 7: WAIT_BARRIER(7); break;
+        case 32: WAIT_BARRIER(32); break;
+        default: WAIT_BARRIER(0); break;
     }
 }
 
@@ -93,10 +87,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
 
     const size_t img_bytes = (size_t)p.H * p.W * p.Cin * 2;
     const unsigned out_bytes = (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(RES ? p.res : p.y), 0, RES ? out_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(RES ? p.res : p.y), 0, RES ? out_bytes : 0u, BUFFER_RSRC_FLAGS);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.w), 0,
-                                                                           (unsigned)(9 * p.n_chunks * p.Cout_pad * 64), 0x00020000);
+                                                                           (unsigned)(9 * p.n_chunks * p.Cout_pad * 64), BUFFER_RSRC_FLAGS);
 
 
     // ---- tiles: persistent work-group, static stride.  Divisions by the (runtime) tile-grid extents are multiply-high by
@@ -136,7 +130,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {           // byte offset of (n, ho, w0 + 4 g, c0 + 4 l31); the epilogue adds the pixel column
             const int ho = tc.h0 + 2 * wave + j;
-            ob[j] = (ho < p.Ho) ? (int)((((size_t)(tc.n * p.Ho + ho) * p.Wo + tc.w0 + 4 * g) * p.Cout + tc.c0 + 4 * l31) * 2) : W_OOB;
+            ob[j] = (ho < p.Ho) ? (int)((((size_t)(tc.n * p.Ho + ho) * p.Wo + tc.w0 + 4 * g) * p.Cout + tc.c0 + 4 * l31) * 2) : OOB_VOFFSET;
         }
         ob[2] = p.Wo - tc.w0 - 4 * g;           // pixel columns (relative to this lane's first) that exist
         ob[3] = (tc.n * p.tiles_h + (tc.h0 >> 4)) * p.tiles_w + (tc.w0 >> 5);   // row of the statistics table (uniform)
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
             const bool inb = live && (ih >= 0) && (ih < p.Hl) && (iw >= 0) && (iw < p.Wl);
             if (p.upsample) { ih >>= 1; iw >>= 1; }
             const int sl = (lane & 3) ^ ((q >> 2) & 3);
-            vo[k] = inb ? ((ih * p.W + iw) * p.Cin + sl * 8) * 2 : W_OOB;
+            vo[k] = inb ? ((ih * p.W + iw) * p.Cin + sl * 8) * 2 : OOB_VOFFSET;
             inb_mask |= inb ? (1u << k) : 0u;
         }
     };
@@ -230,19 +224,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
     auto b_addr = [&](int P) { return P * 64 + (((g ^ (P >> 2)) & 3) << 4); };   // kk = 0; kk = 1 is ^ 32
 
     // ---- prologue ----------------------------------------------------------------------------------------------------------------
-    // Tile walk.  Work-group b runs on XCD b % 8 (observed dispatch order; speed only, never correctness).  With the plain static stride
-    // (b, b + G, ...) the 32 CUs of an XCD work on tiles 8 apart: no two of them share a halo, and every 18x34 patch (1.195x its tile)
-    // comes over the fabric.  xcd_bands: XCD x owns the contiguous eighth [T x / 8, T (x + 1) / 8) of the tile list and its work-groups
-    // walk it in order, so the tiles in flight on one XCD are spatial neighbours (a whole image of a 256^2 map) and their halos meet in
-    // that XCD's L2 (profiles/r06_xcd_bands.txt).  Same registers as before: `step` replaces gridDim.x, `tile_end` replaces total_tiles.
-    int tile = blockIdx.x;                      // grid <= total_tiles
-    int step = (int)gridDim.x, tile_end = total_tiles;
-    if (p.xcd_bands && (gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        step = (int)(gridDim.x >> 3);
-        tile = (int)(((long long)total_tiles * x) >> 3) + (int)(blockIdx.x >> 3);
-        tile_end = (int)(((long long)total_tiles * (x + 1)) >> 3);
-    }
+    int tile, step, tile_end;                   // plain or banded tile walk (mas_tilewalk.h); grid <= total_tiles
+    xcd_band_walk(total_tiles, p.xcd_bands, tile, step, tile_end);
     int c0_cur, c0_nxt, ob_cur[4];
     // ONE plan / image descriptor: the current tile's until its last chunk-B patch has been issued (stage 1 of the last pair),
     // the next tile's from stage 2 of the last pair on (only the in-bounds masks of both tiles are live at the same time)
@@ -255,7 +238,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
         make_plan(t0, vo, inb_cur, ob_cur);
         c0_cur = c0_nxt = t0.c0; n_cur = n_nxt = t0.n;
         *reinterpret_cast<u32x4*>(smem + W_NEXT + tid * 16) = u32x4{(unsigned)ob_cur[0], (unsigned)ob_cur[1], (unsigned)ob_cur[2], (unsigned)ob_cur[3]};
-        rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)t0.n * img_bytes, 0, (unsigned)img_bytes, 0x00020000);
+        rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)t0.n * img_bytes, 0, (unsigned)img_bytes, BUFFER_RSRC_FLAGS);
     }
     inb_nxt = inb_cur;
     {   // bias -> LDS (read back in the epilogue through lgkmcnt: a VMEM load there would wait behind the tile's own stores)
@@ -267,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
     int ss_sel = 0;                              // table of the CURRENT tile's image
     if constexpr (ACT) {
         ss_stage(n_cur, 0);
-        W_WAIT_BARRIER(0);                       // the raw patch of chunk 0 has landed for every wave, the table is visible
+        WAIT_BARRIER(0);                       // the raw patch of chunk 0 has landed for every wave, the table is visible
         ss_fetch(0, 0);
         p_activate(inb_cur, 0);
     }
@@ -306,7 +289,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
         for (int pair = 0; pair < n_pairs; ++pair) {
             const bool last_pair = pair + 1 == n_pairs;
             const int ciA = pair * 64;                        // first channel of chunk A (even) of this pair; B = +32
-            w_static_for(std::make_integer_sequence<int, 6>{}, [&](auto s_c) {
+            static_for(std::make_integer_sequence<int, 6>{}, [&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;
                 constexpr int cb = s / 3, kh = s % 3;         // chunk A / B of the pair (= patch buffer), filter row
                 constexpr int wsel = s & 1;
@@ -332,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                         c0_nxt = nt.c0; n_nxt = nt.n;
                         if constexpr (ACT) ss_stage(nt.n, ss_sel ^ 1);      // visible after the next barrier, first read three stages later
                         rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)nt.n * img_bytes, 0,
-                                                                 (unsigned)img_bytes, 0x00020000);
+                                                                 (unsigned)img_bytes, BUFFER_RSRC_FLAGS);
                     }
                 };
                 auto act_blk = [&]() {
@@ -436,7 +419,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int pc = (r & 3) + 8 * (r >> 2);           // pixel column (+ 4 g, folded into ob_cur)
-                    rv[r] = __builtin_amdgcn_raw_buffer_load_b64(rs_r, pc < ob_cur[2] ? ob_cur[j] : W_OOB, pc * row_bytes, 0);
+                    rv[r] = __builtin_amdgcn_raw_buffer_load_b64(rs_r, pc < ob_cur[2] ? ob_cur[j] : OOB_VOFFSET, pc * row_bytes, 0);
                 }
             };
             // fused statistics: per lane the sum and the sum of squares of its 4 couts over its pixels, as two packed-fp32 pairs each
@@ -448,13 +431,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                 // ragged tiles only (wave-uniform branch): a pixel outside the map must not count -- its accumulators are set to
                 // -bias, so that (with the residual load of an out-of-range offset returning 0) its value is exactly 0; its store is
                 // dropped by the bounds check anyway.  Full tiles (all but the last row / column of tiles) skip this.
-                if (!__all(ob_cur[2] > 27 && ob_cur[0] != W_OOB && ob_cur[1] != W_OOB)) {
+                if (!__all(ob_cur[2] > 27 && ob_cur[0] != OOB_VOFFSET && ob_cur[1] != OOB_VOFFSET)) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int pc = (r & 3) + 8 * (r >> 2);
-                            if (!((pc < ob_cur[2]) && (ob_cur[j] != W_OOB))) {
+                            if (!((pc < ob_cur[2]) && (ob_cur[j] != OOB_VOFFSET))) {
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) acc[i][j][r] = -bv[i];
                             }
@@ -486,8 +469,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
 #endif
             auto store = [&](int j, int r, u32x2 o) {
                 const int pc = (r & 3) + 8 * (r >> 2);
-                const bool ok = (pc < ob_cur[2]) && (ob_cur[j] != W_OOB);
-                __builtin_amdgcn_raw_buffer_store_b64(o, rs_y, ok ? ob_cur[j] : W_OOB, pc * row_bytes, W_ST_AUX);
+                const bool ok = (pc < ob_cur[2]) && (ob_cur[j] != OOB_VOFFSET);
+                __builtin_amdgcn_raw_buffer_store_b64(o, rs_y, ok ? ob_cur[j] : OOB_VOFFSET, pc * row_bytes, W_ST_AUX);
             };
             if constexpr (RES) {
                 res_load(0);
@@ -596,13 +579,12 @@ int mas_conv3x3_wide_launch(const MasConvDesc* d, const void* x, const float* sc
     p.tiles_h = mas_cdiv(d->Ho, 16); p.tiles_w = mas_cdiv(d->Wo, 32); p.n_ct = d->Cout / 128;
     auto magic = [](int dv) { return (unsigned)((0x100000000ULL + (unsigned)dv - 1) / (unsigned)dv); };   // (d = 1 handled in the kernel)
     p.m_ct = magic(p.n_ct); p.m_tw = magic(p.tiles_w); p.m_th = magic(p.tiles_h);
-    static const int xcd_bands = mas_env_int("MAS_CONV_XCD_BANDS", 1);
-    {   // the banded walk needs every band at least as long as the number of work-groups that walk it
+    {
         const long long tiles = (long long)p.N * p.tiles_h * p.tiles_w * p.n_ct;
         static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
         const long long resident = (long long)(wgs_per_cu > 0 ? wgs_per_cu : 4) * mas_num_cus();
         const long long blocks = tiles < resident ? tiles : resident;
-        p.xcd_bands = (xcd_bands && blocks % 8 == 0 && tiles / 8 >= blocks / 8) ? 1 : 0;
+        p.xcd_bands = mas_xcd_band_walk_ok(blocks, tiles) ? 1 : 0;
     }
     if (stats) {
         if (d->act != MAS_ACT_NONE) return residual ? launch_wide<true, true, true>(p, s) : launch_wide<true, false, true>(p, s);

@@ -20,7 +20,7 @@
 // ds_write_b128) into a double buffer; one barrier per tap.  All global loads are ordinary loads, so
 // hipcc's counted s_waitcnt vmcnt(N) keeps the patch prefetch (issued one slot per tap, after that
 // tap's weight loads) in flight across two taps and barriers.
-#include "mas_common.h"
+#include "mas_lds.h"
 #include <stdlib.h>
 
 namespace {
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, 2) void conv_fwd_kernel(ConvParams
     // access ("pending flat") and then turns every lgkmcnt wait in front of an MFMA into lgkmcnt(0), which serialises the
     // software-pipelined fragment reads.
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(Wimg), 0,
-                                                                           (unsigned)(NTAP * p.n_chunks * p.Cout_pad * 128), 0x00020000);
+                                                                           (unsigned)(NTAP * p.n_chunks * p.Cout_pad * 128), BUFFER_RSRC_FLAGS);
     auto w_issue = [&](int stage, int ch, int c0, int buf) {
 #pragma unroll
         for (int k = 0; k < W_DMA; ++k) {

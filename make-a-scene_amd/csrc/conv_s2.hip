@@ -11,29 +11,10 @@
 //     bank-conflicted -- the kernel is bound by the 54 KiB of DMA per 36 MFMAs of a wave, not by LDS);
 //   * double-buffered, one barrier per tile; split-K over tiles into slabs for mas_wgrad_reduce (fixed order: bitwise reproducible);
 //     bias gradient = one more MFMA per k-step against an all-ones operand.
-#include "mas_common.h"
+#include "mas_lds.h"
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) int s2_i32x4;
-typedef __attribute__((ext_vector_type(4))) short s2_s16x4;
-__device__ __forceinline__ void s2_dma16(s2_i32x4 rs, unsigned lds, int vo) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(vo), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ s2_i32x4 s2_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    s2_i32x4 r = {(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)bytes, 0x00020000};
-    r[0] = __builtin_amdgcn_readfirstlane(r[0]); r[1] = __builtin_amdgcn_readfirstlane(r[1]);
-    r[2] = __builtin_amdgcn_readfirstlane(r[2]); r[3] = __builtin_amdgcn_readfirstlane(r[3]);
-    return r;
-}
-__device__ __forceinline__ bf16x8 s2_tr(const unsigned char* a0, const unsigned char* a1) {
-    const s2_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s2_s16x4*)a0);
-    const s2_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s2_s16x4*)a1);
-    const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return *reinterpret_cast<const bf16x8*>(&v);
-}
 
 struct S2WgradParams {
     const unsigned char* x; const unsigned char* dy; float* part; float* part_bias;
@@ -46,7 +27,6 @@ constexpr int S2_DY = 64 * 256;                // 16 KiB
 constexpr int S2_XP = 38 * 1024;               // 297 pixels x 128 B -> 38 DMA pieces of 8 pixels
 constexpr int S2_STAGE = S2_DY + S2_XP;
 constexpr int S2_LDS = 2 * S2_STAGE;           // 108 KiB
-constexpr int S2_OOB = (int)0x80000000;
 
 __global__ __launch_bounds__(S2_NT, 1) void wgrad_s2_kernel(S2WgradParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s2_smem[];
@@ -59,8 +39,8 @@ __global__ __launch_bounds__(S2_NT, 1) void wgrad_s2_kernel(S2WgradParams p) {
     const int ci_t = bid % p.n_ci_t, co_t = bid / p.n_ci_t;
     const int co0 = co_t * 128, ci0 = ci_t * 64;
 
-    const s2_i32x4 rs_dy = s2_rsrc(p.dy, (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2));
-    const s2_i32x4 rs_x = s2_rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
+    const i32x4 rs_dy = rsrc(p.dy, (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2));
+    const i32x4 rs_x = rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
 
     // ---- DMA plan.  dY: 16 pieces of 4 pixels x 256 B; wave w moves pieces 2 w, 2 w + 1 (tile row w >> 1, columns 8 (w & 1) + 4 j + (lane >> 4));
     //      physical 64-byte block (lane >> 2) & 3 = logical block ^ (column & 3).  Patch: pieces wave + 8 k (k < 5, piece < 38) of 8 pixels x 128 B;
@@ -76,8 +56,8 @@ __global__ __launch_bounds__(S2_NT, 1) void wgrad_s2_kernel(S2WgradParams p) {
             const int piece = 2 * wave + j;
             const int oh = oh0 + (piece >> 2), ow = ow0 + 4 * (piece & 3) + lp;
             const bool ok = oh < p.Ho && ow < p.Wo;
-            s2_dma16(rs_dy, __builtin_amdgcn_readfirstlane(lds0 + stage * S2_STAGE + piece * 1024),
-                     ok ? (((n * p.Ho + oh) * p.Wo + ow) * p.Cout + co0) * 2 + dsrc : S2_OOB);
+            dma16(rs_dy, __builtin_amdgcn_readfirstlane(lds0 + stage * S2_STAGE + piece * 1024),
+                     ok ? (((n * p.Ho + oh) * p.Wo + ow) * p.Cout + co0) * 2 + dsrc : OOB_VOFFSET);
         }
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
@@ -88,8 +68,8 @@ __global__ __launch_bounds__(S2_NT, 1) void wgrad_s2_kernel(S2WgradParams p) {
                 const int ih = 2 * oh0 + pr, iw = 2 * ow0 + pc;
                 const bool ok = px < S2_NPP && ih < p.H && iw < p.W;                 // (rows / columns past the map = the one-sided zero padding)
                 const int blk = ((lane >> 2) & 1) ^ ((pc >> 1) & 1);
-                s2_dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + stage * S2_STAGE + S2_DY + piece * 1024),
-                         ok ? (((n * p.H + ih) * p.W + iw) * p.Cin + ci0) * 2 + (blk << 6) + ((lane & 3) << 4) : S2_OOB);
+                dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + stage * S2_STAGE + S2_DY + piece * 1024),
+                         ok ? (((n * p.H + ih) * p.W + iw) * p.Cin + ci0) * 2 + (blk << 6) + ((lane & 3) << 4) : OOB_VOFFSET);
             }
         }
     };
@@ -129,13 +109,13 @@ __global__ __launch_bounds__(S2_NT, 1) void wgrad_s2_kernel(S2WgradParams p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const unsigned char* a0 = sb + a_off + r * 16 * 256;
-            const bf16x8 afr = s2_tr(a0, a0 + 4 * 256);
+            const bf16x8 afr = tr_frag(a0, a0 + 4 * 256);
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
                 for (int kw = 0; kw < 3; ++kw) {
                     const unsigned char* b0 = sb + b_off[kw] + (2 * r + kh) * S2_PW * 128;
-                    mma16(acc[kh * 3 + kw], afr, s2_tr(b0, b0 + 8 * 128));          // D[co][ci]
+                    mma16(acc[kh * 3 + kw], afr, tr_frag(b0, b0 + 8 * 128));          // D[co][ci]
                 }
             if (do_bias) mma16(accb, afr, ones);
         }
@@ -193,8 +173,8 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_fwd_kernel(S2FwdParams p) {
     const int th_i = t % p.tiles_h, n = t / p.tiles_h;
     const int oh0 = th_i * F2_TH, ow0 = tw_i * F2_TW, c0 = ct * 128;
 
-    const s2_i32x4 rs_x = s2_rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
-    const s2_i32x4 rs_w = s2_rsrc(p.w, (unsigned)((size_t)(p.Cin / 64 + (p.Cin % 64 ? 1 : 0)) * 9 * p.rows_pad * 128));
+    const i32x4 rs_x = rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
+    const i32x4 rs_w = rsrc(p.w, (unsigned)((size_t)(p.Cin / 64 + (p.Cin % 64 ? 1 : 0)) * 9 * p.rows_pad * 128));
 
     // ---- DMA plan.  Patch piece wave + 8 k (k < 5, piece < 33): pixel P = 16 piece + (lane >> 2) = row P / 65, column P % 65; physical
     //      16-byte slot lane & 3 holds LOGICAL slot ^ ((P >> 1) & 3).  Weight piece wave + 8 k (k < 3) = tap piece / 8, rows
@@ -230,13 +210,13 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_fwd_kernel(S2FwdParams p) {
         for (int k = 0; k < 5; ++k) {
             if (wave + 8 * k < 33) {
                 const bool ok = (xok >> (8 * kh + k)) & 1u;
-                s2_dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + stage * F2_STAGE + (wave + 8 * k) * 1024), ok ? xo[k] + xs : S2_OOB);
+                dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + stage * F2_STAGE + (wave + 8 * k) * 1024), ok ? xo[k] + xs : OOB_VOFFSET);
             }
         }
         const int wb = (c64 * 9 + kh * 3) * p.rows_pad * 128;                  // uniform: chunk c64, taps kh * 3 ..
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            s2_dma16(rs_w, __builtin_amdgcn_readfirstlane(lds0 + stage * F2_STAGE + F2_PATCH + (wave + 8 * k) * 1024), wo[k] + wb + (h ? ws1[k] : ws0[k]));
+            dma16(rs_w, __builtin_amdgcn_readfirstlane(lds0 + stage * F2_STAGE + F2_PATCH + (wave + 8 * k) * 1024), wo[k] + wb + (h ? ws1[k] : ws0[k]));
     };
 
     // ---- fragment addresses
@@ -294,8 +274,8 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_fwd_kernel(S2FwdParams p) {
 
     // ---- epilogue
     const unsigned out_bytes = (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? (unsigned)(p.Cout * 4) : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? (unsigned)(p.Cout * 4) : 0u, BUFFER_RSRC_FLAGS);
     f32x4 bv[2][2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -308,7 +288,7 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_fwd_kernel(S2FwdParams p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int oh = oh0 + 2 * wave_p + j, ow = ow0 + l31;
-        const int obase = (oh < p.Ho && ow < p.Wo) ? (((n * p.Ho + oh) * p.Wo + ow) * p.Cout + c0 + wave_c * 64 + 8 * g) * 2 : S2_OOB;
+        const int obase = (oh < p.Ho && ow < p.Wo) ? (((n * p.Ho + oh) * p.Wo + ow) * p.Cout + c0 + wave_c * 64 + 8 * g) * 2 : OOB_VOFFSET;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -362,8 +342,8 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_dgrad_kernel(S2DgradParams p
     const int a0 = th_i * F2_TH, b0 = tw_i * F2_TW, ci0 = ct * 128;
     const int nkh = pp ? 1 : 2, nkw = qq ? 1 : 2;
 
-    const s2_i32x4 rs_y = s2_rsrc(p.dy, (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2));
-    const s2_i32x4 rs_w = s2_rsrc(p.w, (unsigned)((size_t)((p.Cout + 63) / 64) * 9 * p.rows_pad * 128));
+    const i32x4 rs_y = rsrc(p.dy, (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2));
+    const i32x4 rs_w = rsrc(p.w, (unsigned)((size_t)((p.Cout + 63) / 64) * 9 * p.rows_pad * 128));
 
     // ---- DMA plan.  Patch piece wave + 8 k (k < 3, piece < 17): pixel P = 16 piece + (lane >> 2) = row P / 33 (dy row a0 + row - dh),
     //      column P % 33 (dy column b0 - 1 + column); slot swizzle as the forward kernel.  Weights: piece wave + 8 k = tap slot k, rows
@@ -393,7 +373,7 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_dgrad_kernel(S2DgradParams p
         for (int k = 0; k < 3; ++k) {
             if (wave + 8 * k < 17) {
                 const bool ok = (yok >> (8 * dh + k)) & 1u;
-                s2_dma16(rs_y, __builtin_amdgcn_readfirstlane(lds0 + stage * G2_STAGE + (wave + 8 * k) * 1024), ok ? yo[k] + ys : S2_OOB);
+                dma16(rs_y, __builtin_amdgcn_readfirstlane(lds0 + stage * G2_STAGE + (wave + 8 * k) * 1024), ok ? yo[k] + ys : OOB_VOFFSET);
             }
         }
 #pragma unroll
@@ -402,7 +382,7 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_dgrad_kernel(S2DgradParams p
                 const int kw = qq ? 1 : 2 * k;
                 const int tap_img = (2 - kh) * 3 + (2 - kw);                   // the transposed image stores the taps flipped
                 const int wb = ((c64 * 9 + tap_img) * p.rows_pad) * 128;      // uniform
-                s2_dma16(rs_w, __builtin_amdgcn_readfirstlane(lds0 + stage * G2_STAGE + G2_PATCH + (wave + 8 * k) * 1024), wo_ + wb + (h ? ws1 : ws0));
+                dma16(rs_w, __builtin_amdgcn_readfirstlane(lds0 + stage * G2_STAGE + G2_PATCH + (wave + 8 * k) * 1024), wo_ + wb + (h ? ws1 : ws0));
             }
         }
     };
@@ -464,11 +444,11 @@ __global__ __launch_bounds__(S2_NT, 1) void conv_s2_dgrad_kernel(S2DgradParams p
     }
 
     const unsigned out_bytes = (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2);
-    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(p.dx, 0, out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(p.dx, 0, out_bytes, BUFFER_RSRC_FLAGS);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int u = 2 * (a0 + 2 * wave_p + j) + pp, v = 2 * (b0 + l31) + qq;
-        const int obase = (u < p.H && v < p.W) ? (((n * p.H + u) * p.W + v) * p.Cin + ci0 + wave_c * 64 + 8 * g) * 2 : S2_OOB;
+        const int obase = (u < p.H && v < p.W) ? (((n * p.H + u) * p.W + v) * p.Cin + ci0 + wave_c * 64 + 8 * g) * 2 : OOB_VOFFSET;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -12,29 +12,10 @@
 //   Tile = 4 x 16 pixels of B (16 KiB, LDS-DMA, 64-byte blocks ^ (pixel & 3)), 4 waves = the 4 32-channel groups of B, 3 accumulator
 //   tiles (96 rows, 72 used) per wave; split-K over tiles into slabs that mas_wgrad_reduce adds in a fixed order; the bias gradient is
 //   one more MFMA per k-step against an all-ones operand.  HBM-bound by construction (12 MFMAs per 16 KiB of B).
-#include "mas_common.h"
+#include "mas_lds.h"
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) int th_i32x4;
-typedef __attribute__((ext_vector_type(4))) short th_s16x4;
-__device__ __forceinline__ void th_dma16(th_i32x4 rs, unsigned lds, int vo) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(vo), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ th_i32x4 th_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    th_i32x4 r = {(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)bytes, 0x00020000};
-    r[0] = __builtin_amdgcn_readfirstlane(r[0]); r[1] = __builtin_amdgcn_readfirstlane(r[1]);
-    r[2] = __builtin_amdgcn_readfirstlane(r[2]); r[3] = __builtin_amdgcn_readfirstlane(r[3]);
-    return r;
-}
-__device__ __forceinline__ bf16x8 th_tr(const unsigned char* a0, const unsigned char* a1) {
-    const th_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) th_s16x4*)a0);
-    const th_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) th_s16x4*)a1);
-    const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return *reinterpret_cast<const bf16x8*>(&v);
-}
 
 struct ThinWgradParams {
     const unsigned char* big; const unsigned char* small; float* part; float* part_bias;
@@ -49,7 +30,6 @@ constexpr int TH_BIG = 64 * 256;               // 64 pixels x 128 channels
 constexpr int TH_SMALL = 2048;                 // (4 + 2) x (16 + 2) = 108 pixels x 16 B in two 1-KiB DMA pieces
 constexpr int TH_STAGE = TH_BIG + TH_SMALL;
 constexpr int TH_LDS = 2 * TH_STAGE;
-constexpr int TH_OOB = (int)0x80000000;
 constexpr int TH_SLAB = 9 * 8 * 128;
 
 __global__ __launch_bounds__(TH_NT, 2) void wgrad_thin_kernel(ThinWgradParams p) {
@@ -58,8 +38,8 @@ __global__ __launch_bounds__(TH_NT, 2) void wgrad_thin_kernel(ThinWgradParams p)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31, G16 = (lane >> 4) & 1, sl = lane & 15;
     const int split = blockIdx.x;
-    const th_i32x4 rs_b = th_rsrc(p.big, (unsigned)((size_t)p.N * p.H * p.W * 256));
-    const th_i32x4 rs_s = th_rsrc(p.small, (unsigned)((size_t)p.N * p.H * p.W * 16));
+    const i32x4 rs_b = rsrc(p.big, (unsigned)((size_t)p.N * p.H * p.W * 256));
+    const i32x4 rs_s = rsrc(p.small, (unsigned)((size_t)p.N * p.H * p.W * 16));
 
     // ---- DMA plan.  B: 16 pieces of 4 pixels x 256 B, wave w moves pieces 4 w .. 4 w + 3 = tile row w; piece 4 w + j holds columns
     //      4 j .. 4 j + 3; lane: column 4 j + (lane >> 4), physical 64-byte block (lane >> 2) & 3 = logical block ^ (column & 3).
@@ -76,12 +56,12 @@ __global__ __launch_bounds__(TH_NT, 2) void wgrad_thin_kernel(ThinWgradParams p)
         for (int j = 0; j < 4; ++j) {
             const int iw = w0 + 4 * j + lp;
             const bool ok = ih < p.H && iw < p.W;
-            th_dma16(rs_b, __builtin_amdgcn_readfirstlane(lds0 + stage * TH_STAGE + (wave * 4 + j) * 1024), ok ? ((n * p.H + ih) * p.W + iw) * 256 + lsrc : TH_OOB);
+            dma16(rs_b, __builtin_amdgcn_readfirstlane(lds0 + stage * TH_STAGE + (wave * 4 + j) * 1024), ok ? ((n * p.H + ih) * p.W + iw) * 256 + lsrc : OOB_VOFFSET);
         }
         if (wave < 2) {
             const int sh = h0 + hr - 1, sw = w0 + hc - 1;
             const bool ok = hp < 108 && sh >= 0 && sh < p.H && sw >= 0 && sw < p.W;
-            th_dma16(rs_s, __builtin_amdgcn_readfirstlane(lds0 + stage * TH_STAGE + TH_BIG + wave * 1024), ok ? ((n * p.H + sh) * p.W + sw) * 16 : TH_OOB);
+            dma16(rs_s, __builtin_amdgcn_readfirstlane(lds0 + stage * TH_STAGE + TH_BIG + wave * 1024), ok ? ((n * p.H + sh) * p.W + sw) * 16 : OOB_VOFFSET);
         }
     };
 
@@ -121,10 +101,10 @@ __global__ __launch_bounds__(TH_NT, 2) void wgrad_thin_kernel(ThinWgradParams p)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                                            // k-step = tile row r (16 pixels)
             const unsigned char* b0 = sb + b_off + r * 16 * 256;
-            const bf16x8 bfr = th_tr(b0, b0 + 4 * 256);
+            const bf16x8 bfr = tr_frag(b0, b0 + 4 * 256);
             bf16x8 afr[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { const unsigned char* a0 = sb + a_off[i] + r * 18 * 16; afr[i] = th_tr(a0, a0 + 4 * 16); }
+            for (int i = 0; i < 3; ++i) { const unsigned char* a0 = sb + a_off[i] + r * 18 * 16; afr[i] = tr_frag(a0, a0 + 4 * 16); }
 #pragma unroll
             for (int i = 0; i < 3; ++i) mma16(acc[i], afr[i], bfr);
             if (bias_s) mma16(accb, afr[1], ones);                               // rows 32..39 = centre tap: sum over the tile of S[pixel][cs]
@@ -174,10 +154,10 @@ __global__ __launch_bounds__(TH_NT, 2) void conv_thin_fwd_kernel(ThinFwdParams p
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)th_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
-    const th_i32x4 rs_x = th_rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * 16));
+    const i32x4 rs_x = rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * 16));
     const unsigned out_bytes = (unsigned)((size_t)p.N * p.H * p.W * 256);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? 512u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, out_bytes, BUFFER_RSRC_FLAGS);
+    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(p.bias ? (void*)p.bias : (void*)p.y, 0, p.bias ? 512u : 0u, BUFFER_RSRC_FLAGS);
 
     // ---- weights: fragment (cout tile i, k-step kk): row 32 i + l31, tap 2 kk + g, channels 0..7 = logical slot 0 of the image row
     bf16x8 afr[4][5];
@@ -210,7 +190,7 @@ __global__ __launch_bounds__(TH_NT, 2) void conv_thin_fwd_kernel(ThinFwdParams p
                 const int hp = piece * 64 + lane, hr = hp / TF_HW, hc = hp - hr * TF_HW;
                 const int ih = h0 + hr, iw = w0 + hc;
                 const bool ok = hp < TF_HALO && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
-                th_dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + stage * TF_STAGE + piece * 1024), ok ? ((n * p.H + ih) * p.W + iw) * 16 : TH_OOB);
+                dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + stage * TF_STAGE + piece * 1024), ok ? ((n * p.H + ih) * p.W + iw) * 16 : OOB_VOFFSET);
             }
         }
     };
@@ -270,7 +250,7 @@ __global__ __launch_bounds__(TH_NT, 2) void conv_thin_fwd_kernel(ThinFwdParams p
                 const int r = 4 * k + (lane >> 4), sl_ = lane & 15;
                 const u32x4 o = *reinterpret_cast<const u32x4*>(ot + r * 256 + ((sl_ ^ (r & 15)) << 4));
                 const int ow = tw_i * TF_TW + r;
-                const int off = (oh < p.H && ow < p.W) ? ((n * p.H + oh) * p.W + ow) * 256 + sl_ * 16 : TH_OOB;
+                const int off = (oh < p.H && ow < p.W) ? ((n * p.H + oh) * p.W + ow) * 256 + sl_ * 16 : OOB_VOFFSET;
                 __builtin_amdgcn_raw_buffer_store_b128(o, rs_y, off, 0, 0);
             }
         }
@@ -312,7 +292,7 @@ __global__ __launch_bounds__(TH_NT, 2) void conv_thin_out_kernel(ThinOutParams p
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)th_smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, l31 = lane & 31;
-    const th_i32x4 rs_x = th_rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
+    const i32x4 rs_x = rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
 
     // ---- weights -> LDS, once: slot (chunk32 q, tap, cout r < 8, logical 16-byte slot ls < 4) from the K64 image
     //      [chunk64][tap][rows_pad][128 B], physical slot = logical ^ ((row >> 1) & 7)
@@ -339,8 +319,8 @@ __global__ __launch_bounds__(TH_NT, 2) void conv_thin_out_kernel(ThinOutParams p
                 const int ih = h0 + pr, iw = w0 + pc;
                 const bool ok = q < TO_NPIX && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
                 const int sl = (lane & 3) ^ ((q >> 2) & 3);
-                th_dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + TO_P + buf * TO_PATCH + piece * 1024),
-                         ok ? (((n * p.H + ih) * p.W + iw) * p.Cin + chunk * 32 + sl * 8) * 2 : TH_OOB);
+                dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + TO_P + buf * TO_PATCH + piece * 1024),
+                         ok ? (((n * p.H + ih) * p.W + iw) * p.Cin + chunk * 32 + sl * 8) * 2 : OOB_VOFFSET);
             }
         }
     };

@@ -25,14 +25,11 @@
 // LDS: 2 x 32 KiB weights + 2 x 39 KiB patch + bias + statistics scratch = 158 KiB, one 512-thread work-group per CU.
 // Tiles that share a patch (the 4 phases x Cout / 128 tiles of a spatial tile) are mapped to the SAME XCD (block b runs on XCD b % 8):
 // the input is fetched into one L2 and hit there by the others.
-#include "mas_common.h"
+#include "mas_lds.h"
 #include <algorithm>
 #include <utility>
 
 namespace {
-
-template <int... I, typename F>
-__device__ __forceinline__ void u_static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 struct Up2Params {
     const unsigned char* x; const unsigned char* w; const float* bias; unsigned char* y;
@@ -64,11 +61,7 @@ constexpr int U_STAT = U_BIAS + U_MAXCOUT * 4;            // [8 waves][128][2] f
 constexpr int U_NEXT = U_STAT + 8 * 128 * 2 * 4 + 16;     // [512 threads][2] the next tile's output offsets, then per wave {w0, statistics row}
 constexpr int U_LDS = U_NEXT + 512 * 8 + 8 * 8;
 constexpr int U_NSLOT = 5;
-constexpr int U_OOB = (int)0x80000000;
 static_assert(U_LDS <= 160 * 1024, "LDS budget");
-
-#define U_WAIT_BARRIER(N) do { asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                               asm volatile("" ::: "memory"); } while (0)
 
 template <bool STATS>
 __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
@@ -80,9 +73,9 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave w owns tile rows 2w, 2w+1 and all 128 couts
     const int g = lane >> 5, l31 = lane & 31;
 
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.out_bytes, BUFFER_RSRC_FLAGS);
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.w), 0,
-                                                                           (unsigned)(16 * p.n_chunks * p.Cout_pad * 64), 0x00020000);
+                                                                           (unsigned)(16 * p.n_chunks * p.Cout_pad * 64), BUFFER_RSRC_FLAGS);
 
     // ---- tiles.  Virtual tile t: XCD t & 7 (= the XCD of the work-group that runs it: the grid is a multiple of 8), k = t >> 3;
     //      spatial tile (k / group) * 8 + xcd, member k % group = phase * n_ct + cout tile.  Spatial tiles past the end (the grid of
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
             const int i = tc.h0 + 2 * wave + j;
             ob[j] = (tc.valid && i < p.H) ? (int)((unsigned)tc.n * p.out_img) + i * p.out_row + (tc.w0 + 4 * g) * p.out_px
                                                 + (p.o_phases == 4 ? (tc.ph >> 1) * p.out_ph_row + (tc.ph & 1) * p.out_ph_px : 0) + (tc.c0 + 4 * l31) * 2
-                                          : U_OOB;
+                                          : OOB_VOFFSET;
         }
         ob[2] = p.W - tc.w0 - 4 * g;
         ob[3] = tc.valid ? ((tc.n * p.tiles_h + (tc.h0 >> 4)) * p.tiles_w + (tc.w0 >> 5)) * p.o_phases + (p.o_phases == 4 ? tc.ph : 0) : -1;
@@ -133,7 +126,7 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
             const int ih = tc.h0 + pr - 1, iw = tc.w0 + pc - 1;
             const bool inb = live && tc.valid && (ih >= 0) && (ih < p.H) && (iw >= 0) && (iw < p.W);
             const int sl = (lane & 3) ^ ((q >> 2) & 3);
-            vo[k] = inb ? ih * p.in_row + iw * p.in_px + sl * 16 : U_OOB;
+            vo[k] = inb ? ih * p.in_row + iw * p.in_px + sl * 16 : OOB_VOFFSET;
         }
     };
     auto p_dma = [&](__amdgpu_buffer_rsrc_t rs, const int (&vo)[U_NSLOT], int soff_, int buf) {
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
     __amdgpu_buffer_rsrc_t rs_x;
     auto img_rsrc = [&](int n) {
         const int nn = n < p.N ? n : p.N - 1;
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)nn * p.in_img, 0, p.in_img, 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.x) + (size_t)nn * p.in_img, 0, p.in_img, BUFFER_RSRC_FLAGS);
     };
     {
         const Tile t0 = decode(tile);
@@ -214,15 +207,15 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
 
         int kq = 0, cq = 0;                      // phase / chunk of the stage being COMPUTED
         for (int q = 0; q < NQ; q += 2) {
-            u_static_for(std::make_integer_sequence<int, 2>{}, [&](auto s_c) {
+            static_for(std::make_integer_sequence<int, 2>{}, [&](auto s_c) {
                 constexpr int s = decltype(s_c)::value;            // = buffer of this stage
                 const bool last = q + s + 1 == NQ;
                 // ---- barrier: this stage's weights and patch have landed (they are the youngest vector-memory operations, except for
                 //      the previous tile's 32 epilogue stores at a tile's first stage); the other buffers are free
                 if (s == 0 && q == 0 && stores_in_flight) {
-                    U_WAIT_BARRIER(32); stores_in_flight = false;
+                    WAIT_BARRIER(32); stores_in_flight = false;
                     if constexpr (STATS) stats_flush();
-                } else U_WAIT_BARRIER(0);
+                } else WAIT_BARRIER(0);
                 // ---- the next stage's coordinates; at a tile's last stage: the next tile's plan
                 int kn = kq, cn = cq + 1;
                 if (cn == p.n_chunks) { cn = 0; ++kn; }
@@ -295,13 +288,13 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
             const f32x4 bv = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + U_BIAS) + c0_cur + 4 * l31);
             f32x2 st_s[2] = {f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f}}, st_q[2] = {f32x2{0.0f, 0.0f}, f32x2{0.0f, 0.0f}};
             if constexpr (STATS) {
-                if (!__all(ob_cur[2] > 27 && ob_cur[0] != U_OOB && ob_cur[1] != U_OOB)) {   // ragged tiles: pixels outside the map count as 0
+                if (!__all(ob_cur[2] > 27 && ob_cur[0] != OOB_VOFFSET && ob_cur[1] != OOB_VOFFSET)) {   // ragged tiles: pixels outside the map count as 0
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const int pc = (r & 3) + 8 * (r >> 2);
-                            if (!((pc < ob_cur[2]) && (ob_cur[j] != U_OOB))) {
+                            if (!((pc < ob_cur[2]) && (ob_cur[j] != OOB_VOFFSET))) {
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) acc[i][j][r] = -bv[i];
                             }
@@ -325,8 +318,8 @@ __global__ __launch_bounds__(512, 2) void conv_up2_kernel(Up2Params p) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ob[i] = (bf16_t)v[i];
                     const int pc = (r & 3) + 8 * (r >> 2);
-                    const bool ok = (pc < ob_cur[2]) && (ob_cur[j] != U_OOB);
-                    __builtin_amdgcn_raw_buffer_store_b64(o, rs_y, ok ? ob_cur[j] : U_OOB, pc * p.out_px, 0);
+                    const bool ok = (pc < ob_cur[2]) && (ob_cur[j] != OOB_VOFFSET);
+                    __builtin_amdgcn_raw_buffer_store_b64(o, rs_y, ok ? ob_cur[j] : OOB_VOFFSET, pc * p.out_px, 0);
                 }
             stores_in_flight = true;
             if constexpr (STATS) {

@@ -11,7 +11,7 @@
 // One work-group (8 waves) owns a 128(co) x 64(ci) x all-taps accumulator block in registers and
 // walks a strided subset of the pixel tiles (split-K); each split STORES its partial sums into its own slab (WgradParams::slabs, round 6:
 // mas_conv_wgrad_partial + the fixed-order mas_wgrad_reduce -- bitwise reproducible) or, through mas_conv_wgrad, commits with fp32 atomics.
-#include "mas_common.h"
+#include "mas_lds.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -522,13 +522,7 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
 // receives { M[4j + (l>>2)][l&3] : j=0..3 } where M[s][e] is element e of lane s's 8 bytes.  With lane s pointed at
 // pixel (s>>2), channels 4(s&3)..+3, lane l ends up with channel l of 4 consecutive pixels -- an MFMA operand run.
 // Per-lane addresses also make the 3x3 tap shifts free (any pixel offset is just an address).
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* a0, const unsigned char* a1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-    const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return *reinterpret_cast<const bf16x8*>(&v);
-}
+// (the read itself: lds_read_tr16 / tr_frag in mas_lds.h)
 
 template <int KS, int BCI_>
 struct TrGeo {

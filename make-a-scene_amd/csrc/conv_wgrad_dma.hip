@@ -20,7 +20,7 @@
 //     is pending and puts an `s_waitcnt vmcnt(0)` in front of the first ds_read_b64_tr_b16 that follows (its transpose-read
 //     intrinsic carries no memory operand to disambiguate) -- which waits for the look-ahead that was issued a few hundred
 //     cycles earlier, every tile.  Ordering is entirely by the counted waits below.
-#include "mas_common.h"
+#include "mas_lds.h"
 
 namespace {
 
@@ -42,34 +42,15 @@ constexpr int D_DY = 128 * 256;                // one dY tile: 128 pixels x 128 
 constexpr int D_XP = 23 * 1024;                // one patch: 180 pixels x 128 B -> 23 DMA pieces of 8 pixels
 constexpr int D_SS = 2 * 1024;                 // scale/shift rows of two tiles (64 channels x 2 floats = 512 B, in a 1 KiB DMA piece)
 constexpr int D_LDS = 2 * D_DY + 3 * D_XP + D_SS;     // 138240 B
-constexpr int D_OOB = (int)0x80000000;
 
-typedef __attribute__((ext_vector_type(4))) short d_s16x4;
 __device__ __forceinline__ bf16x8 d_tr_frag(const unsigned char* a0, const unsigned char* a1) {
 #ifdef D_ABL_NOREAD     // timing experiment only: fragments without LDS reads
     { const unsigned k = (unsigned)(size_t)a0 | 0x3f803f80u; u32x4 q = {k, k, k, k}; return *reinterpret_cast<const bf16x8*>(&q); }
 #endif
-    const d_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) d_s16x4*)a0);
-    const d_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) d_s16x4*)a1);
-    const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return *reinterpret_cast<const bf16x8*>(&v);
+    return tr_frag(a0, a1);
 }
 
 #define D_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-
-typedef __attribute__((ext_vector_type(4))) int d_i32x4;
-// one LDS-DMA piece: 64 lanes x 16 B from descriptor `rs` at per-lane byte offset `vo` (out of range -> zeros) to LDS byte
-// address `lds` (wave-uniform) + 16 lane
-__device__ __forceinline__ void d_dma16(d_i32x4 rs, unsigned lds, int vo) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" :: "s"(lds), "v"(vo), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ d_i32x4 d_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    d_i32x4 r = {(int)(unsigned)a, (int)(unsigned)(a >> 32), (int)bytes, 0x00020000};
-    r[0] = __builtin_amdgcn_readfirstlane(r[0]); r[1] = __builtin_amdgcn_readfirstlane(r[1]);
-    r[2] = __builtin_amdgcn_readfirstlane(r[2]); r[3] = __builtin_amdgcn_readfirstlane(r[3]);
-    return r;
-}
 
 template <int I> struct d_ic { static constexpr int v = I; };
 
@@ -114,9 +95,9 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
     const int co0 = co_t * 128, ci0 = ci_t * 64;
     const int n_mine = (p.n_pt - split + p.nsplit - 1) / p.nsplit;     // tiles of this work-group: split, split + nsplit, ...
 
-    const d_i32x4 rs_dy = d_rsrc(p.dy, KS == 2 ? p.dy_bytes : (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2));
-    const d_i32x4 rs_x = d_rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
-    const d_i32x4 rs_ss = d_rsrc(p.ss, ACT ? (unsigned)((size_t)p.N * p.Cin * 8) : 0u);
+    const i32x4 rs_dy = rsrc(p.dy, KS == 2 ? p.dy_bytes : (unsigned)((size_t)p.N * p.Ho * p.Wo * p.Cout * 2));
+    const i32x4 rs_x = rsrc(p.x, (unsigned)((size_t)p.N * p.H * p.W * p.Cin * 2));
+    const i32x4 rs_ss = rsrc(p.ss, ACT ? (unsigned)((size_t)p.N * p.Cin * 8) : 0u);
 
     // ---- tile cursor: the decode (image, tile row, tile column) is advanced incrementally (no division in the loop) and parks on
     //      the last tile (harmless re-reads at the end)
@@ -169,7 +150,7 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
         prpc[k] = pr | (pc << 8);
         const int r = (pr - pad_top) >> ups, cc = (pc - pad_left) >> ups;               // arithmetic shifts: -1 >> 1 == -1
         const int blk = ((lane >> 2) & 1) ^ ((P >> 1) & 1);
-        xL[k] = (P < D_NPP) ? ((r * p.W + cc) * p.Cin + blk * 32 + (lane & 3) * 8) * 2 : D_OOB;
+        xL[k] = (P < D_NPP) ? ((r * p.W + cc) * p.Cin + blk * 32 + (lane & 3) * 8) * 2 : OOB_VOFFSET;
     }
 
     // dY: wave w moves pieces DYK w .. DYK w + DYK - 1 (4 pixels x 256 B each); lane -> pixel 4 piece + (lane >> 4), physical 64-byte
@@ -181,7 +162,7 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
             vo = dyL + (c.ud + k * 4 * dy_px);
             if (!c.fd) {                            // ragged tile (uniform branch): rows / columns past the map read as zeros
                 const bool ok = (c.h0 + wave < p.Ho) && (c.w0 + 4 * k + (lane >> 4) < p.Wo);
-                vo = ok ? vo : D_OOB;
+                vo = ok ? vo : OOB_VOFFSET;
             }
         } else {
             const int lane = fresh_lane();
@@ -189,12 +170,12 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
             const int ho = c.h0 + (pix >> 4), wo = c.w0 + (pix & 15);
             const int blk = ((lane >> 2) & 3) ^ (pix & 3);
             const bool ok = (ho < p.Ho) && (wo < p.Wo);
-            vo = ok ? (int)((((size_t)(c.n * p.Ho + ho) * p.Wo + wo) * p.Cout + co0 + blk * 32 + (lane & 3) * 8) * 2) : D_OOB;
+            vo = ok ? (int)((((size_t)(c.n * p.Ho + ho) * p.Wo + wo) * p.Cout + co0 + blk * 32 + (lane & 3) * 8) * 2) : OOB_VOFFSET;
         }
 #ifdef D_ABL_NODMA
         if (p.N != -12345) return;
 #endif
-        d_dma16(rs_dy, __builtin_amdgcn_readfirstlane(lds0 + buf * D_DY + piece * 1024), vo);
+        dma16(rs_dy, __builtin_amdgcn_readfirstlane(lds0 + buf * D_DY + piece * 1024), vo);
     };
     // patch: wave w moves pieces w, w + NW, .. below 23 (8 pixels x 128 B each); lane -> patch pixel 8 piece + (lane >> 3), physical
     // block (lane >> 2) & 1 holding logical block ^ ((pixel >> 1) & 1), slot lane & 3
@@ -205,19 +186,19 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
     auto x_issue = [&](const TC& c, int buf, int k) {
         if (wave + NW * k >= 23) return;
         int vo = xL[k] + c.ux;                      // (dead lanes: the marker stays out of range after the add)
-        if (!c.fx) vo = x_inb(k, c) ? vo : D_OOB;   // edge tile (uniform branch): halo pixels outside the image read as zeros
+        if (!c.fx) vo = x_inb(k, c) ? vo : OOB_VOFFSET;   // edge tile (uniform branch): halo pixels outside the image read as zeros
 #ifdef D_ABL_NODMA
         if (p.N != -12345) return;
 #endif
-        d_dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + 2 * D_DY + buf * D_XP + (wave + NW * k) * 1024), vo);
+        dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + 2 * D_DY + buf * D_XP + (wave + NW * k) * 1024), vo);
     };
     // (scale, shift) of the 64 channels of a tile's image: 512 B, lanes 0..31 of one DMA piece, ONE copy per work-group (wave 0 moves
     // it BEFORE the barrier that precedes its first use)
     auto ss_issue = [&](const TC& c, int par) {
         if (wave != 0) return;
         const int lane = fresh_lane();
-        const int vo = lane < 32 ? (int)(((size_t)c.n * p.Cin + ci0) * 8 + lane * 16) : D_OOB;
-        d_dma16(rs_ss, __builtin_amdgcn_readfirstlane(lds0 + 2 * D_DY + 3 * D_XP + par * 1024), vo);
+        const int vo = lane < 32 ? (int)(((size_t)c.n * p.Cin + ci0) * 8 + lane * 16) : OOB_VOFFSET;
+        dma16(rs_ss, __builtin_amdgcn_readfirstlane(lds0 + 2 * D_DY + 3 * D_XP + par * 1024), vo);
     };
     // GroupNorm(+SiLU) in place: this thread takes LOGICAL 16-byte slot lane & 7 (channels ci0 + 8 (lane & 7) ..+7) of the pixels of
     // its own wave's pieces; padding pixels were written as zeros by the DMA and stay zero
@@ -338,9 +319,9 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
                 // costs this kernel as much as an issued LDS read (R2.2's cost model).  (SPLIT 1: a step needs all three kw or none.)
                 if (!kw_needed(pr, 0)) return;
                 const unsigned char* b0 = smem + bxo[0][pr & 1] + pr * (D_PW * 128);
-                const d_s16x4 r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) d_s16x4*)b0);
-                const d_s16x4 r1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) d_s16x4*)(b0 + 4 * 128));
-                const d_s16x4 r2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) d_s16x4*)(b0 + 8 * 128));
+                const s16x4 r0 = lds_read_tr16(b0);
+                const s16x4 r1 = lds_read_tr16(b0 + 4 * 128);
+                const s16x4 r2 = lds_read_tr16(b0 + 8 * 128);
                 const u32x2 a = *reinterpret_cast<const u32x2*>(&r0), b = *reinterpret_cast<const u32x2*>(&r1), c = *reinterpret_cast<const u32x2*>(&r2);
                 const u32x4 f0 = {a[0], a[1], b[0], b[1]}, f2 = {a[1], b[0], b[1], c[0]};
                 const u32x4 f1 = {__builtin_amdgcn_alignbit(a[1], a[0], 16), __builtin_amdgcn_alignbit(b[0], a[1], 16),

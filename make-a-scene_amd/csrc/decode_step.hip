@@ -6,7 +6,7 @@
 //   decode_embed_kernel     image-token embedding + row / column position embedding of the token sampled at the previous step;
 //   sample_kernel           guidance mix, logits write-out, teacher forcing / greedy argmax / top-k + Gumbel-max draw (Philox);
 //   advance_kernel          one thread: the step counters + 1, after every other kernel of the step has read them (stream order).
-#include "mas_common.h"
+#include "attn_decode_core.h"
 #include "mas_philox.h"
 #include <math.h>
 
@@ -18,11 +18,10 @@ namespace {
 // `past` was appended beforehand.  The append comes first: lanes 0 .. NU-1 copy the 16-byte units of this (b, h) slice of k_new /
 // v_new into cache row `past`, then __syncthreads() -- a workgroup-scope release fence (the stores are complete), the barrier, and an
 // acquire fence -- orders those stores before every lane's loads, so the lane that owns key `past` (tid == past % 256) reads the row
-// back from the cache like any other key.  Everything after the barrier is attn_decode_kernel's text, so the compiler builds the same
-// arithmetic for it (a register hand-off inside the key loop changed how it contracts the dot products: not bit for bit).
+// back from the cache like any other key.  Everything after the barrier is the SAME FUNCTION attn_decode_kernel calls (attn_decode_body,
+// attn_decode_core.h), not a copy of it (a variant with a register hand-off inside the key loop contracted the dot products
+// differently: not bit for bit).
 // ------------------------------------------------------------------------------------------------------------------------------
-constexpr int DNT = 256;
-
 struct DecodeDevParams {
     const void* q; const void* kn; const void* vn;   // the new row's q / k / v (slices of the qkv projection)
     void* kc; void* vc; void* o;
@@ -34,14 +33,13 @@ struct DecodeDevParams {
 };
 
 template <typename T, int HD>
-__global__ __launch_bounds__(DNT) void attn_decode_dev_kernel(DecodeDevParams p) {
+__global__ __launch_bounds__(DECODE_NT) void attn_decode_dev_kernel(DecodeDevParams p) {
     constexpr int EPU = 16 / (int)sizeof(T);
     constexpr int NU = HD / EPU;                 // 16-byte units per row
     const int past = *p.past;
     if (past < 0 || past >= p.cap) return;       // misuse guard (uniform over the grid): nothing read or written past the cache
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H;
-    const int L = past + 1;                      // keys visible to the query: 0 .. past
 
     if (tid < 2 * NU) {                          // append: unit tid % NU of k (tid < NU) or v
         const bool isv = tid >= NU;
@@ -52,94 +50,20 @@ __global__ __launch_bounds__(DNT) void attn_decode_dev_kernel(DecodeDevParams p)
     }
     __syncthreads();
 
-    const T* __restrict__ Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.new_bs + (size_t)h * HD;
-    const T* __restrict__ K = reinterpret_cast<const T*>(p.kc) + (size_t)b * p.c_bs + (size_t)h * HD;
-    const T* __restrict__ V = reinterpret_cast<const T*>(p.vc) + (size_t)b * p.c_bs + (size_t)h * HD;
-
-    float qf[HD];                                // the query, pre-scaled (transformer.py:56: q / sqrt(hd))
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const u32x4 raw = *reinterpret_cast<const u32x4*>(Q + u * EPU);
-        const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-        for (int j = 0; j < EPU; ++j) qf[u * EPU + j] = (float)e[j] * p.scale;
-    }
-
-    float m = -1e30f, l = 0.0f, o[HD];
-#pragma unroll
-    for (int d = 0; d < HD; ++d) o[d] = 0.0f;
-
-    for (int key = tid; key < L; key += DNT) {
-        const T* kr = K + (size_t)key * p.ld_c;
-        const T* vr = V + (size_t)key * p.ld_c;
-        float s = 0.0f;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(kr + u * EPU);
-            const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-            for (int j = 0; j < EPU; ++j) s += qf[u * EPU + j] * (float)e[j];
-        }
-        const float m_new = fmaxf(m, s);
-        const float a = __expf(m - m_new), pv = __expf(s - m_new);
-        l = l * a + pv;
-        m = m_new;
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(vr + u * EPU);
-            const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-            for (int j = 0; j < EPU; ++j) o[u * EPU + j] = o[u * EPU + j] * a + pv * (float)e[j];
-        }
-    }
-
-    // ---- merge the 64 lanes of a wave: common maximum, rescale, butterfly sums (fixed order: deterministic) ----
-    float mw = m;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mw = fmaxf(mw, __shfl_xor(mw, off));
-    const float f = __expf(m - mw);              // lanes without a key: m = -1e30 -> f = 0 (or 1 when the whole wave is empty: l = o = 0)
-    l *= f;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) l += __shfl_xor(l, off);
-#pragma unroll
-    for (int d = 0; d < HD; ++d) {
-        float x = o[d] * f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-        o[d] = x;
-    }
-    // ---- merge the 4 waves through LDS ----
-    __shared__ float red[4][HD + 2];
-    if (lane == 0) {
-        red[wave][HD] = mw; red[wave][HD + 1] = l;
-    }
-    if (lane < HD / 1 && lane < 64) {
-#pragma unroll
-        for (int d = 0; d < HD; ++d) if ((d & 63) == lane) red[wave][d] = o[d];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const float m0 = red[0][HD], m1 = red[1][HD], m2 = red[2][HD], m3 = red[3][HD];
-        const float mt = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-        const float f0 = __expf(m0 - mt), f1 = __expf(m1 - mt), f2 = __expf(m2 - mt), f3 = __expf(m3 - mt);
-        const float lt = red[0][HD + 1] * f0 + red[1][HD + 1] * f1 + red[2][HD + 1] * f2 + red[3][HD + 1] * f3;
-        const float inv = 1.0f / lt;
-        T* dst = reinterpret_cast<T*>(p.o) + (size_t)b * p.o_bs + (size_t)h * HD;
-        for (int d = lane; d < HD; d += 64)
-            dst[d] = (T)((red[0][d] * f0 + red[1][d] * f1 + red[2][d] * f2 + red[3][d] * f3) * inv);
-    }
+    const T* Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.new_bs + (size_t)h * HD;
+    const T* K = reinterpret_cast<const T*>(p.kc) + (size_t)b * p.c_bs + (size_t)h * HD;
+    const T* V = reinterpret_cast<const T*>(p.vc) + (size_t)b * p.c_bs + (size_t)h * HD;
+    T* dst = reinterpret_cast<T*>(p.o) + (size_t)b * p.o_bs + (size_t)h * HD;
+    attn_decode_body<T, HD>(Q, K, V, dst, p.ld_c, p.ld_c, past + 1, p.scale);   // keys visible to the query: 0 .. past
 }
 
 template <typename T>
 int launch_decode_dev(const DecodeDevParams& p, int hd, hipStream_t s) {
     const dim3 grid((unsigned)(p.B * p.H));
-    switch (hd) {
-        case 16: hipLaunchKernelGGL((attn_decode_dev_kernel<T, 16>), grid, dim3(DNT), 0, s, p); break;
-        case 32: hipLaunchKernelGGL((attn_decode_dev_kernel<T, 32>), grid, dim3(DNT), 0, s, p); break;
-        case 64: hipLaunchKernelGGL((attn_decode_dev_kernel<T, 64>), grid, dim3(DNT), 0, s, p); break;
-        case 128: hipLaunchKernelGGL((attn_decode_dev_kernel<T, 128>), grid, dim3(DNT), 0, s, p); break;
-        default: MAS_FAIL(MAS_EUNSUPPORTED, "attn_decode_dev: head_dim %d not in {16,32,64,128}", hd);
-    }
+    if (!decode_dispatch_hd(hd, [&](auto hd_c) {
+            hipLaunchKernelGGL((attn_decode_dev_kernel<T, decltype(hd_c)::value>), grid, dim3(DECODE_NT), 0, s, p);
+        }))
+        MAS_FAIL(MAS_EUNSUPPORTED, "attn_decode_dev: head_dim %d not in {16,32,64,128}", hd);
     MAS_CHECK_LAUNCH("attn_decode_dev");
     return MAS_OK;
 }

@@ -26,20 +26,6 @@ constexpr int L1_CHUNK = NT * 4 * L1_QUADS;
 
 struct RowTable { MasFaceRow r[MAS_FACE_MAX_ROWS]; };
 
-template <typename T> struct Quad;
-template <> struct Quad<float> {
-    static __device__ __forceinline__ f32x4 ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-    static __device__ __forceinline__ void st(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-};
-template <> struct Quad<bf16_t> {
-    static __device__ __forceinline__ f32x4 ld(const bf16_t* p) {
-        const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
-        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    }
-    static __device__ __forceinline__ void st(bf16_t* p, f32x4 v) {
-        *reinterpret_cast<bf16x4*>(p) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    }
-};
 template <typename T> __device__ __forceinline__ float round_to(float v) { return (float)(T)v; }
 
 __device__ __forceinline__ float ld_any(const void* p, int dtype, long long off) {

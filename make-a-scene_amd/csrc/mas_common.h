@@ -66,6 +66,22 @@ template <> struct Elem<bf16_t> {
     __device__ static __forceinline__ void st(bf16_t* p, float v) { *p = (bf16_t)v; }
 };
 
+// 4 consecutive elements (p 16-byte (f32) / 8-byte (bf16) aligned) as fp32, fp32 or bf16 storage
+template <typename T> struct Quad;
+template <> struct Quad<float> {
+    static __device__ __forceinline__ f32x4 ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+    static __device__ __forceinline__ void st(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+};
+template <> struct Quad<bf16_t> {
+    static __device__ __forceinline__ f32x4 ld(const bf16_t* p) {
+        const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
+        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+    }
+    static __device__ __forceinline__ void st(bf16_t* p, f32x4 v) {
+        *reinterpret_cast<bf16x4*>(p) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+    }
+};
+
 // 8 consecutive elements as a register vector
 template <typename T> struct Vec8;
 template <> struct Vec8<float> { typedef f32x8 type; };

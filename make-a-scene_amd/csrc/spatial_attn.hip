@@ -22,7 +22,7 @@
 // apply: M tiles four ahead and issued before the softmax) and does the softmax / dS arithmetic on the accumulators instead of
 // bouncing fp32 scores through LDS row by row: forward 58 -> 23 us, backward 72 + 95 -> 31 + 43 us (profiles/r04_spatial_attn.txt).
 // No atomics: every output element is written exactly once (deterministic).
-#include "mas_common.h"
+#include "mas_lds.h"
 #include <math.h>
 
 namespace {
@@ -51,14 +51,6 @@ struct SpParams {
     int N, S, C;
     float scale;
 };
-
-typedef __attribute__((ext_vector_type(4))) short sp_s16x4;
-__device__ __forceinline__ bf16x8 sp_tr_frag(const unsigned char* a0, const unsigned char* a1) {
-    const sp_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) sp_s16x4*)a0);
-    const sp_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) sp_s16x4*)a1);
-    const __attribute__((ext_vector_type(8))) short v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return *reinterpret_cast<const bf16x8*>(&v);
-}
 
 // LDS map (bytes); row strides padded so that 32 consecutive rows do not share banks.  The scores never touch LDS in fp32 (round 4):
 // they stay in the MFMA accumulators through the softmax / dS arithmetic, only the bf16 P / dS operand of the second product is staged.
@@ -259,7 +251,7 @@ __device__ __forceinline__ void sp_apply_run(f32x16 (&acc)[CPW], u32x4 (&pf)[4][
 #pragma unroll
                 for (int i = 0; i < CPW; ++i) {
                     const int ct = min(wave + NW * i, n_ct - 1);         // a channel tile past C recomputes the last real one; sp_store drops it
-                    aq[ks][i] = sp_tr_frag(a_lane + ct * 64, a_lane + ct * 64 + 4 * RM);
+                    aq[ks][i] = tr_frag(a_lane + ct * 64, a_lane + ct * 64 + 4 * RM);
                 }
             }
             if (t + 1 < nt) sp_rows_commit(pf[(t + 1) & 3], (t & 1) ? ms0 : ms1, RM, sp_rot_tile(t + 1, rot, nt) * 32, S, mp);

@@ -327,6 +327,15 @@ int mas_attn_decode(const void* q, const void* k_cache, const void* v_cache, voi
  *   step k:  counter = (j >> 2, k, r, lo32(offset)),  32-bit slot j & 3 (words x, y, z, w),  u = ((bits >> 9) + 0.5) * 2^-23
  *   (exact in float32, in [2^-24, 1 - 2^-24]: never 0 or 1, so every score is finite).
  *   (make-a-scene_amd/csrc/mas_philox.h: mas_sample_bits4, mas_sample_uniform.)
+ * Top-p: mas_sample_tokens_topp is mas_sample_tokens with params = {temperature, s, top_p} (three device floats); both launch the same
+ *   kernel.  In mode 1, with K = {j : lg_j >= kth} the set top-k keeps (everything when top-k is off), q = softmax(lg restricted to K)
+ *   and M_>(x) = the sum of q_i over i in K with lg_i > x (strict), entry j stays iff j is in K and M_>(lg_j) <= top_p: the usual
+ *   nucleus rule (drop the sorted entries whose inclusive cumulative probability exceeds top_p, shifted by one so that the first one
+ *   over the line stays) stated on values.  The maximum and its ties always stay; the kept set is {lg_j >= t*} for one value t*, ties
+ *   at t* kept; top-k first, then top-p on the re-normalised masses.  The token is the Gumbel-max draw over the kept set, same mapping.
+ *   !(top_p < 1) (1, more, NaN) is off: the instructions and tokens of mas_sample_tokens.  top_p <= 0 keeps the maximum and its ties.
+ *   Modes 0 and 2 ignore it.  t* comes from a radix select over fixed-point masses floor(exp(lg_j - max) * 2^32) summed as 64-bit
+ *   integers: repeatable bit for bit, exact line for V < 2^21; an entry 2^-32 below the maximum weighs nothing (it can still be kept).
  * mas_decode_advance: counters[0 .. n-1] += 1 (one thread, n <= 8), ordered after the step's kernels by the stream.                  */
 int mas_attn_decode_dev(const void* q, const void* k_new, const void* v_new, long long new_bs, void* k_cache, void* v_cache, int ld_c,
                         long long c_bs, int capacity, void* o, long long o_bs, int dtype, int B, int H, int hd, const int32_t* past,
@@ -336,6 +345,10 @@ int mas_decode_embed(const int64_t* tokens, long long ld_tok, const int32_t* ste
 int mas_sample_tokens(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode, int top_k,
                       const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced, long long ld_forced,
                       int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out, void* stream);
+int mas_sample_tokens_topp(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode, int top_k,
+                           const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
+                           long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
+                           void* stream);
 int mas_decode_advance(int32_t* counters, int n, void* stream);
 
 /* ---- decode attention split over keys (low batch * heads: make-a-scene_amd/csrc/attn_decode_split.hip).  mas_attn_decode /

@@ -4,7 +4,7 @@
 //   attn_decode_dev_kernel  mas_attn_decode with nq = 1 whose cache length is a device int32 and which appends the new key / value
 //                           row itself;
 //   decode_embed_kernel     image-token embedding + row / column position embedding of the token sampled at the previous step;
-//   sample_kernel           guidance mix, logits write-out, teacher forcing / greedy argmax / top-k + Gumbel-max draw (Philox);
+//   sample_kernel           guidance mix, logits write-out, teacher forcing / greedy argmax / top-k + top-p + Gumbel-max draw (Philox);
 //   advance_kernel          one thread: the step counters + 1, after every other kernel of the step has read them (stream order).
 #include "attn_decode_core.h"
 #include "mas_philox.h"
@@ -93,8 +93,9 @@ __global__ __launch_bounds__(ENT) void decode_embed_kernel(const long long* __re
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // sampler: one work-group per output row.  Passes over the row (L2-resident: re-read instead of held, so V is bounded by nothing
-// but int range): write-out / argmax, then for top-k four 8-bit radix passes over order-preserving keys in LDS, then the Gumbel-max
-// draw.  Guidance mix and temperature in the eager code's fp32 operations, no contraction.
+// but int range): write-out / argmax, then for top-k four 8-bit radix passes over order-preserving keys in LDS, for top-p a maximum
+// pass and four more radix passes whose bins hold fixed-point softmax mass instead of counts, then the Gumbel-max draw.  Guidance mix
+// and temperature in the eager code's fp32 operations, no contraction.
 // ------------------------------------------------------------------------------------------------------------------------------
 constexpr int SNT = 256;
 enum { MODE_GREEDY = 0, MODE_SAMPLE = 1, MODE_FORCED = 2 };
@@ -102,7 +103,8 @@ enum { MODE_GREEDY = 0, MODE_SAMPLE = 1, MODE_FORCED = 2 };
 struct SampleParams {
     const float* logits; long long ld_l, u_off;     // row r at logits + r*ld_l, its unconditional row u_off further
     int B, V, guided, mode, top_k, L;
-    const float* params;                             // {temperature, cond_scale}
+    const float* params;                             // {temperature, cond_scale} and, with has_p, top_p
+    int has_p;                                       // params holds a third float (mas_sample_tokens_topp)
     const long long* seed;                           // {seed, offset}
     const int* step;
     const long long* forced; long long ld_f;
@@ -214,6 +216,73 @@ __global__ __launch_bounds__(SNT) void sample_kernel(SampleParams p) {
         kth = okey_inv(prefix);
     }
 
+    // ---- top-p threshold (include/mas_hip.h, "Top-p"): t* = the largest value x whose mass at or above it exceeds top_p of the total over
+    // the top-k set.  The same radix select as above with masses in the bins: w_j = floor(exp(lg_j - max) * 2^32) added as 64-bit integers
+    // -- exact, so no sum depends on the order of the atomics, and the bins below a chosen bin add up to exactly its mass: every level
+    // finds its crossing inside the bin chosen above it.  `above` is the mass of the keys greater than every key with the prefix.
+    if (p.has_p && p.params[2] < 1.f) {              // uniform; NaN and >= 1 are off, like a launch without the third float
+        const float tp = fmaxf(p.params[2], 0.f);
+        float mv = -INFINITY;
+        int mi = 0x7fffffff;
+        for (int j = tid; j < V; j += SNT) {
+            const float lg = mixed(j) / T;
+            if (lg >= kth) better(mv, mi, lg, j);
+        }
+        const int at = block_argmax(mv, mi, sv, si);
+        __syncthreads();                             // sv / si are read: the draw's reduction below may write them again
+        const float mx = at < V ? mixed(at) / T : INFINITY;
+        if (mx < INFINITY && mx > -INFINITY) {       // uniform.  No finite maximum: no softmax to cut, the top-k set stays as it is
+            __shared__ unsigned long long mass[256];
+            __shared__ unsigned long long msel[2];
+            unsigned prefix = 0, pmask = 0;
+            unsigned long long above = 0, line = 0;  // line = floor(top_p * W): for integers, incl > top_p * W  <=>  incl > line
+            bool cut = true;
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                mass[tid] = 0;
+                __syncthreads();
+                for (int j = tid; j < V; j += SNT) {
+                    const float lg = mixed(j) / T;
+                    if (!(lg >= kth)) continue;
+                    const unsigned key = okey(lg);
+                    if ((key & pmask) == prefix)
+                        atomicAdd(&mass[(key >> shift) & 255u], (unsigned long long)(expf(lg - mx) * 4294967296.f));
+                }
+                __syncthreads();
+                if (wave == 0) {                     // bins in descending order, as in the count select
+                    unsigned long long c[4], tot = 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { c[e] = mass[255 - 4 * lane - e]; tot += c[e]; }
+                    unsigned long long incl = tot;
+#pragma unroll
+                    for (int off = 1; off < 64; off <<= 1) {
+                        const unsigned long long t = __shfl_up(incl, off);
+                        if (lane >= off) incl += t;
+                    }
+                    if (shift == 24) line = (unsigned long long)((double)tp * (double)__shfl(incl, 63));   // W: exact below 2^53
+                    const unsigned long long bal = __ballot(above + incl > line);
+                    if (bal == 0) {
+                        if (lane == 0) msel[0] = 256;    // the line is not below the total (rounding at top_p next to 1): no cut
+                    } else if (lane == __ffsll(bal) - 1) {
+                        unsigned long long before = above + incl - tot;
+                        int e = 0;
+                        for (; e < 3; ++e) {
+                            if (before + c[e] > line) break;
+                            before += c[e];
+                        }
+                        msel[0] = 255u - 4u * lane - e;
+                        msel[1] = before;
+                    }
+                }
+                __syncthreads();
+                if (msel[0] > 255) { cut = false; break; }     // uniform
+                prefix |= (unsigned)msel[0] << shift;
+                pmask |= 255u << shift;
+                above = msel[1];
+            }
+            if (cut) kth = okey_inv(prefix);         // a key of the top-k set: never below the top-k threshold
+        }
+    }
+
     // ---- Gumbel-max over the kept entries: argmax(lg_j - log(-log u_j)), lowest index on ties ----
     const unsigned long long sd = (unsigned long long)p.seed[0];
     const unsigned s0 = (unsigned)sd, s1 = (unsigned)(sd >> 32), off = (unsigned)(unsigned long long)p.seed[1];
@@ -278,11 +347,11 @@ extern "C" int mas_decode_embed(const int64_t* tokens, long long ld_tok, const i
     return MAS_OK;
 }
 
-extern "C" int mas_sample_tokens(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode,
-                                 int top_k, const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
-                                 long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
-                                 void* stream) {
-    MAS_ENTER();
+namespace {
+int sample_tokens_launch(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode, int top_k,
+                         const float* params, int has_p, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
+                         long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
+                         void* stream) {
     if (!logits || !params || !step || !tokens) MAS_FAIL(MAS_EINVAL, "sample_tokens: null argument");
     if (B <= 0 || V <= 0 || L <= 0 || ld_logits < 0 || ld_tokens < L || (logits_out && ld_logits_out < (long long)L * V))
         MAS_FAIL(MAS_EINVAL, "sample_tokens: bad shape B=%d V=%d L=%d", B, V, L);
@@ -292,13 +361,32 @@ extern "C" int mas_sample_tokens(const float* logits, long long ld_logits, long 
     SampleParams p;
     p.logits = logits; p.ld_l = ld_logits; p.u_off = guided ? uncond_off : 0;
     p.B = B; p.V = V; p.guided = guided != 0; p.mode = mode; p.top_k = top_k; p.L = L;
-    p.params = params; p.seed = reinterpret_cast<const long long*>(seed); p.step = step;
+    p.params = params; p.has_p = has_p; p.seed = reinterpret_cast<const long long*>(seed); p.step = step;
     p.forced = reinterpret_cast<const long long*>(forced); p.ld_f = ld_forced;
     p.tokens = reinterpret_cast<long long*>(tokens); p.ld_t = ld_tokens;
     p.lout = logits_out; p.ld_lo = ld_logits_out;
     hipLaunchKernelGGL(sample_kernel, dim3((unsigned)B), dim3(SNT), 0, reinterpret_cast<hipStream_t>(stream), p);
     MAS_CHECK_LAUNCH("sample_tokens");
     return MAS_OK;
+}
+}  // namespace
+
+extern "C" int mas_sample_tokens(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode,
+                                 int top_k, const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
+                                 long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
+                                 void* stream) {
+    MAS_ENTER();
+    return sample_tokens_launch(logits, ld_logits, uncond_off, B, V, guided, mode, top_k, params, 0, seed, step, L, forced, ld_forced,
+                                tokens, ld_tokens, logits_out, ld_logits_out, stream);
+}
+
+extern "C" int mas_sample_tokens_topp(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode,
+                                      int top_k, const float* params, const int64_t* seed, const int32_t* step, int L,
+                                      const int64_t* forced, long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out,
+                                      long long ld_logits_out, void* stream) {
+    MAS_ENTER();
+    return sample_tokens_launch(logits, ld_logits, uncond_off, B, V, guided, mode, top_k, params, 1, seed, step, L, forced, ld_forced,
+                                tokens, ld_tokens, logits_out, ld_logits_out, stream);
 }
 
 extern "C" int mas_decode_advance(int32_t* counters, int n, void* stream) {

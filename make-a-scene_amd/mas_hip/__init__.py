@@ -145,6 +145,8 @@ _SIGNATURES = {
     "mas_decode_embed": (_i, [_p, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),
     "mas_sample_tokens": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _p,
                                C.c_longlong, _p]),
+    "mas_sample_tokens_topp": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong,
+                                    _p, C.c_longlong, _p]),
     "mas_decode_advance": (_i, [_p, _i, _p]),
     "mas_attn_decode_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong,
                                    C.c_longlong, _f, _i, _p, _sz, _p]),

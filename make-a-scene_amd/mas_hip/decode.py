@@ -108,8 +108,10 @@ def decode_embed(tokens: torch.Tensor, step: torch.Tensor, img_emb: torch.Tensor
 
 def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, params: torch.Tensor, mode: int, *, top_k: int = 0,
                   guided: bool = False, seed: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
-                  logits_out: Optional[torch.Tensor] = None, rows: Optional[int] = None) -> torch.Tensor:
-    """One token per row into tokens[r, *step] (``mas_sample_tokens``).  logits fp32 [R, V] with R = 2B under guidance (conditional rows
+                  logits_out: Optional[torch.Tensor] = None, rows: Optional[int] = None, top_p: bool = False) -> torch.Tensor:
+    """One token per row into tokens[r, *step] (``mas_sample_tokens``; with ``top_p`` ``mas_sample_tokens_topp``, whose params hold a
+    third float, the nucleus mass: include/mas_hip.h "Top-p" -- the value lives on the device like the temperature, the flag only selects
+    the entry).  logits fp32 [R, V] with R = 2B under guidance (conditional rows
     first, as ``generate`` stacks them) or B, or a single [1, V] / [2, V] row shared by ``rows`` output rows (row stride 0: the statistics
     tests).  params fp32 {temperature, cond_scale}; seed int64 {seed, offset}; forced int64 [B, L] (teacher forcing); logits_out fp32
     [B, L, V] receives the mixed row."""
@@ -119,8 +121,9 @@ def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor
     nb, length = tokens.shape
     v = logits.shape[1]
     shared = rows is not None
-    if tokens.dtype != torch.int64 or tokens.stride(1) != 1 or step.dtype != torch.int32 or params.dtype != torch.float32 or params.numel() < 2:
-        raise RuntimeError("sample_tokens: tokens int64 [B, L], step int32, params fp32 {temperature, cond_scale}")
+    if tokens.dtype != torch.int64 or tokens.stride(1) != 1 or step.dtype != torch.int32 or params.dtype != torch.float32 \
+            or params.numel() < (3 if top_p else 2) or not params.is_contiguous():
+        raise RuntimeError("sample_tokens: tokens int64 [B, L], step int32, params fp32 {temperature, cond_scale} (and top_p with top_p=True)")
     if shared:
         if rows != nb or logits.shape[0] != (2 if guided else 1):
             raise RuntimeError("sample_tokens: a shared logits row (and its unconditional row) for every output row")
@@ -135,10 +138,10 @@ def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor
         raise RuntimeError("sample_tokens: teacher forcing needs int64 tokens shaped like the output")
     if logits_out is not None and (logits_out.dtype != torch.float32 or logits_out.shape != (nb, length, v) or not logits_out.is_contiguous()):
         raise RuntimeError("sample_tokens: logits_out fp32 contiguous [B, L, V]")
-    check(lib().mas_sample_tokens(_ptr(logits), ld, uoff, nb, v, int(guided), int(mode), int(top_k or 0), _ptr(params), _ptr(seed),
-                                  _ptr(step), length, _ptr(forced), forced.stride(0) if forced is not None else 0, _ptr(tokens),
-                                  tokens.stride(0), _ptr(logits_out), logits_out.stride(0) if logits_out is not None else 0, _stream()),
-          "sample_tokens")
+    entry = lib().mas_sample_tokens_topp if top_p else lib().mas_sample_tokens
+    check(entry(_ptr(logits), ld, uoff, nb, v, int(guided), int(mode), int(top_k or 0), _ptr(params), _ptr(seed), _ptr(step), length,
+                _ptr(forced), forced.stride(0) if forced is not None else 0, _ptr(tokens), tokens.stride(0), _ptr(logits_out),
+                logits_out.stride(0) if logits_out is not None else 0, _stream()), "sample_tokens")
     return tokens
 
 

@@ -8,12 +8,13 @@ sampler kernel, and every later token k = 1 .. L-1 is one replay of a graph capt
     per layer: ln_in, qkv, decode attention that appends the row at past = plen + k - 1 (``mas_attn_decode_dev``, or with
                ``generate(kv_splits=n)`` its split-key pair ``mas_attn_decode_split_dev``), out_proj,
                first sandwich LayerNorm + residual, ln_out, lin1, GELU, lin2, second sandwich LayerNorm + residual
-    final LayerNorm, to_logits, sampler (``mas_sample_tokens``: tokens[:, k] and the logits row k), step counters + 1
+    final LayerNorm, to_logits, sampler (``mas_sample_tokens``, or ``mas_sample_tokens_topp`` with ``generate(top_p=p)``: tokens[:, k]
+               and the logits row k), step counters + 1
 
 The modules' own forward calls build the step (the same HIP LayerNorm / GELU kernels and library GEMMs the eager decode runs on the same
-row shapes), so teacher-forced logits equal the eager ones.  The step, the cache length, temperature, guidance scale and seed live in
-device buffers: one capture serves every token and every call with the same key (rows, guidance, sampling mode, top_k, return_logits,
-compute dtype, autocast state, device, decode-attention split count).  The graph reads the parameters and their bf16 shadows in place; an
+row shapes), so teacher-forced logits equal the eager ones.  The step, the cache length, temperature, guidance scale, top_p and seed live
+in device buffers: one capture serves every token and every call with the same key (rows, guidance, sampling mode, top_k, whether top_p
+is on -- not its value --, return_logits, compute dtype, autocast state, device, decode-attention split count).  The graph reads the parameters and their bf16 shadows in place; an
 entry whose pointers moved (``load_state_dict`` into new storage, ``.to()``, ``invalidate_weight_cache()``) is recaptured.
 
 Tokens are drawn by Gumbel-max from Philox4x32-10 (include/mas_hip.h, "Sampling"): reproducible under ``torch.manual_seed`` or a seeded
@@ -68,7 +69,7 @@ def _pointer_signature(model, bf16_autocast):
 class _Entry:
     """static buffers and the captured graph of one key"""
 
-    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1):
+    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1, top_p=False):
         dev = model.device
         d = model.transformer.layers[0].attn.hidden_dim
         heads = model.transformer.layers[0].attn.num_attn_heads
@@ -86,7 +87,8 @@ class _Entry:
         self.tokens = torch.zeros((b, length), dtype=torch.long, device=dev)
         self.forced = torch.zeros((b, length), dtype=torch.long, device=dev) if mode == decode.FORCED else None
         self.logits_out = torch.empty((b, length, v), dtype=torch.float32, device=dev) if return_logits else None
-        self.params = torch.ones(2, dtype=torch.float32, device=dev)       # {temperature, cond_scale}
+        self.top_p = top_p                                                 # which sampler entry the step calls; the value is params[2]
+        self.params = torch.ones(3, dtype=torch.float32, device=dev)       # {temperature, cond_scale, top_p}
         self.seed = torch.zeros(2, dtype=torch.int64, device=dev)          # {seed, offset}
         self.ctr = torch.zeros(2, dtype=torch.int32, device=dev)           # {k, past}
         self.sig = sig
@@ -99,7 +101,7 @@ class _Entry:
 
     def sample(self, logits):
         decode.sample_tokens(logits, self.tokens, self.ctr[0:1], self.params, self.mode, top_k=self.top_k, guided=self.guided,
-                             seed=self.seed, forced=self.forced, logits_out=self.logits_out)
+                             seed=self.seed, forced=self.forced, logits_out=self.logits_out, top_p=self.top_p)
         decode.advance(self.ctr)
 
 
@@ -157,9 +159,11 @@ def _draw_seed(generator, device):
     return s.to(device)
 
 
-def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, kv_splits=1):
+def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, kv_splits=1,
+                   top_p=None):
     """``MakeAScene.generate(..., graph=True)``; returns None outside the envelope (the caller then runs the eager path).  ``kv_splits``:
-    the resolved split count of the decode attention (1: ``mas_attn_decode_dev``; n > 1: ``mas_attn_decode_split_dev``), part of the key"""
+    the resolved split count of the decode attention (1: ``mas_attn_decode_dev``; n > 1: ``mas_attn_decode_split_dev``), part of the key.
+    ``top_p``: None (off: ``mas_sample_tokens``) or the validated nucleus mass in (0, 1); only "on" is part of the key"""
     reason = _envelope_reason(model)
     if reason is not None:
         warned = model.__dict__.setdefault("_decode_graph_warned", set())
@@ -172,10 +176,11 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     rows = 2 * b if guided else b
     mode = decode.FORCED if img_tokens is not None else (decode.GREEDY if temperature == 0 else decode.SAMPLE)
     top_k = int(top_k) if (mode == decode.SAMPLE and top_k is not None) else 0
+    p_on = mode == decode.SAMPLE and top_p is not None
     autocast = torch.is_autocast_enabled()
     ac_dtype = torch.get_autocast_gpu_dtype() if autocast else None
     dev = model.device
-    key = (b, guided, mode, top_k, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev), int(kv_splits))
+    key = (b, guided, mode, top_k, p_on, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev), int(kv_splits))
     sig = _pointer_signature(model, autocast and ac_dtype == torch.bfloat16)
     graphs = model.__dict__.setdefault("_decode_graphs", {})
     params = _param_pointers(model)
@@ -198,13 +203,14 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     logits0 = model.to_logits(hidden[:, -1:, :])[:, 0, :].float()
     kv = [(cache[i][0], cache[i][1]) for i in range(len(model.transformer.layers))]
     if e is None:
-        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits))
+        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits), p_on)
         graphs[key] = e
 
     # ---- per-call device state, then the static caches ----
     e.rewind(0)
     e.params[0].fill_(float(temperature) if mode == decode.SAMPLE else 1.0)
     e.params[1].fill_(float(cond_scale) if guided else 0.0)
+    e.params[2].fill_(float(top_p) if p_on else 1.0)
     if mode == decode.SAMPLE:
         e.seed.copy_(_draw_seed(generator, dev))
     if mode == decode.FORCED:

@@ -395,7 +395,7 @@ class MakeAScene(nn.Module):
 
     @torch.no_grad()
     def generate(self, text_tokens, seg_tokens, temperature=1.0, top_k=None, cond_scale=None, generator=None, img_tokens=None,
-                 return_logits=False, *, graph=False, kv_splits=None):
+                 return_logits=False, *, graph=False, kv_splits=None, top_p=None):
         """Autoregressive sampling of the ``image_length`` image tokens given text + segmentation tokens, KV-cached: one prefill
         over the prompt (the training attention kernel), then one ``mas_attn_decode`` pass per layer and token.
         ``temperature`` 0 -> greedy; ``top_k`` keeps the k most likely tokens; ``cond_scale`` s -> classifier-free guidance
@@ -414,12 +414,25 @@ class MakeAScene(nn.Module):
         guidance; the measured rule of DESIGN 2.6).
         None or 1: the one-work-group kernels, the bits of every earlier release.  n > 1 changes the summation order, so logits move
         within the kernels' tolerance and a near-tie may sample another token; at equal ``kv_splits`` the eager and the graph path
-        still agree bit for bit.  The prefill is not affected.  Integers > 1 need a head width with a decode kernel (16 / 32 / 64 / 128)."""
+        still agree bit for bit.  The prefill is not affected.  Integers > 1 need a head width with a decode kernel (16 / 32 / 64 / 128).
+        ``top_p``: nucleus sampling, 0 < top_p <= 1 (anything else raises ValueError; None and 1.0 are off: the code path and the bits
+        of a call without it).  After ``top_k``, with q the softmax of the logits / temperature over the entries top_k kept, an entry
+        stays iff the q-mass of the strictly larger values is <= top_p: the ruDALL-E / HF rule (drop the sorted entries whose inclusive
+        cumulative probability exceeds top_p, shifted by one so that the first one over the line stays) stated on values, so that the
+        maximum and every entry tied with the threshold value stay.  The token is drawn from the softmax over what is left
+        (``graph=True``: on the device, ``mas_sample_tokens_topp``; the value is device state, changing it does not recapture).
+        Ignored, like ``top_k``, by greedy and teacher-forced calls."""
+        if top_p is not None:
+            top_p = float(top_p)
+            if not 0.0 < top_p <= 1.0:                                  # NaN fails both comparisons
+                raise ValueError(f"generate: top_p {top_p} outside (0, 1]")
+            if top_p == 1.0:
+                top_p = None
         n_split = self._resolve_kv_splits(kv_splits, text_tokens.shape[0] * (2 if cond_scale is not None else 1))
         if graph:
             from .decode_graph import generate_graph
             out = generate_graph(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits,
-                                 kv_splits=n_split)
+                                 kv_splits=n_split, top_p=top_p)
             if out is not None:
                 return out
         attns = [layer.attn for layer in self.transformer.layers]
@@ -427,7 +440,8 @@ class MakeAScene(nn.Module):
         for a in attns:
             a.decode_kv_splits = n_split
         try:
-            return self._generate_eager(text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits)
+            return self._generate_eager(text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits,
+                                        top_p)
         finally:
             for a, old in zip(attns, saved):
                 if old is None:
@@ -448,7 +462,7 @@ class MakeAScene(nn.Module):
             return decode.resolve_kv_splits("auto", rows, heads, torch.cuda.get_device_properties(dev).multi_processor_count)
         return decode.resolve_kv_splits(kv_splits, rows, heads, 1)
 
-    def _generate_eager(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits):
+    def _generate_eager(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, top_p=None):
         """the token loop of ``generate(graph=False)``"""
         b = text_tokens.shape[0]
         guided = cond_scale is not None
@@ -480,6 +494,13 @@ class MakeAScene(nn.Module):
                 if top_k is not None:
                     kth = torch.topk(lg, int(top_k), dim=-1).values[:, -1:]
                     lg = lg.masked_fill(lg < kth, float("-inf"))
+                if top_p is not None:
+                    # t* = the last sorted value whose exclusive cumulative mass is <= top_p (the first one always is); ties at it stay
+                    srt = torch.sort(lg, dim=-1, descending=True).values
+                    q = torch.softmax(srt, dim=-1)
+                    ok = (q.cumsum(dim=-1) - q) <= top_p
+                    last = torch.where(ok, torch.arange(lg.shape[-1], device=lg.device), 0).amax(dim=-1, keepdim=True)
+                    lg = lg.masked_fill(lg < srt.gather(-1, last), float("-inf"))
                 tok = torch.multinomial(torch.softmax(lg, dim=-1), 1, generator=generator)[:, 0]
             tokens[:, i] = tok
             if i + 1 == self.image_length:

@@ -7,11 +7,16 @@ Temperature 1, top_k 256.  One JSON line.
     python tools/sample_bench.py [--batch 1 8] [--runs 2] [--skip-eager] [--kv-splits 2 4 8 16 auto]
     python tools/sample_bench.py --profile [--kv-splits 8]   # one graph-path call per split count after a warm one: run it under
                                                              # rocprofv3 --kernel-trace --stats
+    python tools/sample_bench.py --skip-eager --kv-splits 8 --top-p 0.9   # beside every graph column the same call with top_p
 
 ``--kv-splits``: beside the unsplit decode attention, the graph path with ``generate(kv_splits=n)`` for every n given (integers or
 "auto"): ``graph_ms_per_token_kv<n>`` columns, measured in the same process, every run alternating over the columns.  With
 ``--profile`` the unsplit call and one call per n run back to back, so one trace holds ``attn_decode_dev_kernel`` beside
 ``attn_decode_split_partial_kernel`` / ``attn_decode_split_combine_kernel`` with 24 * 1023 calls each.
+
+``--top-p P``: ``generate(top_p=P)`` next to every graph-path column (``..._topp`` keys), alternating with it in the same runs; with
+``--profile`` every call is followed by its top_p twin, so the trace's ``sample_kernel`` rows hold both (the per-call wall times tell
+them apart; the kernel statistics of a run with and one without ``--top-p`` give the sampler's own times).
 
 ms per token = wall time of a whole call (prefill, first token and the 1023 replays, synchronised) / 1024; capture = first graph call
 minus a steady one (warm-up step, capture, graph instantiation)."""
@@ -62,6 +67,7 @@ def main():
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--kv-splits", nargs="+", default=[], type=lambda v: v if v == "auto" else int(v),
                     help="also time generate(graph=True, kv_splits=n) for every n given (integers or 'auto')")
+    ap.add_argument("--top-p", type=float, default=None, help="also time every graph-path column with generate(top_p=P)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = build(dev)
@@ -72,9 +78,10 @@ def main():
         res = {"B": 1, "cond_scale": 3.0}
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
             for n in [None] + a.kv_splits:
-                m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, **kw)
-                dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, **kw))
-                res["profile_call_s" if n is None else f"profile_call_s_kv{n}"] = round(dt, 4)
+                for tp in [None] + ([a.top_p] if a.top_p is not None else []):
+                    m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, top_p=tp, **kw)
+                    dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, top_p=tp, **kw))
+                    res[("profile_call_s" if n is None else f"profile_call_s_kv{n}") + ("" if tp is None else "_topp")] = round(dt, 4)
         print(json.dumps(res))
         return
     rows = []
@@ -87,27 +94,29 @@ def main():
                 e = None if a.skip_eager else min(timed(lambda: m.generate(text, seg, cond_scale=cs, **kw))[0] for _ in range(max(1, a.runs - 1)))
             r = {"B": b, "cond_scale": cs, "graph_ms_per_token": round(1e3 * g / L, 4), "graph_images_per_min": round(60 * b / g, 2),
                  "capture_s": round(first - g, 3)}
-            if a.kv_splits:
+            if a.kv_splits or a.top_p is not None:
                 # every column twice (more with --runs), alternating over the columns: the spread of the repeats is the noise to beat
-                cols = [None] + a.kv_splits
+                cols = [(n, tp) for n in [None] + a.kv_splits for tp in [None] + ([a.top_p] if a.top_p is not None else [])]
                 with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-                    for n in a.kv_splits:
-                        m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, **kw)          # capture
-                    times = {n: [] for n in cols}
+                    for n, tp in cols[1:]:
+                        m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, top_p=tp, **kw)          # capture
+                    times = {c: [] for c in cols}
                     for _ in range(max(2, a.runs)):
-                        for n in cols:
-                            times[n].append(timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, **kw))[0])
-                for n in cols:
-                    tag = "none" if n is None else str(n)
-                    r[f"graph_ms_per_token_kv{tag}"] = round(1e3 * min(times[n]) / L, 4)
-                    r[f"spread_ms_per_token_kv{tag}"] = round(1e3 * (max(times[n]) - min(times[n])) / L, 4)
-                r["kv_auto_resolves_to"] = m._resolve_kv_splits("auto", 2 * b if cs is not None else b)
+                        for n, tp in cols:
+                            times[(n, tp)].append(timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, top_p=tp,
+                                                                           **kw))[0])
+                for n, tp in cols:
+                    tag = ("none" if n is None else str(n)) + ("" if tp is None else "_topp")
+                    r[f"graph_ms_per_token_kv{tag}"] = round(1e3 * min(times[(n, tp)]) / L, 4)
+                    r[f"spread_ms_per_token_kv{tag}"] = round(1e3 * (max(times[(n, tp)]) - min(times[(n, tp)])) / L, 4)
+                if a.kv_splits:
+                    r["kv_auto_resolves_to"] = m._resolve_kv_splits("auto", 2 * b if cs is not None else b)
             if e is not None:
                 r.update(eager_ms_per_token=round(1e3 * e / L, 4), eager_images_per_min=round(60 * b / e, 2), speedup=round(e / g, 2))
             rows.append(r)
             print(json.dumps(r), file=sys.stderr, flush=True)
             m.release_decode_graphs()
-    print(json.dumps({"metric": "MakeAScene.generate, config-4 width, bf16 autocast", "tokens_per_image": L, "top_k": kw["top_k"],
+    print(json.dumps({"metric": "MakeAScene.generate, config-4 width, bf16 autocast", "tokens_per_image": L, "top_k": kw["top_k"], "top_p": a.top_p,
                       "device": torch.cuda.get_device_name(0), "rows": rows}))
 
 

@@ -336,6 +336,11 @@ int mas_attn_decode(const void* q, const void* k_cache, const void* v_cache, voi
  *   !(top_p < 1) (1, more, NaN) is off: the instructions and tokens of mas_sample_tokens.  top_p <= 0 keeps the maximum and its ties.
  *   Modes 0 and 2 ignore it.  t* comes from a radix select over fixed-point masses floor(exp(lg_j - max) * 2^32) summed as 64-bit
  *   integers: repeatable bit for bit, exact line for V < 2^21; an entry 2^-32 below the maximum weighs nothing (it can still be kept).
+ * Image prompt: mas_sample_tokens_prompt is mas_sample_tokens_topp (params = three device floats, top_p = 1 for "off") with a per-row
+ *   mask, keep uint8, row r at keep + r*ld_keep (ld_keep >= L): after the logits write-out the work-group of a row with
+ *   keep[r*ld_keep + k] != 0 stores tokens[r, k] = forced[r*ld_forced + k] and returns; every other row goes on as in mode 0 / 1.  The
+ *   same kernel: a free row's token is the one mas_sample_tokens_topp gives (the Philox counter holds the row, the step and the
+ *   vocabulary slot, nothing about the other rows or steps).  Modes 0 and 1 only, keep and forced required: anything else is MAS_EINVAL.
  * mas_decode_advance: counters[0 .. n-1] += 1 (one thread, n <= 8), ordered after the step's kernels by the stream.                  */
 int mas_attn_decode_dev(const void* q, const void* k_new, const void* v_new, long long new_bs, void* k_cache, void* v_cache, int ld_c,
                         long long c_bs, int capacity, void* o, long long o_bs, int dtype, int B, int H, int hd, const int32_t* past,
@@ -349,6 +354,10 @@ int mas_sample_tokens_topp(const float* logits, long long ld_logits, long long u
                            const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
                            long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
                            void* stream);
+int mas_sample_tokens_prompt(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode, int top_k,
+                             const float* params, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
+                             long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
+                             const uint8_t* keep, long long ld_keep, void* stream);
 int mas_decode_advance(int32_t* counters, int n, void* stream);
 
 /* ---- decode attention split over keys (low batch * heads: make-a-scene_amd/csrc/attn_decode_split.hip).  mas_attn_decode /

@@ -4,7 +4,8 @@
 //   attn_decode_dev_kernel  mas_attn_decode with nq = 1 whose cache length is a device int32 and which appends the new key / value
 //                           row itself;
 //   decode_embed_kernel     image-token embedding + row / column position embedding of the token sampled at the previous step;
-//   sample_kernel           guidance mix, logits write-out, teacher forcing / greedy argmax / top-k + top-p + Gumbel-max draw (Philox);
+//   sample_kernel           guidance mix, logits write-out, teacher forcing / greedy argmax / top-k + top-p + Gumbel-max draw (Philox),
+//                           with an image prompt (mas_sample_tokens_prompt) the given token at the positions a per-row mask keeps;
 //   advance_kernel          one thread: the step counters + 1, after every other kernel of the step has read them (stream order).
 #include "attn_decode_core.h"
 #include "mas_philox.h"
@@ -108,6 +109,7 @@ struct SampleParams {
     const long long* seed;                           // {seed, offset}
     const int* step;
     const long long* forced; long long ld_f;
+    const unsigned char* keep; long long ld_k;       // image prompt (mas_sample_tokens_prompt): row r keeps forced[r, k] where keep[r, k] != 0
     long long* tokens; long long ld_t;
     float* lout; long long ld_lo;                    // row r, step k at lout + r*ld_lo + k*V
 };
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(SNT) void sample_kernel(SampleParams p) {
         float* dst = p.lout + (size_t)r * p.ld_lo + (size_t)k * V;
         for (int j = tid; j < V; j += SNT) dst[j] = mixed(j);
     }
-    if (p.mode == MODE_FORCED) {
+    if (p.mode == MODE_FORCED || (p.keep && p.keep[(size_t)r * p.ld_k + k])) {    // uniform over the work-group: one row, one step
         if (tid == 0) p.tokens[(size_t)r * p.ld_t + k] = p.forced[(size_t)r * p.ld_f + k];
         return;
     }
@@ -350,8 +352,8 @@ extern "C" int mas_decode_embed(const int64_t* tokens, long long ld_tok, const i
 namespace {
 int sample_tokens_launch(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode, int top_k,
                          const float* params, int has_p, const int64_t* seed, const int32_t* step, int L, const int64_t* forced,
-                         long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out, long long ld_logits_out,
-                         void* stream) {
+                         long long ld_forced, const uint8_t* keep, long long ld_keep, int64_t* tokens, long long ld_tokens,
+                         float* logits_out, long long ld_logits_out, void* stream) {
     if (!logits || !params || !step || !tokens) MAS_FAIL(MAS_EINVAL, "sample_tokens: null argument");
     if (B <= 0 || V <= 0 || L <= 0 || ld_logits < 0 || ld_tokens < L || (logits_out && ld_logits_out < (long long)L * V))
         MAS_FAIL(MAS_EINVAL, "sample_tokens: bad shape B=%d V=%d L=%d", B, V, L);
@@ -363,6 +365,7 @@ int sample_tokens_launch(const float* logits, long long ld_logits, long long unc
     p.B = B; p.V = V; p.guided = guided != 0; p.mode = mode; p.top_k = top_k; p.L = L;
     p.params = params; p.has_p = has_p; p.seed = reinterpret_cast<const long long*>(seed); p.step = step;
     p.forced = reinterpret_cast<const long long*>(forced); p.ld_f = ld_forced;
+    p.keep = keep; p.ld_k = ld_keep;
     p.tokens = reinterpret_cast<long long*>(tokens); p.ld_t = ld_tokens;
     p.lout = logits_out; p.ld_lo = ld_logits_out;
     hipLaunchKernelGGL(sample_kernel, dim3((unsigned)B), dim3(SNT), 0, reinterpret_cast<hipStream_t>(stream), p);
@@ -377,7 +380,7 @@ extern "C" int mas_sample_tokens(const float* logits, long long ld_logits, long 
                                  void* stream) {
     MAS_ENTER();
     return sample_tokens_launch(logits, ld_logits, uncond_off, B, V, guided, mode, top_k, params, 0, seed, step, L, forced, ld_forced,
-                                tokens, ld_tokens, logits_out, ld_logits_out, stream);
+                                nullptr, 0, tokens, ld_tokens, logits_out, ld_logits_out, stream);
 }
 
 extern "C" int mas_sample_tokens_topp(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode,
@@ -386,7 +389,19 @@ extern "C" int mas_sample_tokens_topp(const float* logits, long long ld_logits, 
                                       long long ld_logits_out, void* stream) {
     MAS_ENTER();
     return sample_tokens_launch(logits, ld_logits, uncond_off, B, V, guided, mode, top_k, params, 1, seed, step, L, forced, ld_forced,
-                                tokens, ld_tokens, logits_out, ld_logits_out, stream);
+                                nullptr, 0, tokens, ld_tokens, logits_out, ld_logits_out, stream);
+}
+
+extern "C" int mas_sample_tokens_prompt(const float* logits, long long ld_logits, long long uncond_off, int B, int V, int guided, int mode,
+                                        int top_k, const float* params, const int64_t* seed, const int32_t* step, int L,
+                                        const int64_t* forced, long long ld_forced, int64_t* tokens, long long ld_tokens, float* logits_out,
+                                        long long ld_logits_out, const uint8_t* keep, long long ld_keep, void* stream) {
+    MAS_ENTER();
+    if (mode == MODE_FORCED) MAS_FAIL(MAS_EINVAL, "sample_tokens_prompt: mode 2 forces every position, it takes no mask");
+    if (!keep || !forced || ld_keep < L || ld_forced < L)
+        MAS_FAIL(MAS_EINVAL, "sample_tokens_prompt: needs the mask and the kept tokens, rows of at least L=%d elements", L);
+    return sample_tokens_launch(logits, ld_logits, uncond_off, B, V, guided, mode, top_k, params, 1, seed, step, L, forced, ld_forced,
+                                keep, ld_keep, tokens, ld_tokens, logits_out, ld_logits_out, stream);
 }
 
 extern "C" int mas_decode_advance(int32_t* counters, int n, void* stream) {

@@ -147,6 +147,8 @@ _SIGNATURES = {
                                C.c_longlong, _p]),
     "mas_sample_tokens_topp": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong,
                                     _p, C.c_longlong, _p]),
+    "mas_sample_tokens_prompt": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong,
+                                      _p, C.c_longlong, _p, C.c_longlong, _p]),
     "mas_decode_advance": (_i, [_p, _i, _p]),
     "mas_attn_decode_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong,
                                    C.c_longlong, _f, _i, _p, _sz, _p]),

@@ -108,13 +108,21 @@ def decode_embed(tokens: torch.Tensor, step: torch.Tensor, img_emb: torch.Tensor
 
 def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor, params: torch.Tensor, mode: int, *, top_k: int = 0,
                   guided: bool = False, seed: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None,
-                  logits_out: Optional[torch.Tensor] = None, rows: Optional[int] = None, top_p: bool = False) -> torch.Tensor:
+                  logits_out: Optional[torch.Tensor] = None, rows: Optional[int] = None, top_p: bool = False,
+                  keep: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One token per row into tokens[r, *step] (``mas_sample_tokens``; with ``top_p`` ``mas_sample_tokens_topp``, whose params hold a
     third float, the nucleus mass: include/mas_hip.h "Top-p" -- the value lives on the device like the temperature, the flag only selects
     the entry).  logits fp32 [R, V] with R = 2B under guidance (conditional rows
     first, as ``generate`` stacks them) or B, or a single [1, V] / [2, V] row shared by ``rows`` output rows (row stride 0: the statistics
     tests).  params fp32 {temperature, cond_scale}; seed int64 {seed, offset}; forced int64 [B, L] (teacher forcing); logits_out fp32
-    [B, L, V] receives the mixed row."""
+    [B, L, V] receives the mixed row.  ``keep`` uint8 [B, L] (image prompt, ``mas_sample_tokens_prompt``): row r at step k gets
+    ``forced[r, k]`` where ``keep[r, k]`` is non-zero and the GREEDY / SAMPLE token otherwise; it needs ``forced`` and the three-float
+    params (top_p = 1.0: off), and is an error with FORCED, which keeps every position already."""
+    if keep is not None:
+        if mode not in (GREEDY, SAMPLE):
+            raise RuntimeError("sample_tokens: keep goes with GREEDY or SAMPLE (FORCED keeps every position)")
+        if forced is None:
+            raise RuntimeError("sample_tokens: keep needs the forced tokens it keeps")
     _require_cuda(logits, "sample_tokens")
     if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
         raise RuntimeError("sample_tokens: fp32 logits [R, V] with contiguous rows")
@@ -122,7 +130,7 @@ def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor
     v = logits.shape[1]
     shared = rows is not None
     if tokens.dtype != torch.int64 or tokens.stride(1) != 1 or step.dtype != torch.int32 or params.dtype != torch.float32 \
-            or params.numel() < (3 if top_p else 2) or not params.is_contiguous():
+            or params.numel() < (3 if top_p or keep is not None else 2) or not params.is_contiguous():
         raise RuntimeError("sample_tokens: tokens int64 [B, L], step int32, params fp32 {temperature, cond_scale} (and top_p with top_p=True)")
     if shared:
         if rows != nb or logits.shape[0] != (2 if guided else 1):
@@ -134,10 +142,19 @@ def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, step: torch.Tensor
         ld, uoff = logits.stride(0), nb * logits.stride(0)
     if mode == SAMPLE and (seed is None or seed.dtype != torch.int64 or seed.numel() < 2):
         raise RuntimeError("sample_tokens: sampling needs the int64 {seed, offset} tensor")
-    if mode == FORCED and (forced is None or forced.dtype != torch.int64 or forced.shape != tokens.shape or forced.stride(1) != 1):
+    if (mode == FORCED or keep is not None) and (forced is None or forced.dtype != torch.int64 or forced.shape != tokens.shape
+                                                 or forced.stride(1) != 1 or forced.device != logits.device):
         raise RuntimeError("sample_tokens: teacher forcing needs int64 tokens shaped like the output")
+    if keep is not None and (keep.dtype != torch.uint8 or keep.shape != tokens.shape or keep.stride(1) != 1 or keep.device != logits.device):
+        raise RuntimeError("sample_tokens: keep is a device uint8 mask shaped like the output")
     if logits_out is not None and (logits_out.dtype != torch.float32 or logits_out.shape != (nb, length, v) or not logits_out.is_contiguous()):
         raise RuntimeError("sample_tokens: logits_out fp32 contiguous [B, L, V]")
+    if keep is not None:
+        check(lib().mas_sample_tokens_prompt(_ptr(logits), ld, uoff, nb, v, int(guided), int(mode), int(top_k or 0), _ptr(params), _ptr(seed),
+                                             _ptr(step), length, _ptr(forced), forced.stride(0), _ptr(tokens), tokens.stride(0),
+                                             _ptr(logits_out), logits_out.stride(0) if logits_out is not None else 0, _ptr(keep),
+                                             keep.stride(0), _stream()), "sample_tokens_prompt")
+        return tokens
     entry = lib().mas_sample_tokens_topp if top_p else lib().mas_sample_tokens
     check(entry(_ptr(logits), ld, uoff, nb, v, int(guided), int(mode), int(top_k or 0), _ptr(params), _ptr(seed), _ptr(step), length,
                 _ptr(forced), forced.stride(0) if forced is not None else 0, _ptr(tokens), tokens.stride(0), _ptr(logits_out),

@@ -1,1 +1,2 @@
 from .vqvae import VQBASE
+from .image_prompt import border_keep_mask, common_prefix

@@ -17,6 +17,11 @@ in device buffers: one capture serves every token and every call with the same k
 is on -- not its value --, return_logits, compute dtype, autocast state, device, decode-attention split count).  The graph reads the parameters and their bf16 shadows in place; an
 entry whose pointers moved (``load_state_dict`` into new storage, ``.to()``, ``invalidate_weight_cache()``) is recaptured.
 
+An image prompt (``generate(img_tokens=..., keep=...)``) is one more key: the step then calls ``mas_sample_tokens_prompt``, which reads the
+mask and the kept tokens from the entry's static buffers (``keep`` uint8 [B, L], ``forced``), so other masks, other tokens and another
+common prefix m never recapture.  With m > 0 the prefill has already run the m leading kept tokens: the caches are copied over plen + m
+rows, the counters start at step m, and the host replays L - 1 - m times.
+
 Tokens are drawn by Gumbel-max from Philox4x32-10 (include/mas_hip.h, "Sampling"): reproducible under ``torch.manual_seed`` or a seeded
 ``generator``, but not the tokens ``torch.multinomial`` would draw (the eager path's)."""
 import warnings
@@ -69,7 +74,7 @@ def _pointer_signature(model, bf16_autocast):
 class _Entry:
     """static buffers and the captured graph of one key"""
 
-    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1, top_p=False):
+    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1, top_p=False, prompted=False):
         dev = model.device
         d = model.transformer.layers[0].attn.hidden_dim
         heads = model.transformer.layers[0].attn.num_attn_heads
@@ -85,7 +90,8 @@ class _Entry:
         self.vc = [torch.empty_like(t) for t in self.kc]
         self.x = torch.empty((rows, 1, d), dtype=torch.float32, device=dev)
         self.tokens = torch.zeros((b, length), dtype=torch.long, device=dev)
-        self.forced = torch.zeros((b, length), dtype=torch.long, device=dev) if mode == decode.FORCED else None
+        self.forced = torch.zeros((b, length), dtype=torch.long, device=dev) if mode == decode.FORCED or prompted else None
+        self.keep = torch.zeros((b, length), dtype=torch.uint8, device=dev) if prompted else None    # image prompt: the kept positions
         self.logits_out = torch.empty((b, length, v), dtype=torch.float32, device=dev) if return_logits else None
         self.top_p = top_p                                                 # which sampler entry the step calls; the value is params[2]
         self.params = torch.ones(3, dtype=torch.float32, device=dev)       # {temperature, cond_scale, top_p}
@@ -101,7 +107,7 @@ class _Entry:
 
     def sample(self, logits):
         decode.sample_tokens(logits, self.tokens, self.ctr[0:1], self.params, self.mode, top_k=self.top_k, guided=self.guided,
-                             seed=self.seed, forced=self.forced, logits_out=self.logits_out, top_p=self.top_p)
+                             seed=self.seed, forced=self.forced, logits_out=self.logits_out, top_p=self.top_p, keep=self.keep)
         decode.advance(self.ctr)
 
 
@@ -128,14 +134,15 @@ def _autocast_without_cache():
     return torch.autocast("cuda", enabled=False, cache_enabled=False)
 
 
-def _capture(model, e):
-    """one eager warm-up step on a side stream (settles the GEMM choices and any allocation), rewind, capture the step on that stream"""
+def _capture(model, e, k=1):
+    """one eager warm-up step on a side stream (settles the GEMM choices and any allocation), rewind to the step k it ran (1, or m + 1
+    behind a prefilled prefix of m image tokens), capture the step on that stream"""
     main = torch.cuda.current_stream()
     side = torch.cuda.Stream(device=main.device)
     side.wait_stream(main)
     with torch.cuda.stream(side), _autocast_without_cache():
         _step(model, e)
-        e.rewind(1)
+        e.rewind(k)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=side), _autocast_without_cache():
         _step(model, e)
@@ -145,7 +152,7 @@ def _capture(model, e):
 
 
 def _replay(e, n):
-    """tokens 1 .. n: the replay calls and nothing else on the host"""
+    """the next n tokens (1 .. n, or m + 1 .. m + n behind a prefix): the replay calls and nothing else on the host"""
     for _ in range(n):
         e.graph.replay()
 
@@ -160,10 +167,12 @@ def _draw_seed(generator, device):
 
 
 def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, kv_splits=1,
-                   top_p=None):
+                   top_p=None, keep=None, prefix=0):
     """``MakeAScene.generate(..., graph=True)``; returns None outside the envelope (the caller then runs the eager path).  ``kv_splits``:
     the resolved split count of the decode attention (1: ``mas_attn_decode_dev``; n > 1: ``mas_attn_decode_split_dev``), part of the key.
-    ``top_p``: None (off: ``mas_sample_tokens``) or the validated nucleus mass in (0, 1); only "on" is part of the key"""
+    ``top_p``: None (off: ``mas_sample_tokens``) or the validated nucleus mass in (0, 1); only "on" is part of the key.
+    ``keep`` / ``prefix``: the validated image-prompt mask (None: none) and the number m of leading kept positions the prefill takes;
+    only "prompted" is part of the key"""
     reason = _envelope_reason(model)
     if reason is not None:
         warned = model.__dict__.setdefault("_decode_graph_warned", set())
@@ -174,13 +183,16 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     b = text_tokens.shape[0]
     guided = cond_scale is not None
     rows = 2 * b if guided else b
-    mode = decode.FORCED if img_tokens is not None else (decode.GREEDY if temperature == 0 else decode.SAMPLE)
+    prompted = keep is not None
+    mode = decode.FORCED if (img_tokens is not None and not prompted) else (decode.GREEDY if temperature == 0 else decode.SAMPLE)
+    m = int(prefix) if prompted else 0
     top_k = int(top_k) if (mode == decode.SAMPLE and top_k is not None) else 0
     p_on = mode == decode.SAMPLE and top_p is not None
     autocast = torch.is_autocast_enabled()
     ac_dtype = torch.get_autocast_gpu_dtype() if autocast else None
     dev = model.device
-    key = (b, guided, mode, top_k, p_on, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev), int(kv_splits))
+    # the split count stays the key's last element: "prompted" goes in front of it
+    key = (b, guided, mode, top_k, p_on, prompted, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev), int(kv_splits))
     sig = _pointer_signature(model, autocast and ac_dtype == torch.bfloat16)
     graphs = model.__dict__.setdefault("_decode_graphs", {})
     params = _param_pointers(model)
@@ -191,7 +203,7 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
         del graphs[key]
         e = None
 
-    # ---- prefill: the eager path's (the training attention kernel over the prompt) ----
+    # ---- prefill: the eager path's (the training attention kernel over the prompt and, behind it, the m leading kept tokens) ----
     if guided:
         text_tokens = torch.cat([text_tokens, torch.zeros_like(text_tokens)], dim=0)
         seg_tokens = torch.cat([seg_tokens, seg_tokens], dim=0)
@@ -199,33 +211,43 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     bb, plen, d = prompt.shape
     for layer in model.transformer.layers:
         layer.attn.cache_capacity = model.total_length
+    if m:
+        prompt = torch.cat([prompt, model._prefix_embeddings(img_tokens, m, guided)], dim=1)
     hidden, cache = model.transformer(prompt, None, cache={}, use_cache=True)
-    logits0 = model.to_logits(hidden[:, -1:, :])[:, 0, :].float()
+    logits0 = model.to_logits(hidden[:, -1:, :])[:, 0, :].float()                  # of image position m
+    prefix_logits = model._prefix_logits(hidden, plen, m, b, cond_scale) if m and return_logits else None
     kv = [(cache[i][0], cache[i][1]) for i in range(len(model.transformer.layers))]
     if e is None:
-        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits), p_on)
+        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits), p_on, prompted)
         graphs[key] = e
 
     # ---- per-call device state, then the static caches ----
-    e.rewind(0)
+    e.rewind(m)
     e.params[0].fill_(float(temperature) if mode == decode.SAMPLE else 1.0)
     e.params[1].fill_(float(cond_scale) if guided else 0.0)
     e.params[2].fill_(float(top_p) if p_on else 1.0)
     if mode == decode.SAMPLE:
         e.seed.copy_(_draw_seed(generator, dev))
-    if mode == decode.FORCED:
+    if mode == decode.FORCED or prompted:
         e.forced.copy_(img_tokens)
+    if prompted:
+        e.keep.copy_(keep)
+        if m:
+            e.tokens[:, :m].copy_(e.forced[:, :m])
+            if prefix_logits is not None:
+                e.logits_out[:, :m].copy_(prefix_logits)
+    rows_filled = plen + m
     from .transformer import _kv_backing
     for li, (k, v) in enumerate(kv):
-        e.kc[li][:, :plen].copy_(_kv_backing(k, bb, d)[:, :plen])
-        e.vc[li][:, :plen].copy_(_kv_backing(v, bb, d)[:, :plen])
-    del cache, kv, hidden
+        e.kc[li][:, :rows_filled].copy_(_kv_backing(k, bb, d)[:, :rows_filled])
+        e.vc[li][:, :rows_filled].copy_(_kv_backing(v, bb, d)[:, :rows_filled])
+    del cache, kv, hidden, prefix_logits
 
-    # ---- token 0 from the prefill (eager, the same sampler kernel), tokens 1 .. L-1 by replay ----
+    # ---- token m (0 without a prefix) from the prefill (eager, the same sampler kernel), tokens m+1 .. L-1 by replay ----
     e.sample(logits0)
-    if model.image_length > 1:
+    if model.image_length - 1 - m > 0:
         if e.graph is None:
-            _capture(model, e)
-        _replay(e, model.image_length - 1)
+            _capture(model, e, m + 1)
+        _replay(e, model.image_length - 1 - m)
     tokens = e.tokens.clone()
     return (tokens, e.logits_out.clone()) if return_logits else tokens

@@ -395,7 +395,7 @@ class MakeAScene(nn.Module):
 
     @torch.no_grad()
     def generate(self, text_tokens, seg_tokens, temperature=1.0, top_k=None, cond_scale=None, generator=None, img_tokens=None,
-                 return_logits=False, *, graph=False, kv_splits=None, top_p=None):
+                 return_logits=False, *, graph=False, kv_splits=None, top_p=None, keep=None, prefill_prefix=True):
         """Autoregressive sampling of the ``image_length`` image tokens given text + segmentation tokens, KV-cached: one prefill
         over the prompt (the training attention kernel), then one ``mas_attn_decode`` pass per layer and token.
         ``temperature`` 0 -> greedy; ``top_k`` keeps the k most likely tokens; ``cond_scale`` s -> classifier-free guidance
@@ -421,18 +421,46 @@ class MakeAScene(nn.Module):
         cumulative probability exceeds top_p, shifted by one so that the first one over the line stays) stated on values, so that the
         maximum and every entry tied with the threshold value stay.  The token is drawn from the softmax over what is left
         (``graph=True``: on the device, ``mas_sample_tokens_topp``; the value is device state, changing it does not recapture).
-        Ignored, like ``top_k``, by greedy and teacher-forced calls."""
+        Ignored, like ``top_k``, by greedy and teacher-forced calls.
+        ``keep``: an image prompt -- bool [B, image_length] on any device, with ``img_tokens`` (for an existing image:
+        ``VQBASE.encode_to_indices``; ``models.border_keep_mask`` builds the mask of ruDALL-E's up / down / left / right borders).
+        Position i of row b returns ``img_tokens[b, i]`` where ``keep[b, i]`` is true and the token of the configured rule (greedy, or
+        temperature / ``top_k`` / ``top_p``, with or without guidance) everywhere else; the returned token is the one fed to the next
+        step, under guidance to the conditional and the unconditional row alike.  ``return_logits`` holds the logits of every position,
+        kept ones included.  None: the code path and the bits of a call without it (``img_tokens`` alone forces every position).  A mask
+        that is not a bool tensor of that shape, or has no ``img_tokens`` [B, image_length] beside it, raises ValueError before the
+        device is touched.  ``graph=True``: the mask and the tokens are device state of one more captured configuration
+        (``mas_sample_tokens_prompt``); changing them never recaptures, and a free position draws what the same seed draws there without
+        the mask, given the same logits.
+        ``prefill_prefix`` (with ``keep`` only): the m leading positions that every row keeps (``models.common_prefix``: the minimum over
+        the rows, at most image_length - 1) are embedded behind the prompt and go through the ONE prefill, whose hidden rows give their
+        logits; the token loop starts at position m, so keeping the top half of the image halves the call.  Finding m reads the mask on
+        the host: one synchronisation before the loop when ``keep`` lives on the GPU, none when it is a CPU tensor; the replay loop of
+        ``graph=True`` stays free of host calls.  False: every position takes a decode step -- the bits of the step-by-step path (the
+        prefill kernel sums in another order, so with True the logits move within the cached-against-uncached tolerance)."""
         if top_p is not None:
             top_p = float(top_p)
             if not 0.0 < top_p <= 1.0:                                  # NaN fails both comparisons
                 raise ValueError(f"generate: top_p {top_p} outside (0, 1]")
             if top_p == 1.0:
                 top_p = None
+        m = 0
+        if keep is not None:
+            want = (text_tokens.shape[0], self.image_length)
+            if img_tokens is None:
+                raise ValueError("generate: keep says which of img_tokens stay; it needs img_tokens")
+            if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != want:
+                raise ValueError(f"generate: keep must be a bool tensor of shape {want}")
+            if not isinstance(img_tokens, torch.Tensor) or tuple(img_tokens.shape) != want:
+                raise ValueError(f"generate: with keep, img_tokens must be a tensor of shape {want}")
+            if prefill_prefix:
+                from .image_prompt import common_prefix
+                m = common_prefix(keep)
         n_split = self._resolve_kv_splits(kv_splits, text_tokens.shape[0] * (2 if cond_scale is not None else 1))
         if graph:
             from .decode_graph import generate_graph
             out = generate_graph(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits,
-                                 kv_splits=n_split, top_p=top_p)
+                                 kv_splits=n_split, top_p=top_p, keep=keep, prefix=m)
             if out is not None:
                 return out
         attns = [layer.attn for layer in self.transformer.layers]
@@ -441,7 +469,7 @@ class MakeAScene(nn.Module):
             a.decode_kv_splits = n_split
         try:
             return self._generate_eager(text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits,
-                                        top_p)
+                                        top_p, keep, m)
         finally:
             for a, old in zip(attns, saved):
                 if old is None:
@@ -462,8 +490,25 @@ class MakeAScene(nn.Module):
             return decode.resolve_kv_splits("auto", rows, heads, torch.cuda.get_device_properties(dev).multi_processor_count)
         return decode.resolve_kv_splits(kv_splits, rows, heads, 1)
 
-    def _generate_eager(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, top_p=None):
-        """the token loop of ``generate(graph=False)``"""
+    def _prefix_embeddings(self, img_tokens, m, guided):
+        """[rows, m, D]: the m leading image tokens at image positions 0 .. m-1, what the token loop would feed one row at a time"""
+        t_in = img_tokens[:, :m].to(self.device)
+        if guided:
+            t_in = torch.cat([t_in, t_in], dim=0)
+        return self.image_token_embedding(t_in) + self.get_image_pos_embeddings(t_in)
+
+    def _prefix_logits(self, hidden, plen, m, b, cond_scale):
+        """[B, m, V] fp32: the (guidance-mixed) logits of image positions 0 .. m-1 from the hidden rows plen-1 .. plen+m-2 of a prefill over
+        the prompt and the m leading kept tokens"""
+        logits = self.to_logits(hidden[:, plen - 1:plen + m - 1, :]).float()
+        if cond_scale is not None:
+            logits = logits[b:] + float(cond_scale) * (logits[:b] - logits[b:])
+        return logits
+
+    def _generate_eager(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, top_p=None,
+                        keep=None, prefix=0):
+        """the token loop of ``generate(graph=False)``; ``keep`` / ``prefix``: the image prompt's mask and how many leading positions go
+        through the prefill instead of the loop"""
         b = text_tokens.shape[0]
         guided = cond_scale is not None
         if guided:
@@ -476,16 +521,26 @@ class MakeAScene(nn.Module):
         buf = prompt.new_empty((bb, self.total_length, d))
         buf[:, :plen] = prompt
         cur = plen
+        if keep is not None:
+            keep = keep.to(prompt.device)
+            img_tokens = img_tokens.to(prompt.device)
+        if prefix:
+            buf[:, plen:plen + prefix] = self._prefix_embeddings(img_tokens, prefix, guided)
+            cur = plen + prefix
         hidden, cache = self.transformer(buf[:, :cur], None, cache={}, use_cache=True)
         tokens = torch.empty((b, self.image_length), dtype=torch.long, device=prompt.device)
         all_logits = [] if return_logits else None
-        for i in range(self.image_length):
+        if prefix:
+            tokens[:, :prefix] = img_tokens[:, :prefix]
+            if return_logits:
+                all_logits.extend(self._prefix_logits(hidden, plen, prefix, b, cond_scale).unbind(dim=1))
+        for i in range(prefix, self.image_length):
             logits = self.to_logits(hidden[:, -1:, :])[:, 0, :].float()
             if guided:
                 logits = logits[b:] + float(cond_scale) * (logits[:b] - logits[b:])
             if return_logits:
                 all_logits.append(logits)
-            if img_tokens is not None:
+            if img_tokens is not None and keep is None:
                 tok = img_tokens[:, i]
             elif temperature == 0:
                 tok = logits.argmax(dim=-1)
@@ -502,6 +557,8 @@ class MakeAScene(nn.Module):
                     last = torch.where(ok, torch.arange(lg.shape[-1], device=lg.device), 0).amax(dim=-1, keepdim=True)
                     lg = lg.masked_fill(lg < srt.gather(-1, last), float("-inf"))
                 tok = torch.multinomial(torch.softmax(lg, dim=-1), 1, generator=generator)[:, 0]
+            if keep is not None:                        # after the draw: what the generator consumes does not depend on the mask
+                tok = torch.where(keep[:, i], img_tokens[:, i], tok)
             tokens[:, i] = tok
             if i + 1 == self.image_length:
                 break

@@ -8,6 +8,7 @@ Temperature 1, top_k 256.  One JSON line.
     python tools/sample_bench.py --profile [--kv-splits 8]   # one graph-path call per split count after a warm one: run it under
                                                              # rocprofv3 --kernel-trace --stats
     python tools/sample_bench.py --skip-eager --kv-splits 8 --top-p 0.9   # beside every graph column the same call with top_p
+    python tools/sample_bench.py --skip-eager --kv-splits 8 --keep-rows 0 16   # image prompts: the top N token rows of a random image kept
 
 ``--kv-splits``: beside the unsplit decode attention, the graph path with ``generate(kv_splits=n)`` for every n given (integers or
 "auto"): ``graph_ms_per_token_kv<n>`` columns, measured in the same process, every run alternating over the columns.  With
@@ -17,6 +18,13 @@ Temperature 1, top_k 256.  One JSON line.
 ``--top-p P``: ``generate(top_p=P)`` next to every graph-path column (``..._topp`` keys), alternating with it in the same runs; with
 ``--profile`` every call is followed by its top_p twin, so the trace's ``sample_kernel`` rows hold both (the per-call wall times tell
 them apart; the kernel statistics of a run with and one without ``--top-p`` give the sampler's own times).
+
+``--keep-rows N ...``: ``generate(img_tokens=random image, keep=its top N token rows)`` next to every graph-path column, once with
+``prefill_prefix`` on (``..._keep<N>`` keys: the kept rows go through the prefill, 1023 - 32 N replays) and once off (``..._keep<N>_steps``:
+every position is a decode step), alternating with the unprompted call in the same runs.  N = 0 keeps nothing: the prompted sampler
+entry on the unprompted amount of work.  The mask is a CPU tensor (no synchronisation to find the prefix).  ms per token stays the
+call time / 1024 whatever is kept, so the columns compare as call times.  With ``--profile`` every call is followed by its prompted
+twins (``prefill_prefix`` off: 1023 more ``sample_kernel`` launches with the mask).
 
 ms per token = wall time of a whole call (prefill, first token and the 1023 replays, synchronised) / 1024; capture = first graph call
 minus a steady one (warm-up step, capture, graph instantiation)."""
@@ -68,20 +76,38 @@ def main():
     ap.add_argument("--kv-splits", nargs="+", default=[], type=lambda v: v if v == "auto" else int(v),
                     help="also time generate(graph=True, kv_splits=n) for every n given (integers or 'auto')")
     ap.add_argument("--top-p", type=float, default=None, help="also time every graph-path column with generate(top_p=P)")
+    ap.add_argument("--keep-rows", type=int, nargs="+", default=[],
+                    help="also time every graph-path column with the top N token rows of a random image kept, prefill_prefix on and off")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = build(dev)
     L = CFG["image_tokens_per_dim"] ** 2
     kw = dict(temperature=1.0, top_k=256)
+    n_dim = CFG["image_tokens_per_dim"]
+    if any(not 0 <= n <= n_dim for n in a.keep_rows):
+        ap.error(f"--keep-rows: 0 .. {n_dim}")
+
+    def prompt_kw(b, pk):
+        """generate's image-prompt arguments of a column: pk = None (unprompted) or (kept token rows, prefill_prefix)"""
+        if pk is None:
+            return {}
+        from models import border_keep_mask
+        img = torch.randint(0, CFG["image_vocab_size"], (b, L), generator=torch.Generator().manual_seed(100 + b)).to(dev)
+        return dict(img_tokens=img, keep=border_keep_mask(n_dim, up=pk[0])[None].repeat(b, 1), prefill_prefix=pk[1])
+
+    prompts = [None] + [(n, on) for n in a.keep_rows for on in (True, False)]
+    ptag = lambda pk: "" if pk is None else f"_keep{pk[0]}" + ("" if pk[1] else "_steps")
     if a.profile:
         text, seg = prompt(1, dev)
         res = {"B": 1, "cond_scale": 3.0}
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
             for n in [None] + a.kv_splits:
                 for tp in [None] + ([a.top_p] if a.top_p is not None else []):
-                    m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, top_p=tp, **kw)
-                    dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, top_p=tp, **kw))
-                    res[("profile_call_s" if n is None else f"profile_call_s_kv{n}") + ("" if tp is None else "_topp")] = round(dt, 4)
+                    for pk in prompts:
+                        pkw = prompt_kw(1, pk)
+                        m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, top_p=tp, **kw, **pkw)
+                        dt, _ = timed(lambda: m.generate(text, seg, cond_scale=3.0, graph=True, kv_splits=n, top_p=tp, **kw, **pkw))
+                        res[("profile_call_s" if n is None else f"profile_call_s_kv{n}") + ("" if tp is None else "_topp") + ptag(pk)] = round(dt, 4)
         print(json.dumps(res))
         return
     rows = []
@@ -94,21 +120,23 @@ def main():
                 e = None if a.skip_eager else min(timed(lambda: m.generate(text, seg, cond_scale=cs, **kw))[0] for _ in range(max(1, a.runs - 1)))
             r = {"B": b, "cond_scale": cs, "graph_ms_per_token": round(1e3 * g / L, 4), "graph_images_per_min": round(60 * b / g, 2),
                  "capture_s": round(first - g, 3)}
-            if a.kv_splits or a.top_p is not None:
+            if a.kv_splits or a.top_p is not None or a.keep_rows:
                 # every column twice (more with --runs), alternating over the columns: the spread of the repeats is the noise to beat
-                cols = [(n, tp) for n in [None] + a.kv_splits for tp in [None] + ([a.top_p] if a.top_p is not None else [])]
+                cols = [(n, tp, pk) for n in [None] + a.kv_splits for tp in [None] + ([a.top_p] if a.top_p is not None else [])
+                        for pk in prompts]
+                pkws = {pk: prompt_kw(b, pk) for pk in prompts}
                 with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
-                    for n, tp in cols[1:]:
-                        m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, top_p=tp, **kw)          # capture
+                    for n, tp, pk in cols[1:]:
+                        m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, top_p=tp, **kw, **pkws[pk])          # capture
                     times = {c: [] for c in cols}
                     for _ in range(max(2, a.runs)):
-                        for n, tp in cols:
-                            times[(n, tp)].append(timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, top_p=tp,
-                                                                           **kw))[0])
-                for n, tp in cols:
-                    tag = ("none" if n is None else str(n)) + ("" if tp is None else "_topp")
-                    r[f"graph_ms_per_token_kv{tag}"] = round(1e3 * min(times[(n, tp)]) / L, 4)
-                    r[f"spread_ms_per_token_kv{tag}"] = round(1e3 * (max(times[(n, tp)]) - min(times[(n, tp)])) / L, 4)
+                        for n, tp, pk in cols:
+                            times[(n, tp, pk)].append(timed(lambda: m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=n, top_p=tp,
+                                                                               **kw, **pkws[pk]))[0])
+                for n, tp, pk in cols:
+                    tag = ("none" if n is None else str(n)) + ("" if tp is None else "_topp") + ptag(pk)
+                    r[f"graph_ms_per_token_kv{tag}"] = round(1e3 * min(times[(n, tp, pk)]) / L, 4)
+                    r[f"spread_ms_per_token_kv{tag}"] = round(1e3 * (max(times[(n, tp, pk)]) - min(times[(n, tp, pk)])) / L, 4)
                 if a.kv_splits:
                     r["kv_auto_resolves_to"] = m._resolve_kv_splits("auto", 2 * b if cs is not None else b)
             if e is not None:
@@ -116,7 +144,7 @@ def main():
             rows.append(r)
             print(json.dumps(r), file=sys.stderr, flush=True)
             m.release_decode_graphs()
-    print(json.dumps({"metric": "MakeAScene.generate, config-4 width, bf16 autocast", "tokens_per_image": L, "top_k": kw["top_k"], "top_p": a.top_p,
+    print(json.dumps({"metric": "MakeAScene.generate, config-4 width, bf16 autocast", "tokens_per_image": L, "top_k": kw["top_k"], "top_p": a.top_p, "keep_rows": a.keep_rows,
                       "device": torch.cuda.get_device_name(0), "rows": rows}))
 
 

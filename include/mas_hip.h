@@ -294,6 +294,16 @@ int mas_dropout_apply(const void* x, void* y, long long n, int dtype, float p, c
 int mas_spatial_attn_fwd(const void* qkv, void* out, float* lse, int dtype, int N, int S, int C, void* stream);
 int mas_spatial_attn_bwd(const void* qkv, const void* dout, const float* lse, float* delta, void* dqkv, int dtype, int N, int S, int C,
                          void* stream);
+/* The same core beyond 256 tokens (the 512^2 model's AttnBlocks see 32x32 = 1024): an online softmax over 256-key chunks, so the scores
+ * are bounded by nothing in LDS and no [S, S] tensor exists.  Same layouts and conventions as the pair above; 1 <= S <= 4096, C <= 512,
+ * C % 32 == 0, bf16 only.  Forward: out [N, S, C], lse [N, S] fp32 (NULL when no backward follows).  Backward: two launches, both
+ * recomputing the probabilities from lse; it also takes `out`, the forward's output, because delta = rowsum(dout o out) has to exist
+ * before the first key chunk (delta [N, S] fp32 is written by the first launch and read by the second).  dqkv [N, S, 3C]: every element
+ * written exactly once, no atomics, results repeat bit for bit.  Not bit-equal to the pair above at S <= 256: the probabilities are
+ * rounded to bf16 before the normalisation here and after it there.                                                                  */
+int mas_spatial_attn_flash_fwd(const void* qkv, void* out, float* lse, int dtype, int N, int S, int C, void* stream);
+int mas_spatial_attn_flash_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int dtype,
+                               int N, int S, int C, void* stream);
 
 /* ---- decode-time (KV-cached) attention  (replaces the cached branch of SelfAttention.forward, models/transformer.py:73-115,
  * for token-by-token sampling: SURVEY 8(f) rank 3).  nq new queries of every (batch, head) against a cache of past + nq keys /

@@ -140,6 +140,8 @@ _SIGNATURES = {
     "mas_dropout_apply": (_i, [_p, _p, C.c_longlong, _i, _f, _p, _p]),
     "mas_spatial_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "mas_spatial_attn_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "mas_spatial_attn_flash_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "mas_spatial_attn_flash_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mas_attn_decode": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f, _p]),
     "mas_attn_decode_dev": (_i, [_p, _p, _p, C.c_longlong, _p, _p, _i, C.c_longlong, _i, _p, C.c_longlong, _i, _i, _i, _i, _p, _f, _p]),
     "mas_decode_embed": (_i, [_p, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),

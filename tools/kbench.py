@@ -142,6 +142,36 @@ def main():
         hh = h if h != 256 else 16
         qkv = torch.randn(n, 3 * cc, hh, hh, device=dev).to(dt).contiguous(memory_format=torch.channels_last).requires_grad_(True)
         fl = 4.0 * n * (hh * hh) ** 2 * cc
+        if hh * hh > 256:
+            # beyond the 256-token kernels: the chunked kernels (spatial_attn_flash.hip) against the library path (two bmm + softmax and
+            # their autograd) in one process, alternating, each column twice; then the allocator's peak of one forward + backward per path
+            go = torch.randn(n, cc, hh, hh, device=dev).to(dt).contiguous(memory_format=torch.channels_last)
+            def fb():
+                qkv.grad = None
+                ops.spatial_attention(qkv, cc).backward(go)
+            old = ops.set_spatial_flash(True)
+            try:
+                cols = []
+                for rep in range(2):
+                    for on in (True, False):
+                        ops.set_spatial_flash(on)
+                        cols.append((on, timeit(lambda: ops.spatial_attention(qkv.detach(), cc), a.iters), timeit(fb, a.iters)))
+                for on, ms, ms2 in cols:
+                    print(f"sp_attn n={n} S={hh*hh} C={cc} {'flash  ' if on else 'library'}: fwd {ms*1e3:8.1f} us {fl/ms/1e9:6.1f} TFLOP/s   "
+                          f"fwd+bwd {ms2*1e3:8.1f} us {3.5*fl/ms2/1e9:6.1f} TFLOP/s")
+                for on in (True, False):
+                    ops.set_spatial_flash(on)
+                    qkv.grad = None
+                    torch.cuda.synchronize()
+                    base = torch.cuda.memory_allocated()
+                    torch.cuda.reset_peak_memory_stats()
+                    fb()
+                    torch.cuda.synchronize()
+                    print(f"sp_attn n={n} S={hh*hh} C={cc} {'flash  ' if on else 'library'}: peak memory of fwd+bwd {(torch.cuda.max_memory_allocated() - base) / 2**20:.1f} MiB "
+                          f"above the {base / 2**20:.1f} MiB of inputs")
+            finally:
+                ops.set_spatial_flash(old)
+            return
         ms = timeit(lambda: ops.spatial_attention(qkv.detach(), cc), a.iters)
         print(f"sp_attn fwd n={n} S={hh*hh} C={cc}: {ms*1e3:.1f} us  {fl/ms/1e9:.1f} TFLOP/s")
         go = torch.randn(n, cc, hh, hh, device=dev).to(dt).contiguous(memory_format=torch.channels_last)

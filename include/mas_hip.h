@@ -445,6 +445,30 @@ int mas_layernorm_bwd_colsum(const void* x, const void* dy, const float* gamma, 
                              float* dgamma, float* dbeta, float* dx_colsum, int in_dtype, int out_dtype, int rows, int D,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* mas_token_ce_* (ABI v9): the stage-2 objective, F.cross_entropy(pred_logit.view(-1, V), img_token.view(-1)) of reference train.py:152 for
+ *   class-index targets, with ignore_index and label smoothing, on fp32 or bf16 logits read IN PLACE: row r of `rows` starts at element
+ *   logits + (r / inner) * outer_stride + (r % inner) * ld and holds V contiguous classes (a contiguous matrix: inner = rows,
+ *   outer_stride = 0, ld = V; the [B, L, V] slice of a [B, S, V] tensor: inner = L, outer_stride = S * V, ld = V).  V any positive int,
+ *   rows * V may exceed 2^31.  Rows that start on a 16-byte boundary are read in 16-byte units, their tail V % (16 / sizeof) and every
+ *   other row element by element.  target int64 [rows]; target == ignore_index: row loss 0 and a zero gradient row; any other target outside
+ *   [0, V): NaN in that row's loss and gradient row (no load is indexed by a target value).  Arithmetic fp32; no atomics: results repeat bit
+ *   for bit.  No host synchronisation: the three calls capture into a graph.
+ *   mas_token_ce_fwd: one pass.  row_loss [rows] fp32 = (1 - eps) ((m - x_t) + log l) + eps ((m - mean_j x_j) + log l) with m = max_j x_j,
+ *     l = sum_j exp(x_j - m); stats [rows][2] fp32 = {m, log l} for the backward (kept apart: m + log l would round at large logits).
+ *   mas_token_ce_reduce: reduction MAS_CE_MEAN | MAS_CE_SUM: out[0] = the sum of row_loss in fp64, fixed order (MEAN: divided by the count),
+ *     out[1] = the count of rows whose target is not ignore_index, both fp32 on the device; all rows ignored: MEAN gives NaN.
+ *   mas_token_ce_bwd: dx [rows][V] contiguous, in the logits' dtype (rounded once), dx_j = w_r (exp((x_j - m) - log l) - (1 - eps) [j = t]
+ *     - eps / V); w_r = grad[0] (MAS_CE_SUM), grad[0] / loss_count[1] (MAS_CE_MEAN; loss_count = the reduce call's out), grad[r]
+ *     (MAS_CE_NONE); grad fp32 on the device.                                                                                          */
+enum { MAS_CE_NONE = 0, MAS_CE_MEAN = 1, MAS_CE_SUM = 2 };
+int mas_token_ce_fwd(const void* logits, int dtype, long long rows, int V, long long inner, long long outer_stride, long long ld,
+                     const int64_t* target, long long ignore_index, float label_smoothing, float* row_loss, float* stats, void* stream);
+int mas_token_ce_reduce(const float* row_loss, const int64_t* target, long long rows, long long ignore_index, int reduction, float* out,
+                        void* stream);
+int mas_token_ce_bwd(const void* logits, int dtype, long long rows, int V, long long inner, long long outer_stride, long long ld,
+                     const int64_t* target, long long ignore_index, float label_smoothing, const float* stats, const float* grad,
+                     const float* loss_count, int reduction, void* dx, void* stream);
+
 /* mas_layernorm_pair_* (ABI v9): the sandwich LayerNorm + residual of one sub-block and the pre-LayerNorm of the next as ONE pass,
  *   xnew = residual + LN1(h),  y2 = LN2(xnew)      (reference models/transformer.py:201-203 + :205, and :207-209 + :197 of the next layer
  *   or the final LayerNorm :264) -- the row stays in registers between the two: 12 B per element instead of 16, bit for bit the values

@@ -27,6 +27,7 @@ ACT_NONE, ACT_AFFINE, ACT_AFFINE_SILU = 0, 1, 2
 ABI_VERSION = 9
 WLAYOUT_K64, WLAYOUT_K32, WLAYOUT_UP2 = 0, 1, 2
 ATTN_DECODE_MAX_SPLITS = 32   # MAS_ATTN_DECODE_MAX_SPLITS
+CE_NONE, CE_MEAN, CE_SUM = 0, 1, 2   # MAS_CE_*
 
 
 class ConvDesc(C.Structure):
@@ -164,6 +165,10 @@ _SIGNATURES = {
     "mas_gelu_tanh_bwd": (_i, [_p, _p, _p, _i, C.c_longlong, _p]),
     "mas_gelu_tanh_bwd_colsum_workspace": (_sz, [_i, _i]),
     "mas_gelu_tanh_bwd_colsum": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _i, _p, _sz, _p]),
+    "mas_token_ce_fwd": (_i, [_p, _i, C.c_longlong, _i, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, _f, _p, _p, _p]),
+    "mas_token_ce_reduce": (_i, [_p, _p, C.c_longlong, C.c_longlong, _i, _p, _p]),
+    "mas_token_ce_bwd": (_i, [_p, _i, C.c_longlong, _i, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, _f, _p, _p, _p, _i, _p,
+                              _p]),
     "mas_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "mas_layernorm_bwd_workspace": (_sz, [_i, _i]),
     "mas_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),

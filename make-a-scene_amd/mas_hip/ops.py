@@ -2039,3 +2039,84 @@ class _LinearBf16(torch.autograd.Function):
 
 def linear_bf16(x, weight, bias):
     return _LinearBf16.apply(x, weight, bias)
+
+
+# --------------------------------------------------------------------------- #
+# stage-2 objective: token cross-entropy (token_loss.hip)
+# --------------------------------------------------------------------------- #
+_CE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}   # MAS_CE_*
+
+
+def _ce_layout(x: torch.Tensor):
+    """-> (x as the kernels read it, inner, outer_stride, ld): row r of the flattened [..., V] logits starts at element
+    (r // inner) * outer_stride + (r % inner) * ld.  A 3-D view with a contiguous last dimension (the [B, L, V] slice of [B, S, V]) is read
+    in place; every other non-contiguous input is copied once."""
+    v = x.shape[-1]
+    rows = x.numel() // v
+    if x.is_contiguous():
+        return x, rows, 0, v
+    if x.dim() == 3 and (v == 1 or x.stride(2) == 1) and x.stride(0) >= 0 and x.stride(1) >= 0:
+        return x, x.shape[1], x.stride(0), x.stride(1)
+    return x.contiguous(), rows, 0, v
+
+
+class _TokenCrossEntropy(torch.autograd.Function):
+    """``mas_token_ce_fwd`` (+ ``mas_token_ce_reduce``) forward, ``mas_token_ce_bwd`` backward: one read of the logits each way and one
+    write of the gradient, in the logits' dtype; the per-row {max, log-sum} pair and the count of rows not ignored stay on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, reduction, ignore_index, eps):
+        x, inner, outer, ld = _ce_layout(logits)
+        v = x.shape[-1]
+        rows = x.numel() // v
+        tgt = target.reshape(-1).contiguous()
+        row_loss = torch.empty(rows, dtype=torch.float32, device=x.device)
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        check(lib().mas_token_ce_fwd(_ptr(x), _DT[x.dtype], rows, v, inner, outer, ld, _ptr(tgt), ignore_index, eps, _ptr(row_loss),
+                                     _ptr(stats), _stream()), "token_ce_fwd")
+        out = None
+        if reduction:
+            out = torch.empty(2, dtype=torch.float32, device=x.device)       # {loss, count of rows not ignored}
+            check(lib().mas_token_ce_reduce(_ptr(row_loss), _ptr(tgt), rows, ignore_index, reduction, _ptr(out), _stream()), "token_ce_reduce")
+        ctx.save_for_backward(x, tgt, stats, out)
+        ctx.cfg = (reduction, ignore_index, eps, inner, outer, ld, logits.shape)
+        return out[0] if reduction else row_loss.view(target.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, tgt, stats, out = ctx.saved_tensors
+        reduction, ignore_index, eps, inner, outer, ld, shape = ctx.cfg
+        v = x.shape[-1]
+        rows = x.numel() // v
+        g = g.float().reshape(-1).contiguous()                              # [1], or [rows] for reduction "none"
+        dx = torch.empty((rows, v), dtype=x.dtype, device=x.device)
+        check(lib().mas_token_ce_bwd(_ptr(x), _DT[x.dtype], rows, v, inner, outer, ld, _ptr(tgt), ignore_index, eps, _ptr(stats), _ptr(g),
+                                     _ptr(out), reduction, _ptr(dx), _stream()), "token_ce_bwd")
+        return dx.view(shape), None, None, None, None
+
+
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor, *, reduction: str = "mean", ignore_index: int = -100,
+                  label_smoothing: float = 0.0, weight=None) -> torch.Tensor:
+    """``F.cross_entropy`` for class-index targets with the LAST dimension of ``logits`` [..., V] as the classes and ``target`` [...]
+    int64 -- the stage-2 objective (reference train.py:152) without the fp32 cast, the copy of a sliced input or the log-softmax
+    temporaries: ``ops.cross_entropy(model(text, seg, img), img)`` replaces ``F.cross_entropy(logits.view(-1, V), img.view(-1))``, and
+    works unchanged on what a wrapper that only routes ``forward()`` (DistributedDataParallel) returns.  fp32 or bf16 logits; the result is
+    fp32 (a scalar, or [...] for ``reduction="none"``), the gradient has the logits' dtype and shape.  A target equal to ``ignore_index``
+    contributes nothing; any other target outside [0, V) makes that row's loss and gradient NaN (torch would device-assert).  Class
+    weights and class-probability targets are not offered."""
+    if reduction not in _CE_REDUCTIONS:
+        raise ValueError(f"cross_entropy: reduction {reduction!r} (one of 'mean', 'sum', 'none')")
+    if not 0.0 <= float(label_smoothing) <= 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing {label_smoothing} outside [0, 1]")
+    if weight is not None:
+        raise ValueError("cross_entropy: class weights (weight=) are not offered")
+    if target.is_floating_point() or target.is_complex():
+        raise ValueError("cross_entropy: class-probability (float) targets are not offered; pass int64 class indices")
+    if logits.dim() < 1 or tuple(target.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"cross_entropy: logits [..., V] {tuple(logits.shape)} need a target of shape [...], got {tuple(target.shape)}")
+    if logits.numel() == 0:
+        raise ValueError("cross_entropy: empty logits")
+    _require_cuda(logits, "cross_entropy")
+    _require_cuda(target, "cross_entropy")
+    _check_dtype(logits, "cross_entropy")
+    return _TokenCrossEntropy.apply(logits, target.long(), _CE_REDUCTIONS[reduction], int(ignore_index), float(label_smoothing))

@@ -579,3 +579,35 @@ class MakeAScene(nn.Module):
         transformer_output, _ = self.transformer(embeddings, None, cache=None, use_cache=False)
         logits = self.to_logits(transformer_output)
         return logits[:, -self.image_length - 1:-1, :]
+
+    def _image_logits(self, text_tokens, seg_tokens, img_tokens):
+        """the logits ``forward`` returns, from the ``image_length`` hidden rows that predict an image token alone: LayerNorm and Linear
+        are row-wise, so slicing BEFORE ``to_logits`` gives the values of ``forward``'s slice without the third of the GEMM it throws away"""
+        embeddings = self._prompt_embeddings(text_tokens, seg_tokens)
+        embeddings = torch.cat((embeddings, self.image_token_embedding(img_tokens) + self.get_image_pos_embeddings(img_tokens)), dim=1)
+        transformer_output, _ = self.transformer(embeddings, None, cache=None, use_cache=False)
+        return self.to_logits(transformer_output[:, -self.image_length - 1:-1, :])
+
+    def token_loss(self, text_tokens, seg_tokens, img_tokens, *, reduction="mean", ignore_index=-100, label_smoothing=0.0):
+        """The stage-2 objective in one call: ``F.cross_entropy(self(text, seg, img).view(-1, V), img.view(-1))`` (reference train.py:152)
+        with the logits computed for the image positions only and fed to ``ops.cross_entropy`` as they are -- fp32, or bf16 under bf16
+        autocast -- without a cast or a copy.  Returns the loss (fp32; [B, image_length] for ``reduction="none"``).  A wrapper that only
+        routes ``forward()`` (DistributedDataParallel) keeps ``ops.cross_entropy(wrapped(text, seg, img), img)``: the same loss kernels on
+        the full-length logits GEMM."""
+        logits = self._image_logits(text_tokens, seg_tokens, img_tokens)
+        return ops.cross_entropy(logits, img_tokens, reduction=reduction, ignore_index=ignore_index, label_smoothing=label_smoothing)
+
+    @torch.no_grad()
+    def log_likelihood(self, text_tokens, seg_tokens, img_tokens, *, per_token=False):
+        """log p(img_tokens | text, seg) under the model, [B] fp32: the sum over the image positions of log p(token | text, seg, earlier
+        tokens) -- the negative of ``token_loss(..., reduction="none")`` summed over each row in a fixed order; ``per_token``: the
+        [B, image_length] terms themselves (their ``.sum(1)`` is the [B] form, bit for bit).
+
+        Reranking: draw n candidates for one prompt, score them and keep the best --
+        ``t = text.expand(n, -1); s = seg.expand(n, -1); cand = model.generate(t, s, top_p=0.9)``;
+        ``score = model.log_likelihood(t, s, cand); best = cand[score.argmax()]`` (divide by ``image_length`` to compare per token).
+        Call it under the autocast mode the candidates were sampled in.  A wrapper that only routes ``forward()`` scores with
+        ``-ops.cross_entropy(wrapped(t, s, cand), cand, reduction="none").sum(1)``."""
+        logits = self._image_logits(text_tokens, seg_tokens, img_tokens)
+        logp = -ops.cross_entropy(logits, img_tokens, reduction="none")
+        return logp if per_token else logp.sum(1)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MAS_ABI_VERSION 9
+#define MAS_ABI_VERSION 10
 
 enum { MAS_OK = 0, MAS_EINVAL = -1, MAS_EUNSUPPORTED = -2, MAS_ELAUNCH = -3, MAS_EWORKSPACE = -4 };
 enum { MAS_F32 = 0, MAS_BF16 = 1 };
@@ -51,6 +51,11 @@ typedef struct MasConvDesc {
                                    H,W above are then the PHYSICAL (pre-upsample) size */
     int32_t w_layout;           /* MAS_WLAYOUT_*: how w_packed was packed; mas_conv_fwd requires mas_conv_weight_layout(d)
                                    or MAS_WLAYOUT_K64 (always accepted); ignored by mas_conv_wgrad */
+    int32_t wgrad_cus;          /* (ABI v10) CUs the persistent 3x3 weight-gradient grid is sized for, which sets its split-K count:
+                                   0 = all of them, -1 = three quarters (for a caller that runs the weight gradient on a second stream
+                                   beside other kernels), n > 0 = n (values above the device's count: all).  Read by mas_conv_wgrad_splits,
+                                   mas_conv_wgrad_partial and mas_conv_wgrad only -- hand the SAME value to splits and partial; ignored
+                                   by every other entry point */
 } MasConvDesc;
 
 int         mas_abi_version(void);

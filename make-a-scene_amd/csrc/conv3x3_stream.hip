@@ -508,9 +508,7 @@ int launch_stream(const StreamParams& p, hipStream_t s) {
     }
     const long long tiles = (long long)p.N * p.tiles_h * p.tiles_w * p.n_ct;
     // 4x the resident work-groups (one per CU): see conv_fwd.hip launch_v -- a co-running RCCL kernel then costs a quarter round
-    long long resident = 4LL * mas_num_cus();
-    static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
-    if (wgs_per_cu > 0) resident = (long long)wgs_per_cu * mas_num_cus();
+    const long long resident = mas_resident_wgs(4);
     const unsigned blocks = (unsigned)(tiles < resident ? tiles : resident);
     StreamParams pb = p;
     pb.xcd_bands = mas_xcd_band_walk_ok(blocks, tiles) ? 1 : 0;

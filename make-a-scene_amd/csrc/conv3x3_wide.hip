@@ -527,11 +527,11 @@ int launch_wide(const WideParams& p, hipStream_t s) {
         mas_attr_done(attr_mask, attr_bit);
     }
     const long long tiles = (long long)p.N * p.tiles_h * p.tiles_w * p.n_ct;
-    long long resident = 4LL * mas_num_cus();              // 4x oversubscription: see conv_fwd.hip launch_v
-    static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
-    if (wgs_per_cu > 0) resident = (long long)wgs_per_cu * mas_num_cus();
+    const long long resident = mas_resident_wgs(4);         // 4x oversubscription: see conv_fwd.hip launch_v
     const unsigned blocks = (unsigned)(tiles < resident ? tiles : resident);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), W_LDS, s, p);
+    WideParams pb = p;
+    pb.xcd_bands = mas_xcd_band_walk_ok(blocks, tiles) ? 1 : 0;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), W_LDS, s, pb);
     MAS_CHECK_LAUNCH("conv3x3_wide");
     return MAS_OK;
 }
@@ -579,13 +579,6 @@ int mas_conv3x3_wide_launch(const MasConvDesc* d, const void* x, const float* sc
     p.tiles_h = mas_cdiv(d->Ho, 16); p.tiles_w = mas_cdiv(d->Wo, 32); p.n_ct = d->Cout / 128;
     auto magic = [](int dv) { return (unsigned)((0x100000000ULL + (unsigned)dv - 1) / (unsigned)dv); };   // (d = 1 handled in the kernel)
     p.m_ct = magic(p.n_ct); p.m_tw = magic(p.tiles_w); p.m_th = magic(p.tiles_h);
-    {
-        const long long tiles = (long long)p.N * p.tiles_h * p.tiles_w * p.n_ct;
-        static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
-        const long long resident = (long long)(wgs_per_cu > 0 ? wgs_per_cu : 4) * mas_num_cus();
-        const long long blocks = tiles < resident ? tiles : resident;
-        p.xcd_bands = mas_xcd_band_walk_ok(blocks, tiles) ? 1 : 0;
-    }
     if (stats) {
         if (d->act != MAS_ACT_NONE) return residual ? launch_wide<true, true, true>(p, s) : launch_wide<true, false, true>(p, s);
         return residual ? launch_wide<false, true, true>(p, s) : launch_wide<false, false, true>(p, s);

@@ -21,6 +21,7 @@
 // hipcc's counted s_waitcnt vmcnt(N) keeps the patch prefetch (issued one slot per tap, after that
 // tap's weight loads) in flight across two taps and barriers.
 #include "mas_lds.h"
+#include "mas_tilewalk.h"
 #include <stdlib.h>
 
 namespace {
@@ -557,9 +558,7 @@ int launch_v(const ConvParams& p0, hipStream_t s) {
     // (an RCCL collective overlapping backward) holds some CUs, a grid of exactly one work-group per CU would run the
     // displaced work-groups as a second full round (2x), this runs them as a fifth quarter-round (1.25x).  Measured cost
     // of the 4x on an idle GPU: < 0.5 % (kbench / bench.py).
-    long long resident = 4LL * (BIG ? 1LL : 2LL) * mas_num_cus();
-    static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);      // tests: one work-group per CU -> several tiles per work-group
-    if (wgs_per_cu > 0) resident = (long long)wgs_per_cu * mas_num_cus();
+    const long long resident = mas_resident_wgs(4 * (BIG ? 1 : 2));
     const unsigned blocks = (unsigned)(tiles < resident ? tiles : resident);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), lds, s, q);
     MAS_CHECK_LAUNCH("conv_fwd");

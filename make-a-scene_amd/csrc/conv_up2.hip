@@ -26,6 +26,7 @@
 // Tiles that share a patch (the 4 phases x Cout / 128 tiles of a spatial tile) are mapped to the SAME XCD (block b runs on XCD b % 8):
 // the input is fetched into one L2 and hit there by the others.
 #include "mas_lds.h"
+#include "mas_tilewalk.h"
 #include <algorithm>
 #include <utility>
 
@@ -358,10 +359,7 @@ int launch_up2(const Up2Params& p, hipStream_t s, const char* name) {
         mas_attr_done(attr_mask, attr_bit);
     }
     const long long tiles = (long long)((p.n_spatial + 7) / 8) * 8 * p.group;
-    long long resident = 4LL * mas_num_cus();              // (conv3x3_wide.hip: 4x oversubscription)
-    static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
-    if (wgs_per_cu > 0) resident = (long long)wgs_per_cu * mas_num_cus();
-    resident = resident / 8 * 8;                           // the tile -> XCD map assumes a grid that is a multiple of 8
+    long long resident = mas_resident_wgs(4) / 8 * 8;      // (conv3x3_wide.hip: 4x oversubscription); the tile -> XCD map assumes a grid that is a multiple of 8
     if (resident < 8) resident = 8;
     const unsigned blocks = (unsigned)(tiles < resident ? tiles : resident);       // (tiles is a multiple of 8)
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), U_LDS, s, p);

@@ -508,15 +508,14 @@ int launch_dma(DmaWgradParams p, hipStream_t s) {
     return MAS_OK;
 }
 
-// MAS_WGRAD_CUS: how many CUs the persistent 3x3 weight-gradient grid is sized for.  0 (the library's default): all of them.  n > 0: n.
-// -1: three quarters -- what mas_hip.ops sets when it runs the weight gradient on a second stream beside the GroupNorm backward passes
+// MasConvDesc.wgrad_cus: how many CUs the persistent 3x3 weight-gradient grid is sized for.  0 (the default): all of them.  n > 0: n.
+// -1: three quarters -- what mas_hip.ops hands in when it runs the weight gradient on a second stream beside the GroupNorm backward passes
 // (MAS_WGRAD_STREAM=1, the default since late round 6): with one work-group on EVERY CU (138 KB of LDS each) the 6 us finalize launch between
 // the two GroupNorm passes is not placed until the weight gradient retires and the apply pass never overlaps; with a quarter of the CUs free it
 // starts at once and the passes run beside the weight gradient: step -1.35 ms at 192 of 256 CUs (208: -0.8, 176: -1.15, 160: -1.0, 128: 0;
 // profiles/r06_wgrad_stream.txt).  Alone, a 192-CU grid is 0.6 ms per step SLOWER: the two knobs go together.
-static int wgrad_cus() {
-    const int n = mas_env_int("MAS_WGRAD_CUS", 0);       // read per call (one getenv): the host side drops the 3/4 grid when its side stream is refused
-    const int all = mas_num_cus();
+static int wgrad_cus(const MasConvDesc* d) {
+    const int n = d->wgrad_cus, all = mas_num_cus();
     if (n == -1) return all * 3 / 4 > 0 ? all * 3 / 4 : all;
     return (n > 0 && n < all) ? n : all;
 }
@@ -542,7 +541,7 @@ static bool dma_setup(const MasConvDesc* d, DmaWgradParams& p) {
     // and a grid of exactly one work-group per CU runs the displaced ones as a second FULL round; MAS_WGRAD_OVERSUB=2 (bench.py sets
     // it for N > 1) halves the work-groups so the hardware rebalances at half-round granularity, for 2x the split-K partials.
     static const int oversub = mas_env_int("MAS_WGRAD_OVERSUB", 1);
-    int nsplit = mas_wgrad_split_start(mas_cdiv(wgrad_cus() * (oversub > 0 ? oversub : 1), out_tiles));
+    int nsplit = mas_wgrad_split_start(mas_cdiv(wgrad_cus(d) * (oversub > 0 ? oversub : 1), out_tiles));
     if (nsplit > p.n_pt) nsplit = p.n_pt;
     if (nsplit < 1) nsplit = 1;
     p.nsplit = nsplit;
@@ -572,8 +571,6 @@ int mas_conv_wgrad_dma_try(const MasConvDesc* d, const void* x, const float* sca
     return rc == MAS_OK ? 1 : rc;
 }
 
-// Split-K factor of the LDS-DMA kernel for this convolution (= slabs of the partial table mas_conv_wgrad_partial writes), or 0 when the
-// shape does not take that kernel (mas_conv_wgrad with its atomic commit is the path then).
 int mas_wgrad1x1_splits(const MasConvDesc* d);                                   // conv1x1.hip
 int mas_wgrad1x1_partial(const MasConvDesc* d, const void* x, const void* dy, float* part, float* part_bias, hipStream_t s);
 
@@ -589,16 +586,25 @@ int mas_conv_wgrad_general_partial(const MasConvDesc* d, const void* x, const fl
 // MAS_WGRAD_GENERAL_SLABS=0: shapes without a slab kernel of their own report 0 splits again and take mas_conv_wgrad's fp32 atomics
 static bool general_slabs() { static const int on = mas_env_int("MAS_WGRAD_GENERAL_SLABS", 1); return on != 0; }
 
+// The ONE route decision of the split-K partial path: which kernel family writes the slabs of this convolution and how many there are
+// (nsplit = 0: none, mas_conv_wgrad with its atomic commit is the path then).  A pure function of d, the once-per-process statics and the
+// device, shared by mas_conv_wgrad_splits (the caller sizes the partial table by it) and mas_conv_wgrad_partial (which writes it).
+enum WgradFamily { WG_1X1, WG_S2, WG_DMA, WG_THIN, WG_GENERAL };
+struct WgradRoute { WgradFamily family; int nsplit; };
+static WgradRoute wgrad_route(const MasConvDesc* d, DmaWgradParams& p) {        // p: filled for WG_DMA
+    WgradRoute r;
+    if (d->ks == 1) r = {WG_1X1, mas_wgrad1x1_splits(d)};                      // plain GEMM (conv1x1.hip)
+    else if (d->stride == 2) r = {WG_S2, mas_wgrad_s2_splits(d)};              // Downsample: conv_s2.hip
+    else if (dma_setup(d, p)) r = {WG_DMA, p.nsplit};
+    else r = {WG_THIN, mas_wgrad_thin_splits(d)};                              // the RGB-edge layers (8 <-> 128 channels): conv_thin.hip
+    if (r.nsplit <= 0) r = {WG_GENERAL, general_slabs() ? mas_conv_wgrad_general_splits(d) : 0};      // every other shape: the general kernels' slab mode
+    return r;
+}
+
+// Slabs of the partial table mas_conv_wgrad_partial writes for this convolution, or 0 when it has no split-K partial path
 extern "C" int mas_conv_wgrad_splits(const MasConvDesc* d) {
     DmaWgradParams p;
-    if (!d) return 0;
-    int k;
-    if (d->ks == 1) k = mas_wgrad1x1_splits(d);
-    else if (d->stride == 2) k = mas_wgrad_s2_splits(d);
-    else if (!dma_setup(d, p)) k = mas_wgrad_thin_splits(d);
-    else k = p.nsplit;
-    if (k > 0 || !general_slabs()) return k;
-    return mas_conv_wgrad_general_splits(d);
+    return d ? wgrad_route(d, p).nsplit : 0;
 }
 
 // The weight gradient as split-K PARTIALS: part [nsplit][Cout][3][3][Cin] fp32 and (when non-NULL) part_bias [nsplit][Cout], every
@@ -609,31 +615,24 @@ extern "C" int mas_conv_wgrad_partial(const MasConvDesc* d, const void* x, const
     MAS_ENTER();
     if (!d || !x || !dy || !part) MAS_FAIL(MAS_EINVAL, "conv_wgrad_partial: null argument");
     if (d->act != MAS_ACT_NONE && !scale_shift) MAS_FAIL(MAS_EINVAL, "conv_wgrad_partial: act prologue needs scale_shift");
-    if (d->ks == 1) {                            // plain GEMM (conv1x1.hip)
-        const int rc = mas_wgrad1x1_partial(d, x, dy, part, part_bias, reinterpret_cast<hipStream_t>(stream));
-        if (rc == 0 && general_slabs() && mas_conv_wgrad_general_splits(d) > 0)
-            return mas_conv_wgrad_general_partial(d, x, scale_shift, dy, part, part_bias, reinterpret_cast<hipStream_t>(stream));
-        if (rc == 0) MAS_FAIL(MAS_EUNSUPPORTED, "conv_wgrad_partial: this 1x1 convolution does not take the split-K partial path (mas_conv_wgrad_splits == 0)");
-        return rc < 0 ? rc : MAS_OK;
-    }
-    if (d->stride == 2) {                        // Downsample: conv_s2.hip
-        const int rc = mas_wgrad_s2_partial(d, x, dy, part, part_bias, reinterpret_cast<hipStream_t>(stream));
-        if (rc == 0 && general_slabs() && mas_conv_wgrad_general_splits(d) > 0)
-            return mas_conv_wgrad_general_partial(d, x, scale_shift, dy, part, part_bias, reinterpret_cast<hipStream_t>(stream));
-        if (rc == 0) MAS_FAIL(MAS_EUNSUPPORTED, "conv_wgrad_partial: this stride-2 convolution does not take the split-K partial path (mas_conv_wgrad_splits == 0)");
-        return rc < 0 ? rc : MAS_OK;
-    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     DmaWgradParams p;
-    if (!dma_setup(d, p)) {                      // the RGB-edge layers (8 <-> 128 channels): conv_thin.hip
-        const int rc = mas_wgrad_thin_partial(d, x, dy, part, part_bias, reinterpret_cast<hipStream_t>(stream));
-        if (rc != 0) return rc < 0 ? rc : MAS_OK;
+    const WgradRoute r = wgrad_route(d, p);
+    int rc = 0;                                  // the family's own kernel: 1 = launched, 0 = declined, < 0 = error
+    switch (r.nsplit > 0 ? r.family : WG_GENERAL) {
+    case WG_1X1:  rc = mas_wgrad1x1_partial(d, x, dy, part, part_bias, s); break;
+    case WG_S2:   rc = mas_wgrad_s2_partial(d, x, dy, part, part_bias, s); break;
+    case WG_THIN: rc = mas_wgrad_thin_partial(d, x, dy, part, part_bias, s); break;
+    case WG_DMA:
+        p.x = (const unsigned char*)x; p.ss = scale_shift; p.dy = (const unsigned char*)dy; p.dw = nullptr; p.dbias = nullptr; p.part = part; p.part_bias = part_bias;
+        return dma_launch(p, s);
+    case WG_GENERAL: break;
     }
-    if (!dma_setup(d, p) && general_slabs() && mas_conv_wgrad_general_splits(d) > 0)      // every other shape: the general kernels' slab mode
-        return mas_conv_wgrad_general_partial(d, x, scale_shift, dy, part, part_bias, reinterpret_cast<hipStream_t>(stream));
-    if (!dma_setup(d, p)) MAS_FAIL(MAS_EUNSUPPORTED, "conv_wgrad_partial: this convolution does not take the split-K partial path (mas_conv_wgrad_splits == 0)");
-    p.x = (const unsigned char*)x; p.ss = scale_shift; p.dy = (const unsigned char*)dy; p.dw = nullptr; p.dbias = nullptr;
-    p.part = part; p.part_bias = part_bias;
-    return dma_launch(p, reinterpret_cast<hipStream_t>(stream));
+    if (rc != 0) return rc < 0 ? rc : MAS_OK;
+    if (general_slabs() && mas_conv_wgrad_general_splits(d) > 0)                 // (also behind a family kernel that declined)
+        return mas_conv_wgrad_general_partial(d, x, scale_shift, dy, part, part_bias, s);
+    MAS_FAIL(MAS_EUNSUPPORTED, "conv_wgrad_partial: this %sconvolution does not take the split-K partial path (mas_conv_wgrad_splits == 0)",
+             d->ks == 1 ? "1x1 " : d->stride == 2 ? "stride-2 " : "");
 }
 
 // ---- Upsample + conv, sub-pixel form: the weight gradient as split-K partials of the 4 x 2x2 phase correlations (KS = 2 above) --------

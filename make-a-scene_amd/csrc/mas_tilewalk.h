@@ -1,5 +1,5 @@
-// How the persistent work-groups of the 3x3 kernels (conv3x3_wide.hip, conv3x3_stream.hip) walk their tile list: plain static stride,
-// or one contiguous band of the list per XCD.
+// How many persistent work-groups the convolution kernels launch, and how those of the 3x3 kernels (conv3x3_wide.hip,
+// conv3x3_stream.hip) walk their tile list: plain static stride, or one contiguous band of the list per XCD.
 #pragma once
 #include "mas_common.h"
 
@@ -7,6 +7,12 @@
 static inline bool mas_xcd_bands_enabled() {
     static const int bands = mas_env_int("MAS_CONV_XCD_BANDS", 1);
     return bands != 0;
+}
+// Work-groups of a persistent grid: per_cu on every CU (the caller's default; MAS_CONV_WGS_PER_CU = n > 0, read once per process,
+// overrides it -- tests: one work-group per CU -> several tiles per work-group).  The grid is min(tiles, this).
+static inline long long mas_resident_wgs(int per_cu) {
+    static const int wgs_per_cu = mas_env_int("MAS_CONV_WGS_PER_CU", 0);
+    return (long long)(wgs_per_cu > 0 ? wgs_per_cu : per_cu) * mas_num_cus();
 }
 // May a launch of `blocks` work-groups over `tiles` tiles take the banded walk?  It needs a grid that is a multiple of the 8 XCDs and
 // every band at least as long as the number of work-groups that walk it.

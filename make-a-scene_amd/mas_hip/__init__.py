@@ -24,7 +24,7 @@ LIB_PATH = os.environ.get("MAS_HIP_LIB") or os.path.join(_HERE, "libmas_hip.so")
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_AFFINE, ACT_AFFINE_SILU = 0, 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 WLAYOUT_K64, WLAYOUT_K32, WLAYOUT_UP2 = 0, 1, 2
 ATTN_DECODE_MAX_SPLITS = 32   # MAS_ATTN_DECODE_MAX_SPLITS
 CE_NONE, CE_MEAN, CE_SUM = 0, 1, 2   # MAS_CE_*
@@ -34,7 +34,7 @@ class ConvDesc(C.Structure):
     """Mirror of ``MasConvDesc`` (include/mas_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in (
         "N", "H", "W", "Cin", "Ho", "Wo", "Cout", "ks", "stride", "pad_top", "pad_left",
-        "in_dtype", "out_dtype", "act", "upsample", "w_layout")]
+        "in_dtype", "out_dtype", "act", "upsample", "w_layout", "wgrad_cus")]
 
 
 class PackItem(C.Structure):

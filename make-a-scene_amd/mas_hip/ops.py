@@ -7,6 +7,7 @@ bf16 / NHWC-packed copies are a cache keyed on the parameter's stamp (in-place v
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -437,11 +438,22 @@ def _desc(n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, in_dt, out_dt, act, up
     return ConvDesc(n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, _DT[in_dt], _DT[out_dt], act, int(upsample), int(w_layout))
 
 
+def _wgrad_desc(n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, dt, act, upsample):
+    """The descriptor of a weight gradient: ``_desc`` plus this device's CU budget (``wgrad_cus``).  Forward and data-gradient
+    descriptors keep budget 0 (the library ignores the field there)."""
+    d = _desc(n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, dt, dt, act, upsample)
+    d.wgrad_cus = wgrad_cus()
+    return d
+
+
+_GEOMETRY = [f for f, _ in ConvDesc._fields_ if f not in ("w_layout", "wgrad_cus")]      # what the memo tables below are keyed by
+
+
 _layout_memo = {}
 
 
 def _preferred_layout(d: ConvDesc) -> int:
-    key = tuple(getattr(d, f) for f, _ in ConvDesc._fields_[:-1])
+    key = tuple(getattr(d, f) for f in _GEOMETRY)
     lay = _layout_memo.get(key)
     if lay is None:
         lay = _layout_memo[key] = int(lib().mas_conv_weight_layout(C.byref(d)))
@@ -457,7 +469,7 @@ def _dev_key():
 
 
 def _up2_wgrad_splits(d: ConvDesc) -> int:
-    key = ("w", _dev_key()) + tuple(getattr(d, f) for f, _ in ConvDesc._fields_[:-1])
+    key = ("w", _dev_key()) + tuple(getattr(d, f) for f in _GEOMETRY)
     k = _up2_memo.get(key)
     if k is None:
         k = _up2_memo[key] = int(lib().mas_conv_up2_wgrad_splits(C.byref(d)))
@@ -465,7 +477,7 @@ def _up2_wgrad_splits(d: ConvDesc) -> int:
 
 
 def _up2_supported(d: ConvDesc, dgrad: bool = False) -> bool:
-    key = (dgrad, _dev_key()) + tuple(getattr(d, f) for f, _ in ConvDesc._fields_[:-1])
+    key = (dgrad, _dev_key()) + tuple(getattr(d, f) for f in _GEOMETRY)
     ok = _up2_memo.get(key)
     if ok is None:
         fn = lib().mas_conv_up2_dgrad_supported if dgrad else lib().mas_conv_up2_supported
@@ -545,13 +557,16 @@ def conv_fwd_raw(x, ss, wp, bias, residual, n, h, w, cin, ho, wo, cout, ks, stri
     return y
 
 
-def conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, act, upsample, want_bias):
+def conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, act, upsample, want_bias, dw_out=None, db_out=None):
+    """-> (dw [Cout][Cin][ks][ks] fp32, db [Cout] fp32 or None).  ``dw_out`` / ``db_out``: fp32 tensors of those shapes to write the
+    result into (a deferred weight gradient hands in tensors of the current stream); allocated here otherwise."""
     if ks == 4 and stride == 2:
         # the discriminator's 4x4 / stride-2 convolutions (reference losses/discriminator.py:20,27): the stride-2 4x4 correlation of x
         # is the stride-1 2x2 correlation of its (padded) space-to-depth image, so the weight gradient runs on the stride-1
         # transpose-read kernel with ks = 2 and 4 Cin channels; dW' [co][(dy,dx,c)][kh'][kw'] -> dW [co][c][2kh'+dy][2kw'+dx]
         if act != ACT_NONE or upsample or pt != pl:
             raise RuntimeError("conv_wgrad: the 4x4 stride-2 geometry takes no prologue / upsample fold and needs pad_top == pad_left")
+        assert dw_out is None and db_out is None     # dw is a permuted view of a temporary; never deferred (no prologue: act == ACT_NONE)
         xs = space_to_depth2x(x, ho + 1, wo + 1, pt)
         dws, db = conv_wgrad_raw(xs, None, dy, n, ho + 1, wo + 1, 4 * cin, ho, wo, cout, 2, 1, 0, 0, ACT_NONE, False, want_bias)
         dw = dws.view(cout, 2, 2, cin, 2, 2).permute(0, 3, 4, 1, 5, 2).reshape(cout, cin, 4, 4)
@@ -563,7 +578,7 @@ def conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, ac
         # Upsample + conv: the weight gradient in the sub-pixel form too (conv_wgrad_dma.hip, 2x2 taps per phase): 2.25x fewer MFMAs for the
         # same bytes; mas_wgrad_reduce_up2 folds the 4 x 4 phase taps back into the 3x3 gradient (fixed order: bitwise reproducible).
         # Batch slices (tensors of 2^31 bytes and more) are reduced one by one and added in slice order.
-        ds = [_desc(n1 - n0, h, w, cin, ho, wo, cout, ks, 1, pt, pl, x.dtype, x.dtype, ACT_NONE, True) for n0, n1 in slices]
+        ds = [_wgrad_desc(n1 - n0, h, w, cin, ho, wo, cout, ks, 1, pt, pl, x.dtype, ACT_NONE, True) for n0, n1 in slices]
         ks_ = [_up2_wgrad_splits(d) for d in ds]
         if all(k > 0 for k in ks_):
             nw4 = cout * 4 * cin
@@ -575,8 +590,9 @@ def conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, ac
             dwo = db = None
             for (n0, n1), d, k in zip(slices, ds, ks_):
                 pb0 = ws.data_ptr() + 4 * 4 * k * nw4
-                dws = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
-                dbs = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
+                first = n0 == 0                      # the first slice writes the outputs, the others are added to them
+                dws = dw_out if first and dw_out is not None else torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
+                dbs = None if not want_bias else db_out if first and db_out is not None else torch.empty(cout, dtype=torch.float32, device=x.device)
                 xs, dys = (x, dy) if len(slices) == 1 else (x[n0:n1], dy[n0:n1])
 
                 def launch_up2():
@@ -593,12 +609,12 @@ def conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, ac
                 if want_bias:
                     db = dbs if db is None else db.add_(dbs)
             return dwo, db
-    descs = [_desc(n1 - n0, h, w, cin, ho, wo, cout, ks, stride, pt, pl, x.dtype, x.dtype, act, upsample) for n0, n1 in slices]
+    descs = [_wgrad_desc(n1 - n0, h, w, cin, ho, wo, cout, ks, stride, pt, pl, x.dtype, act, upsample) for n0, n1 in slices]
     key = (x.device.index, torch.cuda.current_stream().cuda_stream)
     splits = [int(lib().mas_conv_wgrad_splits(C.byref(d))) for d in descs]
     shape = (n, h, w, cin, ho, wo, cout, ks, stride, act, 0)
-    dwo = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x.device)
-    db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
+    dwo = dw_out if dw_out is not None else torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=x.device)
+    db = None if not want_bias else db_out if db_out is not None else torch.empty(cout, dtype=torch.float32, device=x.device)
     if all(k > 0 for k in splits):
         # The convolutions that carry the FLOPs: every split-K work-group stores its partial sums into its own slab of a persistent
         # workspace (written in full by each launch: never zeroed) and ``mas_wgrad_reduce`` adds the slabs in a fixed order straight
@@ -692,17 +708,34 @@ def zero_stuff2x(x, hout, wout):
 # kernels run into the package power cap while the GroupNorm passes that follow each data gradient stay 13 % under it
 # (profiles/r05_energy_budget.txt); a layer's weight gradient depends on nothing its GroupNorm backward produces, so it can run BESIDE those
 # passes instead of in front of the data gradient: launched on the side stream right after the data gradient has been issued (ordered behind
-# it), joined before the autograd node returns -- every tensor crosses streams inside one node only, so the caching allocator needs no
-# record_stream, and whoever consumes the node's outputs (autograd, DDP / GradReducer hooks, the optimizer) sees them ordered on the
-# current stream as before.  The weight-gradient grid is sized for three quarters of the CUs in this mode (MAS_WGRAD_CUS=-1, set below
-# unless the user set it): with a persistent work-group on every CU the tiny finalize launch between the two GroupNorm passes is not placed
-# until the weight gradient retires.  Same kernels, same arithmetic; the split-K count follows the grid, so gradients differ from the
-# one-stream form in summation order only (bitwise reproducible run to run either way).  Step 52.9 -> 51.55 ms on one box
-# (profiles/r06_wgrad_stream.txt).  No CU masks (round 3's masked form lost 20 %).
+# it), joined before the autograd node returns (``_side_section``: the join is its ``finally``).  Same kernels, same arithmetic; the split-K
+# count follows the grid, so gradients differ from the one-stream form in summation order only (bitwise reproducible run to run either way).
+# Step 52.9 -> 51.55 ms on one box (profiles/r06_wgrad_stream.txt).  No CU masks (round 3's masked form lost 20 %).
+# Memory: what the node returns (dw, db -> ``param.grad``) is allocated on the CURRENT stream before the fork and handed in as ``dw_out`` /
+# ``db_out``: ordinary current-stream tensors, written by the side stream between the fork and the join, which whoever consumes them
+# (autograd, DDP / GradReducer hooks, the optimizer) sees ordered on the current stream as before.  The persistent split-K workspaces are
+# keyed by stream and live on.  Only temporaries that die inside the node come from the side stream's allocator pool (the sub-pixel route's
+# per-slice sums of a batch cut into slices); the current stream reads none of them, so no record_stream is needed, and the allocator
+# reissues a side-pool block only to a later side-stream allocation, which is made behind that node's ``side.wait_stream(current)`` on the
+# same host thread -- after the join that followed every earlier use.
 _WGRAD_STREAM = os.environ.get("MAS_WGRAD_STREAM", "1") == "1"
-_WGRAD_CUS_IS_OURS = _WGRAD_STREAM and "MAS_WGRAD_CUS" not in os.environ
-if _WGRAD_CUS_IS_OURS:
-    os.environ["MAS_WGRAD_CUS"] = "-1"                    # (libmas_hip.so reads it at every weight-gradient call)
+# The CU budget of the weight-gradient grid (``MasConvDesc.wgrad_cus``: 0 = all CUs, -1 = three quarters, n > 0 = n), per device.
+# MAS_WGRAD_CUS, read once here, is the user's override.  Otherwise -1 while the side stream is on -- with a persistent work-group on every
+# CU the tiny finalize launch between the two GroupNorm passes is not placed until the weight gradient retires -- and 0 for a device whose
+# probe refused the side stream (``_side_stream_on``; the 3/4 grid only pays beside the GroupNorm passes).  Known: it is -1 until the first
+# probe, and stays -1 when the first backward runs under a graph capture (no probe there).  NOT derived from ``_side_ok``: flipping that
+# alone compares the two schedules at one budget, bit for bit.
+_WGRAD_CUS_USER = int(os.environ["MAS_WGRAD_CUS"] or 0) if "MAS_WGRAD_CUS" in os.environ else None
+_wgrad_cus = {}
+
+
+def wgrad_cus() -> int:
+    """the budget weight-gradient descriptors of the current device carry (``_wgrad_desc``)"""
+    if _WGRAD_CUS_USER is not None:
+        return _WGRAD_CUS_USER
+    return _wgrad_cus.get(torch.cuda.current_device(), -1) if _WGRAD_STREAM else 0
+
+
 # layers below this many input elements keep their weight gradient on the current stream (0: every layer.  Measured at 0 / 2^23 / 2^25 /
 # 2^26: 50.36 / 50.66 / 51.05 / 51.23 ms -- the overlap pays even at the 16 x 16 maps; profiles/r06_wgrad_stream.txt)
 _WGRAD_STREAM_MIN_ELEMS = int(os.environ.get("MAS_WGRAD_STREAM_MIN_ELEMS", "0"))
@@ -756,8 +789,8 @@ def _side_stream_on() -> bool:
             _streams_overlap.last = (float("nan"), float("nan"))
             ok = False
         _side_ok[dev] = ok
-        if not ok and _WGRAD_CUS_IS_OURS:
-            os.environ["MAS_WGRAD_CUS"] = "0"               # the 3/4 grid only pays beside the GroupNorm passes
+        if not ok:
+            _wgrad_cus[dev] = 0                             # the 3/4 grid only pays beside the GroupNorm passes
         if not ok and _streams_overlap.last[0] == _streams_overlap.last[0]:        # (not after a probe that could not run: it has warned already)
             warnings.warn("mas_hip: the weight-gradient side stream shares a HIP hardware queue with the current stream (its kernels would "
                           "serialise: one spin kernel %.3f ms, one per stream %.3f ms): weight gradients stay on the current stream.  Export GPU_MAX_HW_QUEUES=8 (or import mas_hip before "
@@ -773,16 +806,28 @@ def _side_stream():
     return s
 
 
-def _on_side_stream(fn):
-    """fn()'s launches go to the side stream, ordered behind everything issued on the current stream so far"""
-    side = _side_stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        return fn()
+@contextlib.contextmanager
+def _side_section(on):
+    """``with _side_section(on) as on_side:`` around the part of a backward whose weight gradients are deferred.  ``on_side(fn)``: fn()'s
+    launches go to the side stream, ordered behind everything issued on the current stream so far.  On the way out -- also when the body
+    raises (``gn_bwd``, a launch hook) -- the current stream waits for the side stream (``on`` only: nothing was forked otherwise)."""
+    def on_side(fn):
+        side = _side_stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            return fn()
+
+    try:
+        yield on_side
+    finally:
+        if on:
+            torch.cuda.current_stream().wait_stream(_side_stream())
 
 
-def _join_side_stream():
-    torch.cuda.current_stream().wait_stream(_side_stream())
+def _wgrad_outputs(weight, want_bias):
+    """(dw_out, db_out) of a deferred weight gradient, allocated on the current stream (see the note above)"""
+    return (torch.empty(weight.shape, dtype=torch.float32, device=weight.device),
+            torch.empty(weight.shape[0], dtype=torch.float32, device=weight.device) if want_bias else None)
 
 
 class _NormActConv(torch.autograd.Function):
@@ -858,12 +903,12 @@ class _NormActConv(torch.autograd.Function):
         need_gn = act != ACT_NONE and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
         dx = dw = db = dgw = dgb = None
 
-        def wgrad():
+        def wgrad(*outs):
             if a is not None:          # the forward left the activated input: prologue-free weight gradient
-                return conv_wgrad_raw(a, None, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, ACT_NONE, ups, need_b)
-            return conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, act, ups, need_b)
+                return conv_wgrad_raw(a, None, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, ACT_NONE, ups, need_b, *outs)
+            return conv_wgrad_raw(x, ss, dy, n, h, w, cin, ho, wo, cout, ks, stride, pt, pl, act, ups, need_b, *outs)
 
-        # (MAS_WGRAD_STREAM: beside the GroupNorm backward, behind the data gradient -- see _on_side_stream)
+        # (MAS_WGRAD_STREAM: beside the GroupNorm backward, behind the data gradient -- see _side_section)
         defer = (need_w or need_b) and act != ACT_NONE and (need_x or need_gn) and dy.is_cuda and x.numel() >= _WGRAD_STREAM_MIN_ELEMS and _side_stream_on()
         if (need_w or need_b) and not defer:
             dw, db = wgrad()
@@ -909,15 +954,16 @@ class _NormActConv(torch.autograd.Function):
                 da = conv_fwd_raw(d_in, None, wt, None, None, n, hd, wd, cout, hl, wl, cin, ks, 1, ks - 1 - pt, ks - 1 - pl, ACT_NONE, False, cd)
                 if ups:
                     da = sumpool2x(da)
+            with _side_section(defer) as on_side:
+                if defer:
+                    outs = _wgrad_outputs(weight, need_b)
+                    dw, db = on_side(lambda: wgrad(*outs))
+                if act != ACT_NONE:
+                    dx, dgw, dgb = gn_bwd(x, da, None, cfg["groups"], act, gn_w.detach().float(), mr, ss)
+                    dgw, dgb = dgw.to(gn_w.dtype), dgb.to(gn_w.dtype)
+                else:
+                    dx = da
             if defer:
-                dw, db = _on_side_stream(wgrad)
-            if act != ACT_NONE:
-                dx, dgw, dgb = gn_bwd(x, da, None, cfg["groups"], act, gn_w.detach().float(), mr, ss)
-                dgw, dgb = dgw.to(gn_w.dtype), dgb.to(gn_w.dtype)
-            else:
-                dx = da
-            if defer:
-                _join_side_stream()
                 dw = dw.to(weight.dtype) if need_w else None
         dres = dy if ctx.has_res and ctx.needs_input_grad[5] else None
         return dx, dw, (db.to(weight.dtype) if db is not None else None), dgw, dgb, dres, None, None, None
@@ -1008,40 +1054,43 @@ class _ResBlock(torch.autograd.Function):
         dw2 = db2 = dw1 = db1 = dsw = dsb = None
         dx = dg1w = dg1b = None
 
-        def wgrad2():
-            return conv_wgrad_raw(a2, None, dy, *geo2, ACT_NONE, False, True) if a2 is not None else \
-                conv_wgrad_raw(hh, ss2, dy, *geo2, ACT_AFFINE_SILU, False, True)
+        def wgrad2(*outs):
+            return conv_wgrad_raw(a2, None, dy, *geo2, ACT_NONE, False, True, *outs) if a2 is not None else \
+                conv_wgrad_raw(hh, ss2, dy, *geo2, ACT_AFFINE_SILU, False, True, *outs)
 
-        def wgrad1(dh_):
-            return conv_wgrad_raw(a1, None, dh_, *geo1, ACT_NONE, False, True) if a1 is not None else \
-                conv_wgrad_raw(x, ss1, dh_, *geo1, ACT_AFFINE_SILU, False, True)
+        def wgrad1(dh_, *outs):
+            return conv_wgrad_raw(a1, None, dh_, *geo1, ACT_NONE, False, True, *outs) if a1 is not None else \
+                conv_wgrad_raw(x, ss1, dh_, *geo1, ACT_AFFINE_SILU, False, True, *outs)
+
+        def wgrad_side(on_side, weight, fn, *args):       # the outputs on the current stream, the launches on the side stream
+            outs = _wgrad_outputs(weight, True)
+            return on_side(lambda: fn(*args, *outs))
 
         need_x = ng[0] or ng[1] or ng[2]
-        side = dy.is_cuda and x.numel() >= _WGRAD_STREAM_MIN_ELEMS and _side_stream_on()           # weight gradients beside the GroupNorm backward passes (see _on_side_stream)
-        # conv2 / norm2
-        if (ng[7] or ng[8]) and not side:       # (a2 / a1: the activated inputs the forward left behind -> prologue-free weight gradients)
-            dw2, db2 = wgrad2()
-        da2 = conv_fwd_raw(dy, None, ConvWeight(c2w, True), None, None, *geo2, ACT_NONE, False, cd)
-        if (ng[7] or ng[8]) and side:
-            dw2, db2 = _on_side_stream(wgrad2)
-        dh, dg2w, dg2b = gn_bwd(hh, da2, None, groups, ACT_AFFINE_SILU, n2w.detach().float(), mr2, ss2)
-        # the skip path's parameter gradients and its gradient with respect to x
-        dskip = dy
-        if ctx.has_sc:
-            if ng[9] or ng[10]:
-                dsw, dsb = conv_wgrad_raw(x, None, dy, n, h, w, c, h, w, co, 1, 1, 0, 0, ACT_NONE, False, True)
+        side = dy.is_cuda and x.numel() >= _WGRAD_STREAM_MIN_ELEMS and _side_stream_on()           # weight gradients beside the GroupNorm backward passes (see _side_section)
+        with _side_section(side) as on_side:
+            # conv2 / norm2
+            if (ng[7] or ng[8]) and not side:       # (a2 / a1: the activated inputs the forward left behind -> prologue-free weight gradients)
+                dw2, db2 = wgrad2()
+            da2 = conv_fwd_raw(dy, None, ConvWeight(c2w, True), None, None, *geo2, ACT_NONE, False, cd)
+            if (ng[7] or ng[8]) and side:
+                dw2, db2 = wgrad_side(on_side, c2w, wgrad2)
+            dh, dg2w, dg2b = gn_bwd(hh, da2, None, groups, ACT_AFFINE_SILU, n2w.detach().float(), mr2, ss2)
+            # the skip path's parameter gradients and its gradient with respect to x
+            dskip = dy
+            if ctx.has_sc:
+                if ng[9] or ng[10]:
+                    dsw, dsb = conv_wgrad_raw(x, None, dy, n, h, w, c, h, w, co, 1, 1, 0, 0, ACT_NONE, False, True)
+                if need_x:
+                    dskip = conv_fwd_raw(dy, None, ConvWeight(sw, True), None, None, n, h, w, co, h, w, c, 1, 1, 0, 0, ACT_NONE, False, cd)
+            # conv1 / norm1 (+ the skip connection's gradient, fused into the GroupNorm-backward apply pass)
+            if (ng[3] or ng[4]) and not (side and need_x):
+                dw1, db1 = wgrad1(dh) if not side else wgrad_side(on_side, c1w, wgrad1, dh)
             if need_x:
-                dskip = conv_fwd_raw(dy, None, ConvWeight(sw, True), None, None, n, h, w, co, h, w, c, 1, 1, 0, 0, ACT_NONE, False, cd)
-        # conv1 / norm1 (+ the skip connection's gradient, fused into the GroupNorm-backward apply pass)
-        if (ng[3] or ng[4]) and not (side and need_x):
-            dw1, db1 = wgrad1(dh) if not side else _on_side_stream(lambda: wgrad1(dh))
-        if need_x:
-            da1 = conv_fwd_raw(dh, None, ConvWeight(c1w, True), None, None, *geo1t, ACT_NONE, False, cd)
-            if (ng[3] or ng[4]) and side:
-                dw1, db1 = _on_side_stream(lambda: wgrad1(dh))
-            dx, dg1w, dg1b = gn_bwd(x, da1, dskip, groups, ACT_AFFINE_SILU, n1w.detach().float(), mr1, ss1)
-        if side:
-            _join_side_stream()
+                da1 = conv_fwd_raw(dh, None, ConvWeight(c1w, True), None, None, *geo1t, ACT_NONE, False, cd)
+                if (ng[3] or ng[4]) and side:
+                    dw1, db1 = wgrad_side(on_side, c1w, wgrad1, dh)
+                dx, dg1w, dg1b = gn_bwd(x, da1, dskip, groups, ACT_AFFINE_SILU, n1w.detach().float(), mr1, ss1)
         cast = lambda g, ref: g.to(ref.dtype) if g is not None else None
         return (dx, cast(dg1w, n1w), cast(dg1b, n1w), cast(dw1, c1w), cast(db1, c1w), cast(dg2w, n2w), cast(dg2b, n2w),
                 cast(dw2, c2w), cast(db2, c2w), cast(dsw, sw) if sw is not None else None, cast(dsb, sw) if sw is not None else None,
@@ -1734,30 +1783,25 @@ class _ColsumHint:
     STRONG reference to dx, so the allocator cannot hand the same address to another tensor while the entry exists, and a hit requires
     the same storage address, element count, column count and version counter (no in-place write since) -- anything else (a Dropout in
     between, an accumulation, a hook that replaced the gradient) misses and the Linear computes its own sums.  Entries never outlive the
-    backward pass that made them: ``put`` queues an end-of-backward callback on the autograd engine that empties the table (a pruned
-    graph, ``autograd.grad`` on an intermediate or an exception would otherwise keep the last dx -- 25 MB at 12288 x 1024 -- alive)."""
+    backward pass that made them: EVERY ``put`` inside a backward queues an end-of-backward callback on the autograd engine that empties
+    the table (a pruned graph or ``autograd.grad`` on an intermediate would otherwise keep the last dx -- 25 MB at 12288 x 1024 --
+    alive).  The engine drops its queued callbacks when a backward raises: the entries of that pass then live until the next backward
+    that puts one ends, or ``clear()``."""
 
     def __init__(self):
         self.slots = {}
         self.hits = 0                                # (tests / probes read this)
-        self._cb_pending = False
 
     @staticmethod
     def _key(t):
         return (t.device.index, torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else (None, 0)
 
-    def _end_of_backward(self):
-        self.slots.clear()
-        self._cb_pending = False
-
     def put(self, dx, sums):
         self.slots[self._key(dx)] = (dx, dx.data_ptr(), dx.numel(), dx.shape[-1], dx._version, sums)
-        if not self._cb_pending:
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
-                self._cb_pending = True
-            except RuntimeError:                     # not inside a backward pass (direct call of the raw function): the slot is taken or
-                pass                                 # overwritten by the next put
+        try:                                         # (one per put, no "already queued" flag to go stale: the callback is idempotent)
+            torch.autograd.Variable._execution_engine.queue_callback(self.slots.clear)
+        except RuntimeError:                         # not inside a backward pass (direct call of the raw function): the slot is taken or
+            pass                                     # overwritten by the next put
 
     def take(self, dy2):
         ent = self.slots.pop(self._key(dy2), None)

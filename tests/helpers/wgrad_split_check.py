@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """GPU child of tests/test_gpu_wgrad_splits.py: every split-K weight-gradient kernel, run through ``ops.conv_wgrad_raw`` exactly as the
 backward calls it, at the split count this process was started with (MAS_WGRAD_SPLITS / MAS_WGRAD_OVERSUB / unset: read once per
-process by the library).
+process by the library) and the CU budget ``ops`` gives its weight-gradient descriptors (MAS_WGRAD_CUS in the environment, or its default).
 
     wgrad_split_check.py OUT.pt
 
 For every case of CASES: the kernel that ran is the one named (``set_launch_hook`` + ``last_kernel``); every ``ops._wgrad_partials``
 workspace is filled with NaN before each call, so a slab element no launch writes reaches dW as NaN; two calls are bitwise equal.  dW,
-db, the per-slice split counts the library reported and the case go to OUT.pt.  All numeric checks against fp64 are the parent's, on
+db, the per-slice split counts the library reported, the budget and the case go to OUT.pt.  All numeric checks against fp64 are the parent's, on
 the CPU.  Exits non-zero on a failed assertion."""
 import ctypes as C
 import os
@@ -84,7 +84,7 @@ def descs_of(ops, c, slices):
         g = (c["ho"] + 1, c["wo"] + 1, 4 * c["cin"], c["ho"], c["wo"], c["cout"], 2, 1, 0, 0)
     else:
         g = (c["h"], c["w"], c["cin"], c["ho"], c["wo"], c["cout"], c["ks"], c["stride"], c["pt"], c["pl"])
-    return [ops._desc(n1 - n0, *g, dt, dt, c["act"], c["up"]) for n0, n1 in slices]
+    return [ops._wgrad_desc(n1 - n0, *g, dt, c["act"], c["up"]) for n0, n1 in slices]
 
 
 def run(out_path):
@@ -136,8 +136,8 @@ def run(out_path):
     finally:
         ops._MAX_TENSOR_BYTES = max_bytes
         ops.set_launch_hook(None)
-    env = {k: os.environ.get(k) for k in ("MAS_WGRAD_SPLITS", "MAS_WGRAD_OVERSUB", "MAS_WGRAD_CUS")}
-    torch.save(dict(results=results, env=env, cus=torch.cuda.get_device_properties(0).multi_processor_count), out_path)
+    env = {k: os.environ.get(k) for k in ("MAS_WGRAD_SPLITS", "MAS_WGRAD_OVERSUB")}
+    torch.save(dict(results=results, env=env, wgrad_cus=ops.wgrad_cus(), cus=torch.cuda.get_device_properties(0).multi_processor_count), out_path)
 
 
 if __name__ == "__main__":

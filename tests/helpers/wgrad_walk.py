@@ -48,7 +48,7 @@ def general_bci(kernel, ks):
 
 def splits(kernel, g, cus, oversub=1, budget=None, override=0):
     """nsplit of the setup behind `kernel` for geometry g (dict: n, h, w, cin, ho, wo, cout, ks, stride; the DESCRIPTOR's values, i.e.
-    after the 4x4 / stride-2 space-to-depth rewrite).  cus = mas_num_cus(); budget = wgrad_cus() (MAS_WGRAD_CUS, DMA 3x3 only)."""
+    after the 4x4 / stride-2 space-to-depth rewrite).  cus = mas_num_cus(); budget = wgrad_cus(d) (MasConvDesc.wgrad_cus, DMA 3x3 only)."""
     ov = oversub if oversub > 0 else 1
     if kernel == "conv_wgrad_dma":
         n_pt = g["n"] * cdiv(g["ho"], 8) * cdiv(g["wo"], 16)

@@ -50,7 +50,7 @@ def test_split_entries_validate_arguments_without_gpu():
     import mas_hip
     L = mas_hip.lib()
     assert {"mas_attn_decode_split", "mas_attn_decode_split_dev"} <= set(mas_hip.EXPORTS)
-    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 9
+    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 10
     P = 4096            # any non-null 16-byte aligned address: every call below returns before it would be used
     b, h, hd = 2, 16, 64
 

@@ -101,7 +101,7 @@ def test_p_quantisation_and_scale(p, t):
 def test_dropout_entries_validate_arguments_without_gpu():
     import mas_hip
     L = mas_hip.lib()
-    assert L.mas_abi_version() == 9
+    assert L.mas_abi_version() == 10
     assert L.mas_dropout_apply(None, None, 8, mas_hip.BF16, ctypes.c_float(0.1), None, None) == -1 and b"null" in L.mas_last_error()
     assert L.mas_dropout_apply(16, 16, 8, mas_hip.BF16, ctypes.c_float(1.5), 16, None) == -1 and b"outside" in L.mas_last_error()
     assert L.mas_dropout_apply(24, 16, 8, mas_hip.BF16, ctypes.c_float(0.1), 16, None) == -1 and b"aligned" in L.mas_last_error()

@@ -1,6 +1,6 @@
 """Every split-K weight-gradient kernel at many split counts against an fp64 reference.
 
-The split count of a weight gradient is no property of the shape: it follows the CU count, the MAS_WGRAD_CUS budget, MAS_WGRAD_OVERSUB
+The split count of a weight gradient is no property of the shape: it follows the CU count, the CU budget (MasConvDesc.wgrad_cus), MAS_WGRAD_OVERSUB
 and a different clamp in each kernel, so the rest of the suite only sees the few counts its shapes give on one part.  Here it is an
 input: tests/helpers/wgrad_split_check.py runs every family (LDS-DMA 3x3 with and without the Upsample fold and the GroupNorm+SiLU
 prologue, its sub-pixel form, stride 2, bf16 / fp32 1x1, thin 8 <-> 128, the general kernels in slab mode) in one child process per
@@ -104,9 +104,6 @@ def _walk_geo(c, n):
 
 def _run_children(tmp_path):
     env0 = {k: v for k, v in os.environ.items() if k not in ("MAS_WGRAD_SPLITS", "MAS_WGRAD_OVERSUB")}
-    from mas_hip import ops
-    if ops._WGRAD_CUS_IS_OURS:
-        env0.pop("MAS_WGRAD_CUS", None)    # the child's own import sets the side-stream budget, as in training
     got = {}
     for label, extra in SETTINGS:          # one at a time; the first failure ends the test (no further child, no retry)
         out = str(tmp_path / f"wgrad_{len(got)}.pt")
@@ -130,7 +127,7 @@ def test_every_wgrad_kernel_at_every_split_count_vs_fp64(tmp_path):
     failures = []
     for label, res in got.items():
         cus, env = res["cus"], res["env"]
-        budget = cus * 3 // 4 if env["MAS_WGRAD_CUS"] == "-1" else (int(env["MAS_WGRAD_CUS"] or 0) or cus)
+        budget = cus * 3 // 4 if res["wgrad_cus"] == -1 else (res["wgrad_cus"] or cus)      # (ops.wgrad_cus() of the child)
         oversub, override = int(env["MAS_WGRAD_OVERSUB"] or 1), max(0, int(env["MAS_WGRAD_SPLITS"] or 0))
         for c in CHK.CASES:
             r = res["results"][c["name"]]

@@ -75,7 +75,7 @@ def _entry_args(mode, forced, keep, L=4, ld_keep=None):
 def test_prompt_entry_is_exported_and_validates_arguments_without_gpu():
     import mas_hip
     L = mas_hip.lib()
-    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 9
+    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 10
     assert "mas_sample_tokens_prompt" in mas_hip.EXPORTS and hasattr(L, "mas_sample_tokens_prompt")
     for mode, forced, keep, ld_keep, word in ((0, False, True, None, b"kept tokens"), (1, False, True, None, b"kept tokens"),
                                               (0, True, False, None, b"mask"), (2, True, True, None, b"mode 2"),

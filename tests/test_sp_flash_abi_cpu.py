@@ -50,7 +50,7 @@ def test_argument_validation_without_gpu():
 def test_the_shipped_entries_and_the_abi_version_are_unchanged():
     import mas_hip
     L = mas_hip.lib()
-    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 9
+    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 10
     assert L.mas_spatial_attn_fwd(1, 1, None, mas_hip.BF16, 1, 300, 64, None) == -2 and b"256" in L.mas_last_error()
     assert L.mas_spatial_attn_bwd(1, 1, 1, 1, 1, mas_hip.BF16, 1, 300, 64, None) == -2
 

@@ -1,5 +1,5 @@
 """CPU checks of the token cross-entropy (csrc/token_loss.hip, ``mas_hip.ops.cross_entropy``): the three entry points are declared,
-exported and bound under ABI 9 and refuse bad arguments before anything is launched; the float64 reference the GPU tests measure
+exported and bound (ABI 9, 10 today) and refuse bad arguments before anything is launched; the float64 reference the GPU tests measure
 against (tests/helpers/token_ce_ref.py) equals ``F.cross_entropy`` in float64 on every case of the GPU test; the Python surface raises
 without touching a device."""
 import ctypes
@@ -22,9 +22,9 @@ ENTRIES = ("mas_token_ce_fwd", "mas_token_ce_reduce", "mas_token_ce_bwd")
 def test_entries_are_declared_exported_and_bound():
     import mas_hip
     txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mas_hip.h")).read(), flags=re.S)
-    assert "#define MAS_ABI_VERSION 9" in txt and mas_hip.ABI_VERSION == 9
+    assert "#define MAS_ABI_VERSION 10" in txt and mas_hip.ABI_VERSION == 10
     L = mas_hip.lib()
-    assert L.mas_abi_version() == 9
+    assert L.mas_abi_version() == 10
     raw = ctypes.CDLL(mas_hip.LIB_PATH)
     for name in ENTRIES:
         assert re.search(r"\bint\s+%s\s*\(" % name, txt), name + " is not declared in include/mas_hip.h"

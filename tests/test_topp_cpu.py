@@ -132,7 +132,7 @@ def test_topp_entry_validates_arguments_without_gpu():
     sys.path.insert(0, os.path.join(ROOT, "make-a-scene_amd"))
     import mas_hip
     L = mas_hip.lib()
-    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 9
+    assert L.mas_abi_version() == mas_hip.ABI_VERSION == 10
     assert "mas_sample_tokens_topp" in mas_hip.EXPORTS
     assert L.mas_sample_tokens_topp(None, 0, 0, 1, 8, 0, 1, 0, None, None, None, 1, None, 0, None, 1, None, 0, None) == -1
     assert b"null" in L.mas_last_error()

@@ -129,6 +129,25 @@ int    mas_adam_blocks(long long numel);
 int    mas_adam_multi(const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
                       float weight_decay, double bias_correction1, double bias_correction2, void* stream);
 
+/* ---- Global-norm gradient clipping and AdamW over the same table (what torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW do between
+ * backward() and step(); additions under ABI 10).  Every entry walks the MasAdamItem table above (g, n, first_block; p, m, v are read only
+ * by mas_adam_multi_ex), total_blocks = the sum of mas_adam_blocks(n).
+ *   mas_grad_sqnorm_multi: partials[b] = sum of g^2 over work-group b's (at most 4096) elements, squared and added in fp64; `partials` holds
+ *     total_blocks doubles, owned by the caller.  Fixed summation order: the same data gives the same bits.  No atomics.
+ *   mas_grad_clip_coef: ONE work-group adds partials[0 .. n_partials) and then extra[0 .. n_extra) in fp64 (`extra`: squared norms of tensors
+ *     that no table holds; may be NULL with n_extra = 0, and n_partials may be 0 when n_extra is not), then writes
+ *     out[0] = (float)sqrt(sum), out[1] = min(max_norm / (out[0] + 1e-6f), 1) in fp32 -- clip_grad_norm_'s coefficient.  A NaN sum gives a NaN
+ *     norm AND a NaN coefficient (error_if_nonfinite = False).  max_norm <= 0, NaN or infinite: MAS_EINVAL.
+ *   mas_adam_multi_ex: mas_adam_multi with g * (*grad_scale_device) in place of g (NULL: no scaling; g is not written) and, with
+ *     decoupled_wd != 0, AdamW's weight decay: p -= lr wd p ahead of the moment update, no wd p term in g.  NULL and 0 is mas_adam_multi.
+ *   mas_grad_scale_multi: g *= *scale_device in place (the items' g is WRITTEN here, const in the struct notwithstanding).               */
+int    mas_grad_sqnorm_multi(const MasAdamItem* items_device, int n_items, int total_blocks, double* partials, void* stream);
+int    mas_grad_clip_coef(const double* partials, int n_partials, const double* extra, int n_extra, float max_norm, float* out, void* stream);
+int    mas_adam_multi_ex(const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
+                         float weight_decay, double bias_correction1, double bias_correction2, const float* grad_scale_device,
+                         int decoupled_wd, void* stream);
+int    mas_grad_scale_multi(const MasAdamItem* items_device, int n_items, int total_blocks, const float* scale_device, void* stream);
+
 /* ---- GroupNorm statistics (replaces the reduction half of torch.nn.GroupNorm,
  * modules.py:40-41).  x: [N,HW,C] NHWC.  Outputs:
  *   mean_rstd [N][G][2] fp32, scale_shift [N][C][2] fp32 with

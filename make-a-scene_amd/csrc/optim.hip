@@ -15,19 +15,33 @@ namespace {
 
 constexpr int ADAM_NT = 256, ADAM_PER_BLOCK = 4096;     // 4 x float4 per thread and tensor
 
-__global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* __restrict__ items, int n_items, float step_size, float inv_bc2_sqrt,
-                                                             float b1, float b2, float eps, float wd) {   // (inv_bc2_sqrt: sqrt(bias_correction2) itself)
+// the item that owns work-group b (items in ascending first_block order)
+__device__ __forceinline__ MasAdamItem item_of_block(const MasAdamItem* __restrict__ items, int n_items, int b) {
     int lo = 0, hi = n_items - 1;
-    const int b = blockIdx.x;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (items[mid].first_block <= b) lo = mid; else hi = mid - 1;
     }
-    const MasAdamItem it = items[lo];
+    return items[lo];
+}
+
+// SCALE: every gradient is multiplied by *grad_scale as it is loaded (the clip coefficient of mas_grad_clip_coef; g itself is not written).
+// DECOUPLED: AdamW -- p -= lr wd p ahead of the moments, no wd p term in g (torch's fused functor in its ADAMW mode).
+// <false, false> is the plain Adam step: neither `grad_scale` nor `lr` is read.
+template <bool SCALE, bool DECOUPLED>
+__global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* __restrict__ items, int n_items, float step_size, float inv_bc2_sqrt,
+                                                             float b1, float b2, float eps, float wd,     // (inv_bc2_sqrt: sqrt(bias_correction2) itself)
+                                                             const float* __restrict__ grad_scale, float lr) {
+    const int b = blockIdx.x;
+    const MasAdamItem it = item_of_block(items, n_items, b);
     const long long base = (long long)(b - it.first_block) * ADAM_PER_BLOCK;
     const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+    float gs = 1.0f;
+    if constexpr (SCALE) gs = *grad_scale;
     auto upd = [&](float& p, float g, float& m, float& v) {
-        if (wd != 0.0f) g += p * wd;
+        if constexpr (SCALE) g *= gs;
+        if constexpr (DECOUPLED) { if (wd != 0.0f) p -= lr * wd * p; }
+        else if (wd != 0.0f) g += p * wd;
         m = fmaf(omb1, g - m, m);                    // torch: lerp(exp_avg, grad, 1 - beta1)
         v = b2 * v + omb2 * g * g;
         const float denom = sqrtf(v) / inv_bc2_sqrt + eps;
@@ -58,19 +72,154 @@ __global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* 
     }
 }
 
+// ---- global-norm gradient clipping over the same table -----------------------------------------------------------------------------
+// sum of the 256 lanes' fp64 values, valid in thread 0: wave shuffles (offsets 32 ... 1), then the four wave sums through LDS in wave order.
+// The order is fixed, so the same data gives the same bits on every call.
+__device__ __forceinline__ double block_sum_f64(double a) {
+    __shared__ double wsum[ADAM_NT / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 0; w < ADAM_NT / 64; ++w) t += wsum[w];
+    }
+    return t;
+}
+
+// partials[b] = sum of g^2 over block b's elements, squared and added in fp64 from the first addition (the square of an fp32 value is exact
+// in fp64; gradients of 1e20 or 1e-30 neither overflow nor vanish).  One store per work-group, no atomics, nothing between work-groups.
+__global__ __launch_bounds__(ADAM_NT) void grad_sqnorm_multi_kernel(const MasAdamItem* __restrict__ items, int n_items, double* __restrict__ partials) {
+    const int b = blockIdx.x;
+    const MasAdamItem it = item_of_block(items, n_items, b);
+    const long long base = (long long)(b - it.first_block) * ADAM_PER_BLOCK;
+    double acc = 0.0;
+    if ((reinterpret_cast<uintptr_t>(it.g) & 15) == 0 && base + ADAM_PER_BLOCK <= it.n) {
+        f32x4 g[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g[k] = *reinterpret_cast<const f32x4*>(it.g + base + (long long)(k * ADAM_NT + threadIdx.x) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { const double d = (double)g[k][e]; acc += d * d; }
+        }
+    } else {                                         // a tensor's last block, or unaligned storage: element by element
+        for (int k = threadIdx.x; k < ADAM_PER_BLOCK; k += ADAM_NT) {
+            const long long i = base + k;
+            if (i < it.n) { const double d = (double)it.g[i]; acc += d * d; }
+        }
+    }
+    acc = block_sum_f64(acc);
+    if (threadIdx.x == 0) partials[b] = acc;
+}
+
+// One work-group: thread t adds partials[t], partials[t + 256], ... and then extra[t], extra[t + 256], ... in fp64; block sum; then
+// out[0] = (float)sqrt(sum), out[1] = min(max_norm / (out[0] + 1e-6f), 1) in fp32 -- torch.nn.utils.clip_grad_norm_'s coefficient.
+// The clamp is a comparison that a NaN fails, so a NaN norm gives a NaN coefficient (fminf would return 1).
+__global__ __launch_bounds__(ADAM_NT) void grad_clip_coef_kernel(const double* __restrict__ partials, int n_partials, const double* __restrict__ extra,
+                                                                 int n_extra, float max_norm, float* __restrict__ out) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n_partials; i += ADAM_NT) acc += partials[i];
+    for (int i = threadIdx.x; i < n_extra; i += ADAM_NT) acc += extra[i];
+    acc = block_sum_f64(acc);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(acc);
+        const float c = max_norm / (norm + 1e-6f);
+        out[0] = norm;
+        out[1] = c > 1.0f ? 1.0f : c;
+    }
+}
+
+// g *= *scale in place (the standalone clip_grad_norm_: the caller's optimizer reads the gradients afterwards)
+__global__ __launch_bounds__(ADAM_NT) void grad_scale_multi_kernel(const MasAdamItem* __restrict__ items, int n_items, const float* __restrict__ scale) {
+    const int b = blockIdx.x;
+    const MasAdamItem it = item_of_block(items, n_items, b);
+    const long long base = (long long)(b - it.first_block) * ADAM_PER_BLOCK;
+    float* g = const_cast<float*>(it.g);
+    const float s = *scale;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0 && base + ADAM_PER_BLOCK <= it.n) {
+        f32x4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const f32x4*>(g + base + (long long)(k * ADAM_NT + threadIdx.x) * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(g + base + (long long)(k * ADAM_NT + threadIdx.x) * 4) = v[k] * s;
+    } else {
+        for (int k = threadIdx.x; k < ADAM_PER_BLOCK; k += ADAM_NT) {
+            const long long i = base + k;
+            if (i < it.n) g[i] *= s;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int mas_adam_blocks(long long numel) { return numel <= 0 ? 0 : (int)((numel + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK); }
 
-extern "C" int mas_adam_multi(const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
-                              float weight_decay, double bias_correction1, double bias_correction2, void* stream) {
+namespace {
+
+template <bool SCALE, bool DECOUPLED>
+int adam_launch(const char* name, const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
+                float weight_decay, double bias_correction1, double bias_correction2, const float* grad_scale_device, void* stream) {
     MAS_ENTER();
-    if (!items_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "adam_multi: empty batch");
-    if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) MAS_FAIL(MAS_EINVAL, "adam_multi: bias corrections must be positive (step >= 1)");
+    if (!items_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "%s: empty batch", name);
+    if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) MAS_FAIL(MAS_EINVAL, "%s: bias corrections must be positive (step >= 1)", name);
     const float step_size = (float)((double)lr / bias_correction1);
     const float inv_bc2_sqrt = (float)sqrt(bias_correction2);      // (passed as the divisor, like torch's bias_correction2_sqrt)
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream), items_device, n_items,
-                       step_size, inv_bc2_sqrt, beta1, beta2, eps, weight_decay);
-    MAS_CHECK_LAUNCH("adam_multi");
+    hipLaunchKernelGGL((adam_multi_kernel<SCALE, DECOUPLED>), dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
+                       items_device, n_items, step_size, inv_bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale_device, lr);
+    MAS_CHECK_LAUNCH(name);
+    return MAS_OK;
+}
+
+}  // namespace
+
+extern "C" int mas_adam_multi(const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
+                              float weight_decay, double bias_correction1, double bias_correction2, void* stream) {
+    return adam_launch<false, false>("adam_multi", items_device, n_items, total_blocks, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                                     bias_correction2, nullptr, stream);
+}
+
+extern "C" int mas_adam_multi_ex(const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, double bias_correction1, double bias_correction2, const float* grad_scale_device,
+                                 int decoupled_wd, void* stream) {
+    const bool dec = decoupled_wd != 0;
+    if (!grad_scale_device && !dec)
+        return mas_adam_multi(items_device, n_items, total_blocks, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, stream);
+#define MAS_ADAM_EX(S, D) adam_launch<S, D>("adam_multi_ex", items_device, n_items, total_blocks, lr, beta1, beta2, eps, weight_decay, \
+                                            bias_correction1, bias_correction2, grad_scale_device, stream)
+    if (grad_scale_device) return dec ? MAS_ADAM_EX(true, true) : MAS_ADAM_EX(true, false);
+    return MAS_ADAM_EX(false, true);
+#undef MAS_ADAM_EX
+}
+
+extern "C" int mas_grad_sqnorm_multi(const MasAdamItem* items_device, int n_items, int total_blocks, double* partials, void* stream) {
+    MAS_ENTER();
+    if (!items_device || !partials || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "grad_sqnorm_multi: null or empty arguments");
+    hipLaunchKernelGGL(grad_sqnorm_multi_kernel, dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream), items_device,
+                       n_items, partials);
+    MAS_CHECK_LAUNCH("grad_sqnorm_multi");
+    return MAS_OK;
+}
+
+extern "C" int mas_grad_clip_coef(const double* partials, int n_partials, const double* extra, int n_extra, float max_norm, float* out,
+                                  void* stream) {
+    MAS_ENTER();
+    if (!out || n_partials < 0 || n_extra < 0 || n_partials + n_extra <= 0 || (n_partials > 0 && !partials) || (n_extra > 0 && !extra))
+        MAS_FAIL(MAS_EINVAL, "grad_clip_coef: null or empty arguments");
+    if (!(max_norm > 0.0f) || isinf(max_norm)) MAS_FAIL(MAS_EINVAL, "grad_clip_coef: max_norm must be positive and finite");
+    hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream), partials, n_partials, extra, n_extra,
+                       max_norm, out);
+    MAS_CHECK_LAUNCH("grad_clip_coef");
+    return MAS_OK;
+}
+
+extern "C" int mas_grad_scale_multi(const MasAdamItem* items_device, int n_items, int total_blocks, const float* scale_device, void* stream) {
+    MAS_ENTER();
+    if (!items_device || !scale_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "grad_scale_multi: null or empty arguments");
+    hipLaunchKernelGGL(grad_scale_multi_kernel, dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream), items_device,
+                       n_items, scale_device);
+    MAS_CHECK_LAUNCH("grad_scale_multi");
     return MAS_OK;
 }

@@ -101,6 +101,10 @@ _SIGNATURES = {
     "mas_pack_batch_blocks": (_i, [_i, _i, _i, _i, _i, _i]),
     "mas_adam_blocks": (_i, [C.c_longlong]),
     "mas_adam_multi": (_i, [_p, _i, _i, _f, _f, _f, _f, _f, C.c_double, C.c_double, _p]),
+    "mas_grad_sqnorm_multi": (_i, [_p, _i, _i, _p, _p]),
+    "mas_grad_clip_coef": (_i, [_p, _i, _p, _i, _f, _p, _p]),
+    "mas_adam_multi_ex": (_i, [_p, _i, _i, _f, _f, _f, _f, _f, C.c_double, C.c_double, _p, _i, _p]),
+    "mas_grad_scale_multi": (_i, [_p, _i, _i, _p, _p]),
     "mas_pack_conv_weight_batch": (_i, [_p, _i, _i, _p]),
     "mas_pack_tile_blocks": (_i, [_i, _i, _i]),
     "mas_pack_conv_weight_tiles": (_i, [_p, _i, _i, _i, _p]),

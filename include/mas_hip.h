@@ -493,6 +493,29 @@ int mas_token_ce_bwd(const void* logits, int dtype, long long rows, int V, long 
                      const int64_t* target, long long ignore_index, float label_smoothing, const float* stats, const float* grad,
                      const float* loss_count, int reduction, void* dx, void* stream);
 
+/* mas_seg_loss_* (additions under ABI 10): the VQ-SEG objective of reference losses/loss_seg.py:6-41 in one pass each way.  For x = the
+ *   prediction logits [N, C, H, W], t = the target of the same shape, w = pos_weight [C] fp32 (any content) and n = N C H W:
+ *     lw = 1 + (w[c] - 1) t;  bce = (1 - t) x + lw softplus(-x);  mse = (sigmoid(x) - t)^2;  loss = mean(bce) + mse_on mean(mse)
+ *     dx = g / n [ (1 - t) - lw (1 - sigmoid(x)) + mse_on 2 (sigmoid(x) - t) sigmoid(x) (1 - sigmoid(x)) ]
+ *   = F.binary_cross_entropy_with_logits(pos_weight = w) (+ F.mse_loss(sigmoid(x), t)), from one exp(-|x|) per element: finite for any
+ *   finite x.  x fp32 or bf16 (MAS_F32 / MAS_BF16); t fp32, bf16 or MAS_SEG_U8 (bool: 0 / 1 bytes).  Each tensor is DENSE and on its own
+ *   MAS_SEG_NCHW or MAS_SEG_NHWC (channels_last memory); neither is copied, base pointers need the element's alignment only, n may
+ *   exceed 2^31 (H W <= 2^30; C <= 15360 when both tensors have the same layout, C <= 7679 when they differ: the weights, and then one
+ *   pixel of targets beside them, must fit in LDS; beyond that MAS_EUNSUPPORTED).  Arithmetic fp32, sums fp64 across tiles, lanes and work-groups; no atomics, and the grid depends
+ *   on the shape and the CU count alone: results repeat bit for bit.  No host synchronisation: the calls capture into a graph.
+ *   mas_seg_loss_blocks: the work-groups of the forward = the {bce_sum, mse_sum} fp64 pairs `partials` must hold (negative: an error code).
+ *   mas_seg_loss_fwd: partials[b] = work-group b's two sums.  mas_seg_loss_reduce: ONE work-group adds partial_pairs pairs in a fixed
+ *     order -> out[0..2] = {loss, mean(bce), mse_on mean(mse)} fp32 on the device, each rounded once from fp64.
+ *   mas_seg_loss_bwd: dx in x's dtype (rounded once) and x's layout; grad = the upstream gradient g, one fp32 on the device.        */
+enum { MAS_SEG_NCHW = 0, MAS_SEG_NHWC = 1 };
+enum { MAS_SEG_U8 = 2 };      /* target dtype beside MAS_F32 / MAS_BF16 */
+int mas_seg_loss_blocks(int N, int C, int H, int W, int x_dtype, int x_layout, int t_layout);
+int mas_seg_loss_fwd(const void* x, int x_dtype, int x_layout, const void* t, int t_dtype, int t_layout, const float* pos_weight,
+                     int N, int C, int H, int W, int mse_on, double* partials, int partial_pairs, void* stream);
+int mas_seg_loss_reduce(const double* partials, int partial_pairs, long long numel, int mse_on, float* out, void* stream);
+int mas_seg_loss_bwd(const void* x, int x_dtype, int x_layout, const void* t, int t_dtype, int t_layout, const float* pos_weight,
+                     int N, int C, int H, int W, int mse_on, const float* grad, void* dx, void* stream);
+
 /* mas_layernorm_pair_* (ABI v9): the sandwich LayerNorm + residual of one sub-block and the pre-LayerNorm of the next as ONE pass,
  *   xnew = residual + LN1(h),  y2 = LN2(xnew)      (reference models/transformer.py:201-203 + :205, and :207-209 + :197 of the next layer
  *   or the final LayerNorm :264) -- the row stays in registers between the two: 12 B per element instead of 16, bit for bit the values

@@ -28,6 +28,7 @@ ABI_VERSION = 10
 WLAYOUT_K64, WLAYOUT_K32, WLAYOUT_UP2 = 0, 1, 2
 ATTN_DECODE_MAX_SPLITS = 32   # MAS_ATTN_DECODE_MAX_SPLITS
 CE_NONE, CE_MEAN, CE_SUM = 0, 1, 2   # MAS_CE_*
+SEG_NCHW, SEG_NHWC, SEG_U8 = 0, 1, 2   # MAS_SEG_*: layout codes; the uint8 target dtype beside F32 / BF16
 
 
 class ConvDesc(C.Structure):
@@ -173,6 +174,10 @@ _SIGNATURES = {
     "mas_token_ce_reduce": (_i, [_p, _p, C.c_longlong, C.c_longlong, _i, _p, _p]),
     "mas_token_ce_bwd": (_i, [_p, _i, C.c_longlong, _i, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, _f, _p, _p, _p, _i, _p,
                               _p]),
+    "mas_seg_loss_blocks": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "mas_seg_loss_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p]),
+    "mas_seg_loss_reduce": (_i, [_p, _i, C.c_longlong, _i, _p, _p]),
+    "mas_seg_loss_bwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "mas_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "mas_layernorm_bwd_workspace": (_sz, [_i, _i]),
     "mas_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),

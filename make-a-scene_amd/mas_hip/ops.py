@@ -15,8 +15,8 @@ from typing import Optional
 
 import torch
 
-from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, WLAYOUT_K64, WLAYOUT_UP2, ConvDesc, PackItem, \
-    PackTileItem, check, lib
+from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, SEG_NCHW, SEG_NHWC, SEG_U8, WLAYOUT_K64, WLAYOUT_UP2, \
+    ConvDesc, PackItem, PackTileItem, check, lib
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 _state = {"compute_dtype": torch.bfloat16 if os.environ.get("MAS_COMPUTE_DTYPE", "bf16") == "bf16" else torch.float32}
@@ -2164,3 +2164,88 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, *, reduction: str 
     _require_cuda(target, "cross_entropy")
     _check_dtype(logits, "cross_entropy")
     return _TokenCrossEntropy.apply(logits, target.long(), _CE_REDUCTIONS[reduction], int(ignore_index), float(label_smoothing))
+
+
+# --------------------------------------------------------------------------- #
+# VQ-SEG objective: weighted logits-BCE (+ MSE of the sigmoid) (seg_loss.hip)
+# --------------------------------------------------------------------------- #
+_SEG_TARGET_DT = {torch.float32: F32, torch.bfloat16: BF16, torch.uint8: SEG_U8}
+
+
+def _seg_dense(x: torch.Tensor):
+    """-> (x as the kernels read it, layout code): dense NCHW and dense NHWC (channels_last) memory are read in place; any other stride
+    pattern (a slice, an expanded tensor) is made dense NCHW first -- the one copy this op ever makes, and only then."""
+    if x.is_contiguous():
+        return x, SEG_NCHW
+    if x.is_contiguous(memory_format=torch.channels_last):
+        return x, SEG_NHWC
+    return x.contiguous(), SEG_NCHW
+
+
+class _SegLoss(torch.autograd.Function):
+    """``mas_seg_loss_fwd`` + ``mas_seg_loss_reduce`` forward, ``mas_seg_loss_bwd`` backward: one read of prediction and target each way
+    and one write of the gradient, in the prediction's dtype and memory layout.  Saved: the three inputs, nothing of their size."""
+
+    @staticmethod
+    def forward(ctx, prediction, target, pos_weight, mse):
+        x, xl = _seg_dense(prediction)
+        t, tl = _seg_dense(target)
+        n, c, h, w = x.shape
+        blocks = lib().mas_seg_loss_blocks(n, c, h, w, _DT[x.dtype], xl, tl)
+        check(min(blocks, 0), "seg_loss_blocks")
+        partials = torch.empty(2 * blocks, dtype=torch.float64, device=x.device)
+        out = torch.empty(3, dtype=torch.float32, device=x.device)      # {loss, mean bce, mean mse}
+        check(lib().mas_seg_loss_fwd(_ptr(x), _DT[x.dtype], xl, _ptr(t), _SEG_TARGET_DT[t.dtype], tl, _ptr(pos_weight), n, c, h, w, int(mse),
+                                     _ptr(partials), blocks, _stream()), "seg_loss_fwd")
+        check(lib().mas_seg_loss_reduce(_ptr(partials), blocks, x.numel(), int(mse), _ptr(out), _stream()), "seg_loss_reduce")
+        ctx.save_for_backward(x, t, pos_weight)
+        ctx.cfg = (xl, tl, bool(mse))
+        terms = out[1:]
+        ctx.mark_non_differentiable(terms)
+        return out[0], terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_terms):
+        x, t, pos_weight = ctx.saved_tensors
+        xl, tl, mse = ctx.cfg
+        n, c, h, w = x.shape
+        g = g.float().reshape(1)
+        dx = torch.empty_like(x)                                        # dense x: the same strides
+        check(lib().mas_seg_loss_bwd(_ptr(x), _DT[x.dtype], xl, _ptr(t), _SEG_TARGET_DT[t.dtype], tl, _ptr(pos_weight), n, c, h, w, int(mse),
+                                     _ptr(g), _ptr(dx), _stream()), "seg_loss_bwd")
+        return dx, None, None, None
+
+
+def seg_loss(prediction: torch.Tensor, target: torch.Tensor, pos_weight: torch.Tensor, *, mse: bool = False, return_terms: bool = False):
+    """The VQ-SEG reconstruction objective (reference losses/loss_seg.py:6-41) as one kernel each way:
+    ``F.binary_cross_entropy_with_logits(prediction, target, pos_weight=pos_weight[:, None, None])``, plus
+    ``F.mse_loss(torch.sigmoid(prediction), target)`` with ``mse=True``, both means over all N C H W elements.  ``prediction`` [N, C, H, W]
+    fp32 or bf16 logits; ``target`` of the same shape, fp32, bf16, uint8 or bool ({0, 1} or soft); ``pos_weight`` [C].  Each of the two is
+    read in place when it is dense NCHW or dense channels_last, whichever the other is; anything else (a slice) is made dense first.  The
+    loss is an fp32 scalar on the device, the gradient has the prediction's dtype, shape and memory layout; nothing of the inputs' size
+    is saved or allocated beside it, and nothing synchronises with the host.  ``return_terms=True`` also returns the detached
+    ``{"bce_mean", "mse_mean"}`` (``mse_mean`` is 0 without ``mse``)."""
+    if prediction.dim() != 4 or tuple(target.shape) != tuple(prediction.shape):
+        raise ValueError(f"seg_loss: prediction [N, C, H, W] {tuple(prediction.shape)} needs a target of the same shape, got {tuple(target.shape)}")
+    if prediction.numel() == 0:
+        raise ValueError("seg_loss: empty prediction")
+    if pos_weight.dim() != 1 or pos_weight.shape[0] != prediction.shape[1]:
+        raise ValueError(f"seg_loss: pos_weight {tuple(pos_weight.shape)} must be [C] = [{prediction.shape[1]}]")
+    if target.requires_grad:
+        raise ValueError("seg_loss: the target is not differentiated; detach it")
+    for t_ in (prediction, target, pos_weight):
+        _require_cuda(t_, "seg_loss")
+    if prediction.dtype not in _DT:
+        raise RuntimeError(f"seg_loss: prediction dtype {prediction.dtype} not supported (float32 / bfloat16)")
+    if target.dtype == torch.bool:
+        target = target.view(torch.uint8)
+    if target.dtype not in _SEG_TARGET_DT:
+        raise RuntimeError(f"seg_loss: target dtype {target.dtype} not supported (float32 / bfloat16 / uint8 / bool)")
+    pw = pos_weight.detach()
+    if pw.dtype != torch.float32 or not pw.is_contiguous():
+        pw = pw.float().contiguous()
+    loss, terms = _SegLoss.apply(prediction, target, pw, bool(mse))
+    if return_terms:
+        return loss, {"bce_mean": terms[0], "mse_mean": terms[1]}
+    return loss

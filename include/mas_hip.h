@@ -516,6 +516,30 @@ int mas_seg_loss_reduce(const double* partials, int partial_pairs, long long num
 int mas_seg_loss_bwd(const void* x, int x_dtype, int x_layout, const void* t, int t_dtype, int t_layout, const float* pos_weight,
                      int N, int C, int H, int W, int mse_on, const float* grad, void* dx, void* stream);
 
+/* mas_seg_expand, mas_seg_loss_labels_* (additions under ABI 10): the VQ-SEG map as LABEL PLANES instead of a one-hot tensor.
+ *   planes: uint8 [N, P, H, W] dense, P = n_groups + value_channels <= 8.  Plane g < n_groups is a class label: 0 sets nothing, v in
+ *   1..groups[g] sets channel base_g + v - 1 to 1 (base_g = groups[0] + ... + groups[g - 1]), anything above groups[g] sets nothing.
+ *   Plane n_groups + k holds the VALUE of channel sum(groups) + k as a byte.  C = sum(groups) + value_channels; 1 <= groups[g] <= 255;
+ *   `groups` is a host array.  Nothing is addressed through a label: a pixel's P bytes become at most P {channel, value} pairs that the
+ *   channels of the output (or of the prediction) are compared with.
+ *   mas_seg_expand: the dense map, NHWC (out_layout MAS_SEG_NHWC: [N, H, W, C_pad], channels C..C_pad - 1 exact zeros, C_pad >= C) or NCHW
+ *     ([N, C_pad, H, W]), fp32 or bf16; written in 16-byte units where `out` is 16-byte aligned and C_pad (NHWC) or H W (NCHW) is a
+ *     multiple of the unit, one element at a time otherwise.
+ *   mas_seg_loss_labels_fwd / _bwd: the loss and gradient of mas_seg_loss_fwd / _bwd (the same per-element code) with the target derived
+ *     in registers from the planes; x (and dx) fp32 or bf16, dense NCHW or NHWC, element alignment only.  A work-group takes tiles of
+ *     MAS_SEG_LABELS_TILE pixels of one image x all channels and reads a tile's labels once.  partials / mas_seg_loss_reduce / grad as
+ *     above; mas_seg_loss_labels_blocks sizes grid and workspace (negative: an error code).  No atomics, no host synchronisation.     */
+enum { MAS_SEG_LABELS_TILE = 256, MAS_SEG_MAX_PLANES = 8 };
+int mas_seg_expand(const unsigned char* planes, const int* groups, int n_groups, int value_channels, int N, int H, int W, void* out,
+                   int out_dtype, int out_layout, int C_pad, void* stream);
+int mas_seg_loss_labels_blocks(const int* groups, int n_groups, int value_channels, int N, int H, int W, int x_dtype, int x_layout);
+int mas_seg_loss_labels_fwd(const void* x, int x_dtype, int x_layout, const unsigned char* planes, const int* groups, int n_groups,
+                            int value_channels, const float* pos_weight, int N, int H, int W, int mse_on, double* partials,
+                            int partial_pairs, void* stream);
+int mas_seg_loss_labels_bwd(const void* x, int x_dtype, int x_layout, const unsigned char* planes, const int* groups, int n_groups,
+                            int value_channels, const float* pos_weight, int N, int H, int W, int mse_on, const float* grad, void* dx,
+                            void* stream);
+
 /* mas_layernorm_pair_* (ABI v9): the sandwich LayerNorm + residual of one sub-block and the pre-LayerNorm of the next as ONE pass,
  *   xnew = residual + LN1(h),  y2 = LN2(xnew)      (reference models/transformer.py:201-203 + :205, and :207-209 + :197 of the next layer
  *   or the final LayerNorm :264) -- the row stays in registers between the two: 12 B per element instead of 16, bit for bit the values

@@ -9,6 +9,10 @@ the kernel reads prediction and target once each way, in place in whichever of N
 CPU tensors, dtypes outside the op's envelope (prediction fp32 / bf16; target fp32 / bf16 / uint8 / bool) and ``MAS_SEG_LOSS=0`` run the
 torch expression, exactly as before.
 
+The target may also be a ``mas_hip.seglabels.SegLabels`` (the map as 4 label bytes per pixel): on the GPU the loss is then
+``mas_hip.ops.seg_loss_labels`` (csrc/seg_labels.hip), which derives the target in registers, so that no dense target exists anywhere;
+``MAS_SEG_LOSS=0``, CPU labels and predictions outside the op's envelope densify the labels and run the torch expression.
+
 Both classes weigh the positive class of the five channels 153..157 twenty-fold (``pos_weight`` of the logits BCE; a persistent buffer
 named ``weight``, so ``state_dict`` carries it as the reference's does) and add ``codebook_weight * qloss``;
 ``VQVAEWithBCELoss`` adds the mean squared error of the sigmoid as well."""
@@ -17,6 +21,8 @@ import os
 import torch
 import torch.nn.functional as F
 from torch import nn
+
+from mas_hip.seglabels import SegLabels
 
 _HEAVY_CHANNELS = (153, 158)        # half-open channel range with positive weight 20
 _HEAVY_WEIGHT = 20.0
@@ -38,6 +44,22 @@ class _SegLossBase(nn.Module):
                 and target.dtype in (torch.float32, torch.bfloat16, torch.uint8, torch.bool) and not target.requires_grad
                 and 0 < prediction.numel() and prediction.shape[1] <= _HIP_MAX_CHANNELS and os.environ.get("MAS_SEG_LOSS", "1") != "0")
 
+    def _labels(self, target, prediction, mse):
+        """-> the reconstruction terms for a ``SegLabels`` target, or None after which the caller runs the dense expression"""
+        if target.shape[1] != self.weight.shape[0] or tuple(target.shape) != tuple(prediction.shape):
+            raise ValueError(f"{type(self).__name__}: SegLabels of logical shape {tuple(target.shape)} ({target.layout}) against a prediction "
+                             f"{tuple(prediction.shape)} and {self.weight.shape[0]} channel weights")
+        if (prediction.is_cuda and target.is_cuda and prediction.dtype in (torch.float32, torch.bfloat16) and 0 < prediction.numel()
+                and os.environ.get("MAS_SEG_LOSS", "1") != "0"):
+            from mas_hip import ops
+            return ops.seg_loss_labels(prediction, target, self.weight, mse=mse)
+        return None
+
+    @staticmethod
+    def _densify(target, prediction):
+        """CPU labels / ``MAS_SEG_LOSS=0``: the dense fp32 map, made where the labels are, beside the prediction"""
+        return target.dense(torch.float32).to(prediction.device)
+
     def _bce(self, target, prediction):
         # channels last, so that the per-channel pos_weight broadcasts over (N, H, W)
         return F.binary_cross_entropy_with_logits(prediction.movedim(1, -1), target.movedim(1, -1), pos_weight=self.weight)
@@ -45,6 +67,11 @@ class _SegLossBase(nn.Module):
 
 class BCELossWithQuant(_SegLossBase):
     def forward(self, qloss, target, prediction):
+        if isinstance(target, SegLabels):
+            rec = self._labels(target, prediction, False)
+            if rec is not None:
+                return rec + self.codebook_weight * qloss
+            target = self._densify(target, prediction)
         if self._hip(target, prediction):
             from mas_hip import ops
             return ops.seg_loss(prediction, target, self.weight) + self.codebook_weight * qloss
@@ -53,6 +80,11 @@ class BCELossWithQuant(_SegLossBase):
 
 class VQVAEWithBCELoss(_SegLossBase):
     def forward(self, qloss, target, prediction):
+        if isinstance(target, SegLabels):
+            rec = self._labels(target, prediction, True)
+            if rec is not None:
+                return rec + self.codebook_weight * qloss
+            target = self._densify(target, prediction)
         if self._hip(target, prediction):
             from mas_hip import ops
             return ops.seg_loss(prediction, target, self.weight, mse=True) + self.codebook_weight * qloss

@@ -29,6 +29,7 @@ WLAYOUT_K64, WLAYOUT_K32, WLAYOUT_UP2 = 0, 1, 2
 ATTN_DECODE_MAX_SPLITS = 32   # MAS_ATTN_DECODE_MAX_SPLITS
 CE_NONE, CE_MEAN, CE_SUM = 0, 1, 2   # MAS_CE_*
 SEG_NCHW, SEG_NHWC, SEG_U8 = 0, 1, 2   # MAS_SEG_*: layout codes; the uint8 target dtype beside F32 / BF16
+SEG_LABELS_TILE, SEG_MAX_PLANES = 256, 8   # MAS_SEG_LABELS_TILE: pixels of one tile of the label-plane kernels; MAS_SEG_MAX_PLANES
 
 
 class ConvDesc(C.Structure):
@@ -178,6 +179,10 @@ _SIGNATURES = {
     "mas_seg_loss_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p]),
     "mas_seg_loss_reduce": (_i, [_p, _i, C.c_longlong, _i, _p, _p]),
     "mas_seg_loss_bwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "mas_seg_expand": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p]),
+    "mas_seg_loss_labels_blocks": (_i, [_p, _i, _i, _i, _i, _i, _i, _i]),
+    "mas_seg_loss_labels_fwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _i, _p]),
+    "mas_seg_loss_labels_bwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
     "mas_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "mas_layernorm_bwd_workspace": (_sz, [_i, _i]),
     "mas_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),

@@ -17,6 +17,7 @@ import torch
 
 from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, SEG_NCHW, SEG_NHWC, SEG_U8, WLAYOUT_K64, WLAYOUT_UP2, \
     ConvDesc, PackItem, PackTileItem, check, lib
+from .seglabels import SegLabels
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 _state = {"compute_dtype": torch.bfloat16 if os.environ.get("MAS_COMPUTE_DTYPE", "bf16") == "bf16" else torch.float32}
@@ -982,7 +983,18 @@ def norm_act_conv(x, weight, bias, gn_w=None, gn_b=None, residual=None, *, strid
     # weights are exactly zero-gradient-free slices) keeps every launch on the vectorised / transpose-read paths.
     epu = 8 if cd == torch.bfloat16 else 4
     cout, cin = weight.shape[0], weight.shape[1]
-    if act == ACT_NONE and cin % epu:
+    if isinstance(x, SegLabels):
+        # label planes (the VQ-SEG encoder's first convolution): the one-hot map is written once, already cast, channels_last and padded to
+        # the width the branch below pads a dense input to; only the weight is padded here (differentiably, as there)
+        if act != ACT_NONE:
+            raise RuntimeError("conv: SegLabels feed a plain convolution only (no GroupNorm in front)")
+        if x.shape[1] != cin:
+            raise ValueError(f"conv: SegLabels of {x.shape[1]} channels ({x.layout}), weight expects {cin}")
+        padc = (epu - cin % epu) % epu
+        x = seg_expand(x, dtype=cd, channels_last=True, pad_to=cin + padc)
+        if padc:
+            weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, padc))
+    elif act == ACT_NONE and cin % epu:
         padc = epu - cin % epu
         x = torch.nn.functional.pad(nhwc(x, cd), (0, 0, 0, 0, 0, padc))
         weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, padc))
@@ -2246,6 +2258,104 @@ def seg_loss(prediction: torch.Tensor, target: torch.Tensor, pos_weight: torch.T
     if pw.dtype != torch.float32 or not pw.is_contiguous():
         pw = pw.float().contiguous()
     loss, terms = _SegLoss.apply(prediction, target, pw, bool(mse))
+    if return_terms:
+        return loss, {"bce_mean": terms[0], "mse_mean": terms[1]}
+    return loss
+
+
+# --------------------------------------------------------------------------- #
+# VQ-SEG map as label planes: the dense map written once, the objective without a dense target (seg_labels.hip)
+# --------------------------------------------------------------------------- #
+def _seg_layout_args(labels, what: str):
+    """-> (the planes as the kernels read them, host int array of the group sizes, n_groups, value_channels)"""
+    from .seglabels import SegLabels
+    if not isinstance(labels, SegLabels):
+        raise TypeError(f"{what}: labels must be a mas_hip.seglabels.SegLabels, got {type(labels).__name__}")
+    _require_cuda(labels.planes, what)
+    if labels.planes.numel() == 0:
+        raise ValueError(f"{what}: empty labels")
+    lay = labels.layout
+    groups = (C.c_int * max(len(lay.groups), 1))(*lay.groups)
+    return labels.planes.contiguous(), groups, len(lay.groups), lay.value_channels
+
+
+def seg_expand(labels, *, dtype: torch.dtype, channels_last: bool = True, pad_to: Optional[int] = None) -> torch.Tensor:
+    """``SegLabels`` -> the dense map ``[B, C_pad, H, W]`` (``mas_seg_expand``): one pass that reads 4 bytes per pixel and writes the map once,
+    in channels_last memory (what the encoder's first convolution reads) or NCHW.  ``pad_to`` >= C pads the channel axis with exact zeros
+    (160 for the 159 classes in bf16: one 16-byte slot more); ``dtype`` float32 or bfloat16."""
+    planes, groups, ng, nv = _seg_layout_args(labels, "seg_expand")
+    if dtype not in _DT:
+        raise RuntimeError(f"seg_expand: dtype {dtype} not supported (float32 / bfloat16)")
+    b, c, h, w = labels.shape
+    cp = c if pad_to is None else int(pad_to)
+    if cp < c:
+        raise ValueError(f"seg_expand: pad_to = {cp} is less than the layout's {c} channels")
+    out = torch.empty((b, cp, h, w), dtype=dtype, device=planes.device,
+                      memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    check(lib().mas_seg_expand(_ptr(planes), groups, ng, nv, b, h, w, _ptr(out), _DT[dtype], SEG_NHWC if channels_last else SEG_NCHW, cp,
+                               _stream()), "seg_expand")
+    return out
+
+
+class _SegLossLabels(torch.autograd.Function):
+    """``mas_seg_loss_labels_fwd`` + ``mas_seg_loss_reduce`` forward, ``mas_seg_loss_labels_bwd`` backward.  Saved: the prediction, the planes
+    and the weights, nothing else."""
+
+    @staticmethod
+    def forward(ctx, prediction, planes, pos_weight, layout, mse):
+        x, xl = _seg_dense(prediction)
+        n, c, h, w = x.shape
+        groups = (C.c_int * max(len(layout.groups), 1))(*layout.groups)
+        ng, nv = len(layout.groups), layout.value_channels
+        blocks = lib().mas_seg_loss_labels_blocks(groups, ng, nv, n, h, w, _DT[x.dtype], xl)
+        check(min(blocks, 0), "seg_loss_labels_blocks")
+        partials = torch.empty(2 * blocks, dtype=torch.float64, device=x.device)
+        out = torch.empty(3, dtype=torch.float32, device=x.device)      # {loss, mean bce, mean mse}
+        check(lib().mas_seg_loss_labels_fwd(_ptr(x), _DT[x.dtype], xl, _ptr(planes), groups, ng, nv, _ptr(pos_weight), n, h, w, int(mse),
+                                            _ptr(partials), blocks, _stream()), "seg_loss_labels_fwd")
+        check(lib().mas_seg_loss_reduce(_ptr(partials), blocks, x.numel(), int(mse), _ptr(out), _stream()), "seg_loss_reduce")
+        ctx.save_for_backward(x, planes, pos_weight)
+        ctx.cfg = (xl, layout, bool(mse))
+        terms = out[1:]
+        ctx.mark_non_differentiable(terms)
+        return out[0], terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_terms):
+        x, planes, pos_weight = ctx.saved_tensors
+        xl, layout, mse = ctx.cfg
+        n, c, h, w = x.shape
+        groups = (C.c_int * max(len(layout.groups), 1))(*layout.groups)
+        g = g.float().reshape(1)
+        dx = torch.empty_like(x)                                        # dense x: the same strides
+        check(lib().mas_seg_loss_labels_bwd(_ptr(x), _DT[x.dtype], xl, _ptr(planes), groups, len(layout.groups), layout.value_channels,
+                                            _ptr(pos_weight), n, h, w, int(mse), _ptr(g), _ptr(dx), _stream()), "seg_loss_labels_bwd")
+        return dx, None, None, None, None
+
+
+def seg_loss_labels(prediction: torch.Tensor, labels, pos_weight: torch.Tensor, *, mse: bool = False, return_terms: bool = False):
+    """``seg_loss`` with the target given as ``SegLabels``: the same loss and gradient (the per-element code is shared, csrc/seg_elem.h), the
+    target derived in registers from 4 bytes per pixel -- no dense target exists anywhere.  ``prediction`` [N, C, H, W] fp32 or bf16
+    logits, dense NCHW or channels_last, read in place; ``labels`` of the logical shape [N, C, H, W]; ``pos_weight`` [C]."""
+    from .seglabels import SegLabels
+    if not isinstance(labels, SegLabels):
+        raise TypeError(f"seg_loss_labels: labels must be a mas_hip.seglabels.SegLabels, got {type(labels).__name__}")
+    if prediction.dim() != 4 or tuple(labels.shape) != tuple(prediction.shape):
+        raise ValueError(f"seg_loss_labels: prediction [N, C, H, W] {tuple(prediction.shape)} needs labels of the same logical shape, got "
+                         f"{tuple(labels.shape)} ({labels.layout})")
+    if prediction.numel() == 0:
+        raise ValueError("seg_loss_labels: empty prediction")
+    if pos_weight.dim() != 1 or pos_weight.shape[0] != prediction.shape[1]:
+        raise ValueError(f"seg_loss_labels: pos_weight {tuple(pos_weight.shape)} must be [C] = [{prediction.shape[1]}]")
+    for t_ in (prediction, labels.planes, pos_weight):
+        _require_cuda(t_, "seg_loss_labels")
+    if prediction.dtype not in _DT:
+        raise RuntimeError(f"seg_loss_labels: prediction dtype {prediction.dtype} not supported (float32 / bfloat16)")
+    pw = pos_weight.detach()
+    if pw.dtype != torch.float32 or not pw.is_contiguous():
+        pw = pw.float().contiguous()
+    loss, terms = _SegLossLabels.apply(prediction, labels.planes.contiguous(), pw, labels.layout, bool(mse))
     if return_terms:
         return loss, {"bce_mean": terms[0], "mse_mean": terms[1]}
     return loss

@@ -156,9 +156,11 @@ class TokenDataset(torch.utils.data.Dataset):
 
 
 @torch.no_grad()
-def tokenize_batch(vq_img, vq_seg, images: torch.Tensor, segmentations: torch.Tensor):
+def tokenize_batch(vq_img, vq_seg, images: torch.Tensor, segmentations):
     """Frozen-VQ encode of one batch: images [B,3,H,W] and segmentation maps [B,C_seg,h,w] -> (img_tokens [B, (H/16)^2],
-    seg_tokens [B, (h/16)^2]) on the MI355X encoder / VQ kernels (BASELINE config 5's first stage)."""
+    seg_tokens [B, (h/16)^2]) on the MI355X encoder / VQ kernels (BASELINE config 5's first stage).  ``segmentations`` is the dense map or
+    a ``mas_hip.seglabels.SegLabels`` (4 label bytes per pixel instead of 636: the one-hot map is then written once, on the device, in the
+    layout the encoder's first convolution reads) -- the tokens are the same."""
     return vq_img.encode_to_indices(images), vq_seg.encode_to_indices(segmentations)
 
 

@@ -540,6 +540,29 @@ int mas_seg_loss_labels_bwd(const void* x, int x_dtype, int x_layout, const unsi
                             int value_channels, const float* pos_weight, int N, int H, int W, int mse_on, const float* grad, void* dx,
                             void* stream);
 
+/* mas_seg_classify, mas_seg_agreement (additions under ABI 10): VQ-SEG logits BACK to the label planes above, and the integer counts that
+ *   pixel accuracy and per-class IoU are made of.  planes / groups / n_groups / value_channels / C as for mas_seg_expand.
+ *   mas_seg_classify: x = logits [N, C, H, W], fp32 or bf16, dense MAS_SEG_NCHW or MAS_SEG_NHWC, element alignment only -> planes uint8
+ *     [N, P, H, W].  tau: HOST array of P fp32 thresholds ON THE LOGIT, tau = log(t / (1 - t)) for a probability t, -INFINITY for none
+ *     (NaN: MAS_EINVAL).  Class plane g: m = the largest logit of channels base_g .. base_g + groups[g] - 1, a = the FIRST channel that
+ *     holds it (torch.argmax's rule); byte = m > tau[g] ? a - base_g + 1 : 0.  Value plane: byte = x > tau ? 1 : 0.  This is the rule of
+ *     reference log_utils.py:55-67 (argmax one-hot, times `sigmoid > 0.2` for face and edges: tau = {-inf, -inf, log 0.25, log 0.25}).
+ *     Logits are compared as fp32 (bf16 widens exactly): the bytes are exact for every finite and infinite input; with a NaN in a group
+ *     the byte is unspecified but within 0 .. groups[g].  x is read once and nothing of its size is held; 16-byte loads where x is 16-byte
+ *     aligned, planes 8-byte aligned and H W a multiple of the unit (NCHW) or always, with head and tail (NHWC); 64-bit offsets.
+ *   mas_seg_agreement: pred, target = two plane tensors of one layout -> counts, device int64 [3 C + P + 1], ADDED to what it holds:
+ *     counts[0 .. C - 1] = inter, [C .. 2 C - 1] = pred, [2 C .. 3 C - 1] = target, per channel: for the class channel base_g + v - 1 the
+ *     pixels whose pred byte / target byte / both equal v, for a value channel the pixels whose byte is > 0 (a target edge value of 2
+ *     counts as set); counts[3 C + k] = the pixels where plane k of the two says the same (class planes: equal bytes after bytes above
+ *     groups[k] became 0; value planes: equal `> 0`); counts[3 C + P] += N H W.  A byte addresses a counter only after 1 <= v <= groups[g].
+ *     Integer sums only (LDS histograms, then 64-bit integer atomics): exact, and independent of any order.  counts 8-byte aligned.
+ *   Both: no host synchronisation (they capture into a graph), grids from the shape and the CU count.  Null arguments: MAS_EINVAL.  More
+ *     than MAS_SEG_MAX_PLANES planes, a group above 255, H W > 2^30, more than 4e18 logits, N H W > 2^32 (agreement): MAS_EUNSUPPORTED. */
+int mas_seg_classify(const void* x, int x_dtype, int x_layout, const int* groups, int n_groups, int value_channels, const float* tau,
+                     int N, int H, int W, unsigned char* planes, void* stream);
+int mas_seg_agreement(const unsigned char* pred, const unsigned char* target, const int* groups, int n_groups, int value_channels,
+                      int N, int H, int W, long long* counts, void* stream);
+
 /* mas_layernorm_pair_* (ABI v9): the sandwich LayerNorm + residual of one sub-block and the pre-LayerNorm of the next as ONE pass,
  *   xnew = residual + LN1(h),  y2 = LN2(xnew)      (reference models/transformer.py:201-203 + :205, and :207-209 + :197 of the next layer
  *   or the final LayerNorm :264) -- the row stays in registers between the two: 12 B per element instead of 16, bit for bit the values

@@ -183,6 +183,8 @@ _SIGNATURES = {
     "mas_seg_loss_labels_blocks": (_i, [_p, _i, _i, _i, _i, _i, _i, _i]),
     "mas_seg_loss_labels_fwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _i, _p]),
     "mas_seg_loss_labels_bwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "mas_seg_classify": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p]),
+    "mas_seg_agreement": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "mas_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "mas_layernorm_bwd_workspace": (_sz, [_i, _i]),
     "mas_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),

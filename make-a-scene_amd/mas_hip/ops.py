@@ -2359,3 +2359,47 @@ def seg_loss_labels(prediction: torch.Tensor, labels, pos_weight: torch.Tensor, 
     if return_terms:
         return loss, {"bce_mean": terms[0], "mse_mean": terms[1]}
     return loss
+
+
+# --------------------------------------------------------------------------- #
+# VQ-SEG logits back to label planes, and the counts of pixel accuracy / IoU (seg_classify.hip)
+# --------------------------------------------------------------------------- #
+def seg_classify(prediction: torch.Tensor, layout=None, thresholds=None) -> SegLabels:
+    """VQ-SEG logits ``[N, C, H, W]`` -> ``SegLabels`` by the reference Visualizer's rule (log_utils.py:55-67) as one kernel
+    (``mas_seg_classify``): per class plane the FIRST channel with the largest logit (``torch.argmax``'s rule), 0 where that logit is not
+    above the plane's threshold; per value plane ``logit > threshold``.  ``thresholds``: ``P`` probabilities in (0, 1) or ``None`` (no
+    gate), or one float for every plane; the default, ``(None, None, 0.2, 0.2)``, exists for the reference layout only.  The comparison is
+    made on the logit against ``float32(log(t / (1 - t)))``: exact, no sigmoid.  fp32 or bf16, dense NCHW or channels_last memory read in
+    place, once; anything else (a slice) is made dense first.  Nothing of the logits' size is allocated and nothing synchronises."""
+    from .seglabels import SegLayout, _check_logits, logit_thresholds
+    layout = layout if layout is not None else SegLayout()
+    taus = logit_thresholds(layout, thresholds, "seg_classify")
+    _check_logits(prediction, layout, "seg_classify")
+    _require_cuda(prediction, "seg_classify")
+    x, xl = _seg_dense(prediction.detach())
+    n, _, h, w = x.shape
+    groups = (C.c_int * max(len(layout.groups), 1))(*layout.groups)
+    tau = (C.c_float * layout.planes)(*taus)
+    planes = torch.empty((n, layout.planes, h, w), dtype=torch.uint8, device=x.device)
+    check(lib().mas_seg_classify(_ptr(x), _DT[x.dtype], xl, groups, len(layout.groups), layout.value_channels, tau, n, h, w, _ptr(planes),
+                                 _stream()), "seg_classify")
+    return SegLabels(planes, layout)
+
+
+def seg_agreement(pred, target, out=None):
+    """Counts for pixel accuracy and per-class IoU between two ``SegLabels`` of one layout and shape (``mas_seg_agreement``) ->
+    ``mas_hip.seglabels.SegAgreement``.  ``out``: a ``SegAgreement`` of the same layout on the same device that the counts are ADDED to
+    (and which is returned); without it a zeroed one is made.  Integer counting: exact, the same in any order; no host synchronisation."""
+    from .seglabels import SegAgreement
+    p_planes, groups, ng, nv = _seg_layout_args(pred, "seg_agreement")
+    t_planes, _, _, _ = _seg_layout_args(target, "seg_agreement")
+    if pred.layout != target.layout or tuple(p_planes.shape) != tuple(t_planes.shape) or p_planes.device != t_planes.device:
+        raise ValueError(f"seg_agreement: prediction {tuple(p_planes.shape)} ({pred.layout}, {p_planes.device}) and target "
+                         f"{tuple(t_planes.shape)} ({target.layout}, {t_planes.device}) differ")
+    if out is None:
+        out = SegAgreement(pred.layout, device=p_planes.device)
+    elif not isinstance(out, SegAgreement) or out.layout != pred.layout or out.counts.device != p_planes.device:
+        raise ValueError("seg_agreement: out must be a SegAgreement of the labels' layout on their device")
+    b, _, h, w = p_planes.shape
+    check(lib().mas_seg_agreement(_ptr(p_planes), _ptr(t_planes), groups, ng, nv, b, h, w, _ptr(out.counts), _stream()), "seg_agreement")
+    return out

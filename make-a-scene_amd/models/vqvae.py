@@ -53,6 +53,26 @@ class VQBASE(nn.Module):
         quant_b = self.quantize.get_codebook_entry(code_b.reshape(b, -1), (b, side, side, self.quantize.codebook_dim))
         return self.decode(quant_b)
 
+    @torch.no_grad()
+    def decode_to_labels(self, code_b, layout=None, thresholds=None):
+        """VQ-SEG tokens -> the scene as ``mas_hip.seglabels.SegLabels``: ``decode_code`` and then the reference Visualizer's reading of the
+        logits (log_utils.py:55-67; ``ops.seg_classify``).  ``layout`` / ``thresholds`` as ``SegLabels.from_logits``.  Call in ``eval()``
+        mode, like ``encode_to_indices``: tokens -> scene -> tokens closes with it."""
+        if self.training:
+            raise RuntimeError("decode_to_labels: decode with the frozen model in eval() mode")
+        from mas_hip.seglabels import SegLabels
+        return SegLabels.from_logits(self.decode_code(code_b), layout, thresholds)
+
+    @torch.no_grad()
+    def reconstruct_labels(self, x, layout=None, thresholds=None):
+        """a segmentation map (``SegLabels`` or dense) -> its reconstruction as ``SegLabels``: ``forward``'s logits read by
+        ``SegLabels.from_logits``.  ``eval()`` mode only."""
+        if self.training:
+            raise RuntimeError("reconstruct_labels: reconstruct with the frozen model in eval() mode")
+        from mas_hip.seglabels import SegLabels
+        quant, _ = self.encode(x)
+        return SegLabels.from_logits(self.decode(quant), layout, thresholds)
+
     def forward(self, input):
         quant, diff = self.encode(input)
         dec = self.decode(quant)

@@ -19,17 +19,10 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: F401,E402  -- must come first: PyTorch-ROCm bundles its own libamdhip64; loading ours before it leaves torch without GPUs
 
+from . import _header  # noqa: E402
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MAS_HIP_LIB") or os.path.join(_HERE, "libmas_hip.so")   # env override: A/B kernel experiments
-
-F32, BF16 = 0, 1
-ACT_NONE, ACT_AFFINE, ACT_AFFINE_SILU = 0, 1, 2
-ABI_VERSION = 10
-WLAYOUT_K64, WLAYOUT_K32, WLAYOUT_UP2 = 0, 1, 2
-ATTN_DECODE_MAX_SPLITS = 32   # MAS_ATTN_DECODE_MAX_SPLITS
-CE_NONE, CE_MEAN, CE_SUM = 0, 1, 2   # MAS_CE_*
-SEG_NCHW, SEG_NHWC, SEG_U8 = 0, 1, 2   # MAS_SEG_*: layout codes; the uint8 target dtype beside F32 / BF16
-SEG_LABELS_TILE, SEG_MAX_PLANES = 256, 8   # MAS_SEG_LABELS_TILE: pixels of one tile of the label-plane kernels; MAS_SEG_MAX_PLANES
 
 
 class ConvDesc(C.Structure):
@@ -90,141 +83,13 @@ class ObjPlan(C.Structure):
                [(n, C.c_int32) for n in ("n_cells", "n_images", "n_canvas", "H", "W", "pad_")]
 
 
-_p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-_SIGNATURES = {
-    "mas_abi_version": (C.c_int, []),
-    "mas_last_error": (C.c_char_p, []),
-    "mas_last_kernel": (C.c_char_p, []),
-    "mas_packed_weight_elems": (_sz, [_i, _i, _i]),
-    "mas_packed_weight_elems_up2": (_sz, [_i, _i]),
-    "mas_pack_conv_weight": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    "mas_conv_weight_layout": (_i, [C.POINTER(ConvDesc)]),
-    "mas_pack_conv_weight_layout": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "mas_pack_batch_blocks": (_i, [_i, _i, _i, _i, _i, _i]),
-    "mas_adam_blocks": (_i, [C.c_longlong]),
-    "mas_adam_multi": (_i, [_p, _i, _i, _f, _f, _f, _f, _f, C.c_double, C.c_double, _p]),
-    "mas_grad_sqnorm_multi": (_i, [_p, _i, _i, _p, _p]),
-    "mas_grad_clip_coef": (_i, [_p, _i, _p, _i, _f, _p, _p]),
-    "mas_adam_multi_ex": (_i, [_p, _i, _i, _f, _f, _f, _f, _f, C.c_double, C.c_double, _p, _i, _p]),
-    "mas_grad_scale_multi": (_i, [_p, _i, _i, _p, _p]),
-    "mas_pack_conv_weight_batch": (_i, [_p, _i, _i, _p]),
-    "mas_pack_tile_blocks": (_i, [_i, _i, _i]),
-    "mas_pack_conv_weight_tiles": (_i, [_p, _i, _i, _i, _p]),
-    "mas_gn_stats_workspace": (_sz, [_i, _i]),
-    "mas_gn_stats": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _sz, _p]),
-    "mas_gn_bwd_workspace": (_sz, [_i, _i]),
-    "mas_gn_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "mas_gn_bwd_3pass": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
-    "mas_gn_act": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
-    "mas_gn_small_supported": (_i, [_i, _i, _i, _i]),
-    "mas_gn_stats_act": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _p]),
-    "mas_conv_fwd": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p]),
-    "mas_conv_stat_rows": (_i, [C.POINTER(ConvDesc)]),
-    "mas_conv_fwd_stats": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _p]),
-    "mas_gn_stats_from_partials": (_i, [_p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
-    "mas_conv_wgrad": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p]),
-    "mas_wgrad_commit": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "mas_conv_s2_dgrad_supported": (_i, [C.POINTER(ConvDesc)]),
-    "mas_conv_s2_dgrad": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p]),
-    "mas_conv_up2_supported": (_i, [C.POINTER(ConvDesc)]),
-    "mas_conv_up2_dgrad_supported": (_i, [C.POINTER(ConvDesc)]),
-    "mas_conv_up2_dgrad": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p]),
-    "mas_conv_up2_wgrad_splits": (_i, [C.POINTER(ConvDesc)]),
-    "mas_conv_up2_wgrad_partial": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p, _p]),
-    "mas_wgrad_reduce_up2": (_i, [_p, _p, _i, _p, _p, _i, _i, _p]),
-    "mas_conv_wgrad_splits": (_i, [C.POINTER(ConvDesc)]),
-    "mas_conv_wgrad_partial": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p]),
-    "mas_wgrad_reduce": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _p]),
-    "mas_vq_workspace": (_sz, [_i, _i]),
-    "mas_vq_argmin_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
-    "mas_vq_bwd": (_i, [_p, _p, _p, _p, _p, _f, _i, _i, _i, _p, _p, _p]),
-    "mas_attn_causal_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, _f, _p]),
-    "mas_attn_causal_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "mas_attn_causal_fwd_drop": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, _f, _f, _p,
-                                      _p]),
-    "mas_attn_causal_bwd_drop": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p, _p]),
-    "mas_attn_dropout_mask": (_i, [_p, _i, _i, _i, _f, _p, _p]),
-    "mas_dropout_apply": (_i, [_p, _p, C.c_longlong, _i, _f, _p, _p]),
-    "mas_spatial_attn_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
-    "mas_spatial_attn_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "mas_spatial_attn_flash_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
-    "mas_spatial_attn_flash_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "mas_attn_decode": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f, _p]),
-    "mas_attn_decode_dev": (_i, [_p, _p, _p, C.c_longlong, _p, _p, _i, C.c_longlong, _i, _p, C.c_longlong, _i, _i, _i, _i, _p, _f, _p]),
-    "mas_decode_embed": (_i, [_p, C.c_longlong, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p]),
-    "mas_sample_tokens": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong, _p,
-                               C.c_longlong, _p]),
-    "mas_sample_tokens_topp": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong,
-                                    _p, C.c_longlong, _p]),
-    "mas_sample_tokens_prompt": (_i, [_p, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, C.c_longlong, _p, C.c_longlong,
-                                      _p, C.c_longlong, _p, C.c_longlong, _p]),
-    "mas_decode_advance": (_i, [_p, _i, _p]),
-    "mas_attn_decode_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_longlong, C.c_longlong, C.c_longlong,
-                                   C.c_longlong, _f, _i, _p, _sz, _p]),
-    "mas_attn_decode_split_dev": (_i, [_p, _p, _p, C.c_longlong, _p, _p, _i, C.c_longlong, _i, _p, C.c_longlong, _i, _i, _i, _i, _p, _f,
-                                       _i, _p, _sz, _p]),
-    "mas_upsample2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    "mas_sumpool2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    "mas_zero_stuff2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "mas_space_to_depth2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "mas_gelu_tanh_fwd": (_i, [_p, _p, _i, C.c_longlong, _p]),
-    "mas_gelu_tanh_bwd": (_i, [_p, _p, _p, _i, C.c_longlong, _p]),
-    "mas_gelu_tanh_bwd_colsum_workspace": (_sz, [_i, _i]),
-    "mas_gelu_tanh_bwd_colsum": (_i, [_p, _p, _p, _p, _i, C.c_longlong, _i, _p, _sz, _p]),
-    "mas_token_ce_fwd": (_i, [_p, _i, C.c_longlong, _i, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, _f, _p, _p, _p]),
-    "mas_token_ce_reduce": (_i, [_p, _p, C.c_longlong, C.c_longlong, _i, _p, _p]),
-    "mas_token_ce_bwd": (_i, [_p, _i, C.c_longlong, _i, C.c_longlong, C.c_longlong, C.c_longlong, _p, C.c_longlong, _f, _p, _p, _p, _i, _p,
-                              _p]),
-    "mas_seg_loss_blocks": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "mas_seg_loss_fwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _i, _p]),
-    "mas_seg_loss_reduce": (_i, [_p, _i, C.c_longlong, _i, _p, _p]),
-    "mas_seg_loss_bwd": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "mas_seg_expand": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p]),
-    "mas_seg_loss_labels_blocks": (_i, [_p, _i, _i, _i, _i, _i, _i, _i]),
-    "mas_seg_loss_labels_fwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _i, _p]),
-    "mas_seg_loss_labels_bwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p]),
-    "mas_seg_classify": (_i, [_p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _p, _p]),
-    "mas_seg_agreement": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
-    "mas_layernorm_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
-    "mas_layernorm_bwd_workspace": (_sz, [_i, _i]),
-    "mas_layernorm_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
-    "mas_layernorm_bwd_add": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
-    "mas_bn_workspace": (_sz, [_i, _i]),
-    "mas_bn_partial_sums": (_i, [_p, _p, _p, _i, _i, _p, _p, _sz, _p]),
-    "mas_bn_finalize": (_i, [_p, _p, _p, _f, _f, _p, _p, _p, _p, _i, _p]),
-    "mas_bn_apply": (_i, [_p, _p, _p, _i, _i, _p]),
-    "mas_bn_bwd_apply": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "mas_bn_partial_sums_act": (_i, [_p, _p, _p, _p, _f, _i, _i, _i, _p, _p, _sz, _p]),
-    "mas_bn_apply_act": (_i, [_p, _p, _p, _f, _i, _i, _i, _p]),
-    "mas_bn_bwd_apply_act": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _i, _p]),
-    "mas_layernorm_bwd_colsum": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
-    "mas_layernorm_pair_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
-    "mas_colsum_workspace": (_sz, [_i, _i]),
-    "mas_colsum": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
-    "mas_face_crop_fwd": (_i, [C.POINTER(FaceImage), C.POINTER(FaceImage), C.POINTER(FaceRow), _i, _p, _i, _p]),
-    "mas_face_crop_bwd": (_i, [_p, C.POINTER(FaceRow), _i, C.POINTER(FaceImage), _p]),
-    "mas_face_stem_fwd": (_i, [_p, _p, _p, _i, _i, _p]),
-    "mas_face_stem_dgrad": (_i, [_p, _p, _p, _i, _i, _p]),
-    "mas_face_bn_fold": (_i, [_p, _i, _p, _p]),
-    "mas_face_pool_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "mas_face_pool_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "mas_face_join_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
-    "mas_face_join_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
-    "mas_face_relu_bn_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "mas_face_subsample2x": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    "mas_face_l1_workspace": (_i, [C.POINTER(FaceFeats)]),
-    "mas_face_l1_fwd": (_i, [C.POINTER(FaceFeats), _p, _p, _p]),
-    "mas_face_l1_bwd": (_i, [C.POINTER(FaceFeats), _i, _i, _p, C.POINTER(_p), _p]),
-    "mas_obj_canvas_fwd": (_i, [C.POINTER(FaceImage), C.POINTER(FaceImage), C.POINTER(ObjPlan), _p, _p, _p, _i, _p]),
-    "mas_obj_canvas_bwd": (_i, [_p, _i, C.POINTER(ObjPlan), _p, C.POINTER(FaceImage), _p]),
-    "mas_obj_relu_fwd": (_i, [_p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p]),
-    "mas_obj_relu_bwd": (_i, [_p, _p, _p, C.c_longlong, _i, _p]),
-    "mas_obj_pool_fwd": (_i, [_p, _p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p]),
-    "mas_obj_pool_bwd": (_i, [_p, _p, _p, _p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p]),
-    "mas_obj_head_fwd": (_i, [_p, _p, C.POINTER(ObjPlan), _i, _i, _i, _i, _p, _p]),
-    "mas_obj_finalize": (_i, [_p, C.POINTER(ObjPlan), _p, _p]),
-    "mas_obj_head_bwd": (_i, [_p, _p, C.POINTER(ObjPlan), _i, _i, _i, _p, _p, _p]),
-}
+# Every prototype and every integer constant of include/mas_hip.h, read from the header itself (_header.py says what it can read and
+# raises on the rest).  _SIGNATURES: {name: (restype, [argtypes])} in header order; MAS_X is this module's X (F32, BF16, ACT_*,
+# WLAYOUT_*, CE_*, SEG_*, ABI_VERSION, ATTN_DECODE_MAX_SPLITS, FACE_SIZE, OBJ_ALIGN, ...).  The structs above are the ones the host
+# fills in; the five it hands over by reference are named here, and a pointer to any other struct is a device table: c_void_p.
+_SIGNATURES, constants = _header.load({"MasConvDesc": ConvDesc, "MasFaceImage": FaceImage, "MasFaceRow": FaceRow, "MasFaceFeats": FaceFeats,
+                                       "MasObjPlan": ObjPlan})
+globals().update((name[len("MAS_"):], value) for name, value in constants.items())
 EXPORTS = tuple(_SIGNATURES)
 
 _lib = None
@@ -243,12 +108,13 @@ def lib():
                         "(hipcc --offload-arch=gfx950); there is no PyTorch/CPU fallback for this path")
                 L = C.CDLL(LIB_PATH)
                 for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name, None)
-                    if fn is None:
-                        continue          # optional symbol of a later ABI revision; callers check
+                    try:
+                        fn = getattr(L, name)
+                    except AttributeError:
+                        raise RuntimeError(f"{LIB_PATH} does not export {name}, which include/mas_hip.h declares: rebuild it") from None
                     fn.restype, fn.argtypes = res, args
-                if L.mas_abi_version() != ABI_VERSION:
-                    raise RuntimeError(f"libmas_hip.so ABI {L.mas_abi_version()} != binding {ABI_VERSION}")
+                if L.mas_abi_version() != constants["MAS_ABI_VERSION"]:
+                    raise RuntimeError(f"libmas_hip.so ABI {L.mas_abi_version()} != binding {constants['MAS_ABI_VERSION']}")
                 _lib = L
     return _lib
 
@@ -257,3 +123,31 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = lib().mas_last_error()
         raise RuntimeError(f"libmas_hip {what} failed (code {rc}): {msg.decode() if msg else ''}")
+
+
+# What every caller of the library needs beside lib() and check(): dtype codes, pointers, the current stream.
+_DT = {torch.float32: constants["MAS_F32"], torch.bfloat16: constants["MAS_BF16"]}
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _require_cuda(t, what: str):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: the MI355X path needs a GPU tensor (no CPU fallback); got device {t.device}")
+
+
+def _image(t, who: str) -> FaceImage:
+    """``MasFaceImage`` of a [N, 3, H, W] tensor of any strides; ``who``: the loss the error messages name"""
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise ValueError(f"{who}: images must be [N, 3, H, W], got {tuple(t.shape)}")
+    if t.dtype not in _DT:
+        raise TypeError(f"{who}: images must be float32 or bfloat16, got {t.dtype}")
+    n, c, h, w = t.shape
+    sn, sc, sh, sw = t.stride()
+    return FaceImage(t.data_ptr(), _DT[t.dtype], n, c, h, w, 0, sn, sc, sh, sw)

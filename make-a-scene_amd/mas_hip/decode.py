@@ -7,8 +7,8 @@ from typing import Optional
 
 import torch
 
-from . import ATTN_DECODE_MAX_SPLITS, check, lib
-from .ops import _ATTN_HEAD_DIMS, _DT, _ptr, _require_cuda, _stream
+from . import ATTN_DECODE_MAX_SPLITS, _DT, _ptr, _require_cuda, _stream, check, lib
+from .ops import _ATTN_HEAD_DIMS
 
 GREEDY, SAMPLE, FORCED = 0, 1, 2
 AUTO_MAX_SPLITS = 8   # resolve_kv_splits("auto") never goes beyond: more splits measured slower

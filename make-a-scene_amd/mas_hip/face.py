@@ -11,14 +11,13 @@ import ctypes as C
 
 import torch
 
-from . import ACT_NONE, FaceBnItem, FaceFeats, FaceImage, FaceRow, check, lib
+from . import ACT_NONE, FACE_SIZE, FaceBnItem, FaceFeats, FaceRow, _DT, _image, _ptr as _p, _require_cuda, _stream, check, lib
 from . import ops
 
-FACE = 254            # CenterCrop(254)
+FACE = FACE_SIZE      # CenterCrop(254): MAS_FACE_SIZE of include/mas_hip.h
 RESIZE = 256          # Resize(256): the short side
 MAX_ROWS = 6          # faces[:6] (reference face_loss.py:140)
 ALPHAS = (0.1, 0.25 * 0.01, 0.25 * 0.1, 0.25 * 0.2, 0.25 * 0.02)
-_DT = {torch.float32: 0, torch.bfloat16: 1}
 
 
 # --------------------------------------------------------------------------- #
@@ -75,16 +74,6 @@ def plan(bboxes, n_images: int):
     return len(faces), rows
 
 
-def _image(t: torch.Tensor) -> FaceImage:
-    if t.dim() != 4 or t.shape[1] != 3:
-        raise ValueError(f"FaceLoss: images must be [N, 3, H, W], got {tuple(t.shape)}")
-    if t.dtype not in _DT:
-        raise TypeError(f"FaceLoss: images must be float32 or bfloat16, got {t.dtype}")
-    n, c, h, w = t.shape
-    sn, sc, sh, sw = t.stride()
-    return FaceImage(t.data_ptr(), _DT[t.dtype], n, c, h, w, 0, sn, sc, sh, sw)
-
-
 def _rows_array(rows):
     arr = (FaceRow * len(rows))()
     for i, r in enumerate(rows):
@@ -95,8 +84,8 @@ def _rows_array(rows):
 def crop_faces(img, rec, rows, dtype):
     """[R, 3, 254, 254] (channels_last, ``dtype``): CenterCrop(Resize(crop(.))) of every row, one launch."""
     out = torch.empty((len(rows), 3, FACE, FACE), dtype=dtype, device=img.device, memory_format=torch.channels_last)
-    gi, gr = _image(img), _image(rec)
-    check(lib().mas_face_crop_fwd(C.byref(gi), C.byref(gr), _rows_array(rows), len(rows), C.c_void_p(out.data_ptr()), _DT[dtype], ops._stream()),
+    gi, gr = _image(img, "FaceLoss"), _image(rec, "FaceLoss")
+    check(lib().mas_face_crop_fwd(C.byref(gi), C.byref(gr), _rows_array(rows), len(rows), C.c_void_p(out.data_ptr()), _DT[dtype], _stream()),
           "face_crop_fwd")
     return out
 
@@ -104,8 +93,8 @@ def crop_faces(img, rec, rows, dtype):
 def crop_faces_bwd(dfaces: torch.Tensor, rows, like: torch.Tensor):
     """d ``like`` (its dtype and layout) from the fp32 NHWC gradients of ``rows`` (all taken as rows of ``like``), one launch."""
     drec = torch.empty_like(like)
-    g = _image(drec)
-    check(lib().mas_face_crop_bwd(C.c_void_p(dfaces.data_ptr()), _rows_array(rows), len(rows), C.byref(g), ops._stream()), "face_crop_bwd")
+    g = _image(drec, "FaceLoss")
+    check(lib().mas_face_crop_bwd(C.c_void_p(dfaces.data_ptr()), _rows_array(rows), len(rows), C.byref(g), _stream()), "face_crop_bwd")
     return drec
 
 
@@ -181,16 +170,12 @@ def fold_bn(mod):
         _bn_tables.clear()                      # one live module layout at a time is the common case; stale addresses are never reused
         _bn_tables[key] = table
     ss = torch.empty((off, 2), dtype=torch.float32, device=dev)
-    check(lib().mas_face_bn_fold(C.c_void_p(table.data_ptr()), len(bns), C.c_void_p(ss.data_ptr()), ops._stream()), "face_bn_fold")
+    check(lib().mas_face_bn_fold(C.c_void_p(table.data_ptr()), len(bns), C.c_void_p(ss.data_ptr()), _stream()), "face_bn_fold")
     return ss, offs
 
 
 def _ssp(ss, offs, bn):
     return C.c_void_p(ss.data_ptr() + 8 * offs[id(bn)]) if bn is not None else None
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _conv1x1(x, w, cout, residual=None, transpose=False):
@@ -206,14 +191,14 @@ def _conv3x3(x, w, cout, transpose=False):
 def _bn_relu(y, ss, offs, bn):
     n, c, h, w = y.shape
     out = torch.empty_like(y)
-    check(lib().mas_bn_apply_act(_p(y), _ssp(ss, offs, bn), _p(out), 0.0, _DT[y.dtype], n * h * w, c, ops._stream()), "bn_apply_act")
+    check(lib().mas_bn_apply_act(_p(y), _ssp(ss, offs, bn), _p(out), 0.0, _DT[y.dtype], n * h * w, c, _stream()), "bn_apply_act")
     return out
 
 
 def _subsample(x):
     n, c, h, w = x.shape
     y = torch.empty((n, c, (h + 1) // 2, (w + 1) // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-    check(lib().mas_face_subsample2x(_p(x), _p(y), _DT[x.dtype], n, h, w, c, ops._stream()), "face_subsample2x")
+    check(lib().mas_face_subsample2x(_p(x), _p(y), _DT[x.dtype], n, h, w, c, _stream()), "face_subsample2x")
     return y
 
 
@@ -231,7 +216,7 @@ def _block_fwd(blk, x, ss, offs):
     out = torch.empty_like(y3)
     n, c, h, w = y3.shape
     check(lib().mas_face_join_fwd(_p(y3), _ssp(ss, offs, blk.bn3), _p(r), _ssp(ss, offs, bnr), _p(out), _DT[out.dtype], n * h * w, c,
-                                  ops._stream()), "face_join_fwd")
+                                  _stream()), "face_join_fwd")
     return out, (a1, a2)
 
 
@@ -245,13 +230,13 @@ def _block_bwd(blk, x_shape, dout, dadd, out, a1, a2, ss, offs):
     dr = torch.empty_like(out)
     bnr = blk.downsample[1] if blk.downsample is not None else None
     check(lib().mas_face_join_bwd(_p(dout), _p(dadd), _p(out), _ssp(ss, offs, blk.bn3), _ssp(ss, offs, bnr), _p(dy3), _p(dr), dt, m, c,
-                                  ops._stream()), "face_join_bwd")
+                                  _stream()), "face_join_bwd")
     da2 = _conv1x1(dy3, blk.conv3.weight, planes, transpose=True)
     dy2 = torch.empty_like(da2)
-    check(lib().mas_face_relu_bn_bwd(_p(da2), _p(a2), _ssp(ss, offs, blk.bn2), _p(dy2), dt, m, planes, ops._stream()), "face_relu_bn_bwd")
+    check(lib().mas_face_relu_bn_bwd(_p(da2), _p(a2), _ssp(ss, offs, blk.bn2), _p(dy2), dt, m, planes, _stream()), "face_relu_bn_bwd")
     da1 = _conv3x3(dy2, blk.conv2.weight, planes, transpose=True)
     dy1 = torch.empty_like(da1)
-    check(lib().mas_face_relu_bn_bwd(_p(da1), _p(a1), _ssp(ss, offs, blk.bn1), _p(dy1), dt, m, planes, ops._stream()), "face_relu_bn_bwd")
+    check(lib().mas_face_relu_bn_bwd(_p(da1), _p(a1), _ssp(ss, offs, blk.bn1), _p(dy1), dt, m, planes, _stream()), "face_relu_bn_bwd")
     cin, hin, win = x_shape
     dres = _conv1x1(dr, blk.downsample[0].weight, cin, transpose=True) if blk.downsample is not None else dr
     dxs = _conv1x1(dy1, blk.conv1.weight, cin, residual=dres, transpose=True)        # the shortcut's gradient in the epilogue
@@ -266,10 +251,10 @@ def network_forward(mod, faces, ss, offs):
     dt = faces.dtype
     y0 = torch.empty((r, 64, 127, 127), dtype=dt, device=faces.device, memory_format=torch.channels_last)
     w0 = mod.conv1.weight.detach().float().contiguous()
-    check(lib().mas_face_stem_fwd(_p(faces), _p(w0), _p(y0), _DT[dt], r, ops._stream()), "face_stem_fwd")
+    check(lib().mas_face_stem_fwd(_p(faces), _p(w0), _p(y0), _DT[dt], r, _stream()), "face_stem_fwd")
     z = torch.empty((r, 64, 63, 63), dtype=dt, device=faces.device, memory_format=torch.channels_last)
     idx = torch.empty(r * 63 * 63 * 64, dtype=torch.uint8, device=faces.device)
-    check(lib().mas_face_pool_fwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(z), _p(idx), _DT[dt], r, 127, 127, 64, ops._stream()), "face_pool_fwd")
+    check(lib().mas_face_pool_fwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(z), _p(idx), _DT[dt], r, 127, 127, 64, _stream()), "face_pool_fwd")
     feats, saved, h = [y0], [], z
     for li, blk in blocks_of(mod):
         shape_in = tuple(h.shape[1:])
@@ -298,7 +283,7 @@ def l1_forward(feats, half):
         check(nws, "face_l1_workspace")
     ws = torch.empty(max(nws, 1), dtype=torch.float32, device=feats[0].device)
     out = torch.empty(6, dtype=torch.float32, device=feats[0].device)
-    check(lib().mas_face_l1_fwd(C.byref(f), _p(ws), _p(out), ops._stream()), "face_l1_fwd")
+    check(lib().mas_face_l1_fwd(C.byref(f), _p(ws), _p(out), _stream()), "face_l1_fwd")
     return out
 
 
@@ -334,7 +319,7 @@ class _FaceLoss(torch.autograd.Function):
         seeds = [torch.empty((nb,) + tuple(f.shape[1:]), dtype=f.dtype, device=f.device, memory_format=torch.channels_last) for f in feats]
         f = _feats_table(feats, ctx.half)
         sp = (C.c_void_p * 5)(*[s.data_ptr() for s in seeds])
-        check(lib().mas_face_l1_bwd(C.byref(f), row0, nb, _p(dl6), sp, ops._stream()), "face_l1_bwd")
+        check(lib().mas_face_l1_bwd(C.byref(f), row0, nb, _p(dl6), sp, _stream()), "face_l1_bwd")
         blocks = blocks_of(mod)
         d = None
         for k in range(len(blocks) - 1, -1, -1):
@@ -346,10 +331,10 @@ class _FaceLoss(torch.autograd.Function):
         dy0 = torch.empty_like(y0)
         idx = ctx.idx[row0 * 63 * 63 * 64:]
         dt = _DT[y0.dtype]
-        check(lib().mas_face_pool_bwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(d), _p(idx), _p(seeds[0]), _p(dy0), dt, nb, 127, 127, 64, ops._stream()),
+        check(lib().mas_face_pool_bwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(d), _p(idx), _p(seeds[0]), _p(dy0), dt, nb, 127, 127, 64, _stream()),
               "face_pool_bwd")
         dfaces = torch.empty((nb, FACE, FACE, 3), dtype=torch.float32, device=y0.device)
-        check(lib().mas_face_stem_dgrad(_p(dy0), _p(ctx.w0), _p(dfaces), dt, nb, ops._stream()), "face_stem_dgrad")
+        check(lib().mas_face_stem_dgrad(_p(dy0), _p(ctx.w0), _p(dfaces), dt, nb, _stream()), "face_stem_dgrad")
         drec = crop_faces_bwd(dfaces, ctx.rows[row0:], rec)
         return None, drec, None, None, None, None
 
@@ -357,8 +342,8 @@ class _FaceLoss(torch.autograd.Function):
 def face_loss(mod, img, rec, bbox, dtype=None):
     """The evaluation-mode FaceLoss on the HIP path: -> [6] fp32 (five weighted feature distances and the loss), or None without
     faces (nothing launched)."""
-    ops._require_cuda(img, "FaceLoss")
-    ops._require_cuda(rec, "FaceLoss")
+    _require_cuda(img, "FaceLoss")
+    _require_cuda(rec, "FaceLoss")
     n, rows = plan(bbox, min(img.shape[0], rec.shape[0]))
     if n == 0:
         return None

@@ -23,18 +23,18 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ACT_NONE, FaceImage, ObjPlan, check, lib
+from . import ACT_NONE, OBJ_ALIGN, OBJ_CANVAS_C, OBJ_MIN_SIDE, ObjPlan, _DT, _image, _ptr as _p, _require_cuda, _stream, check, lib
 from . import ops
 
-ALIGN = 16            # crop origins (and canvas sizes) are multiples of 16: every 2x2 pool window of a valid output stays in one crop
+# ALIGN, MIN_SIDE and CP are the header's MAS_OBJ_ALIGN, MAS_OBJ_MIN_SIDE and MAS_OBJ_CANVAS_C
+ALIGN = OBJ_ALIGN     # crop origins (and canvas sizes) are multiples of 16: every 2x2 pool window of a valid output stays in one crop
 GUTTER = 16           # zeros after every crop: >= 1 zero pixel between crops down to level 4 (16 >> 4)
-MIN_SIDE = 16         # a box with a side under 16 px is skipped (VGG's fourth pool would have no output: the reference raises)
+MIN_SIDE = OBJ_MIN_SIDE   # a box with a side under 16 px is skipped (VGG's fourth pool would have no output: the reference raises)
 CANVAS_W = 1024       # canvas width (wider when a crop needs it)
 CANVAS_H_MAX = 2048   # canvas height before a new canvas starts (taller when a crop needs it)
-CP = 8                # canvas channels: RGB and five zeros (the first convolution's input, one 16-byte bf16 vector)
+CP = OBJ_CANVAS_C     # canvas channels: RGB and five zeros (the first convolution's input, one 16-byte bf16 vector)
 LEVELS = 5
 CHANNELS = (64, 128, 256, 512, 512)
-_DT = {torch.float32: 0, torch.bfloat16: 1}
 
 
 def head_pixels(c: int) -> int:
@@ -165,20 +165,6 @@ def upload(plan: Plan, device):
 # --------------------------------------------------------------------------- #
 # kernel calls
 # --------------------------------------------------------------------------- #
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _image(t: torch.Tensor) -> FaceImage:
-    if t.dim() != 4 or t.shape[1] != 3:
-        raise ValueError(f"ObjectLoss: images must be [N, 3, H, W], got {tuple(t.shape)}")
-    if t.dtype not in _DT:
-        raise TypeError(f"ObjectLoss: images must be float32 or bfloat16, got {t.dtype}")
-    n, c, h, w = t.shape
-    sn, sc, sh, sw = t.stride()
-    return FaceImage(t.data_ptr(), _DT[t.dtype], n, c, h, w, 0, sn, sc, sh, sw)
-
-
 def _nhwc(n, c, h, w, dtype, device):
     return torch.empty((n, c, h, w), dtype=dtype, device=device, memory_format=torch.channels_last)
 
@@ -186,8 +172,8 @@ def _nhwc(n, c, h, w, dtype, device):
 def canvas_fwd(img, rec, p: ObjPlan, shift, scale, dtype):
     """[2 * n_canvas, 8, H, W] (channels_last): the scaled crops of img (first half) and rec (second half), zeros elsewhere"""
     out = _nhwc(2 * p.n_canvas, CP, p.H, p.W, dtype, img.device)
-    gi, gr = _image(img), _image(rec)
-    check(lib().mas_obj_canvas_fwd(C.byref(gi), C.byref(gr), C.byref(p), _p(shift), _p(scale), _p(out), _DT[dtype], ops._stream()),
+    gi, gr = _image(img, "ObjectLoss"), _image(rec, "ObjectLoss")
+    check(lib().mas_obj_canvas_fwd(C.byref(gi), C.byref(gr), C.byref(p), _p(shift), _p(scale), _p(out), _DT[dtype], _stream()),
           "obj_canvas_fwd")
     return out
 
@@ -195,46 +181,46 @@ def canvas_fwd(img, rec, p: ObjPlan, shift, scale, dtype):
 def canvas_bwd(dcanvas, p: ObjPlan, scale, like):
     """d ``like`` (its dtype and strides, written in full) from the rec-side canvas gradient [n_canvas, 8, H, W]"""
     drec = torch.empty_like(like)
-    g = _image(drec)
-    check(lib().mas_obj_canvas_bwd(_p(dcanvas), _DT[dcanvas.dtype], C.byref(p), _p(scale), C.byref(g), ops._stream()), "obj_canvas_bwd")
+    g = _image(drec, "ObjectLoss")
+    check(lib().mas_obj_canvas_bwd(_p(dcanvas), _DT[dcanvas.dtype], C.byref(p), _p(scale), C.byref(g), _stream()), "obj_canvas_bwd")
     return drec
 
 
 def relu_fwd(y, p: ObjPlan, level: int):
     n, c = y.shape[:2]
-    check(lib().mas_obj_relu_fwd(_p(y), C.byref(p), level, n, c, _DT[y.dtype], ops._stream()), "obj_relu_fwd")
+    check(lib().mas_obj_relu_fwd(_p(y), C.byref(p), level, n, c, _DT[y.dtype], _stream()), "obj_relu_fwd")
     return y
 
 
 def relu_bwd(da, a, out=None):
     dy = da if out is None else out
-    check(lib().mas_obj_relu_bwd(_p(da), _p(a), _p(dy), a.numel(), _DT[a.dtype], ops._stream()), "obj_relu_bwd")
+    check(lib().mas_obj_relu_bwd(_p(da), _p(a), _p(dy), a.numel(), _DT[a.dtype], _stream()), "obj_relu_bwd")
     return dy
 
 
 def pool_fwd(x, p: ObjPlan, level: int):
     n, c, h, w = x.shape
     y = _nhwc(n, c, h // 2, w // 2, x.dtype, x.device)
-    check(lib().mas_obj_pool_fwd(_p(x), _p(y), C.byref(p), level, n, c, _DT[x.dtype], ops._stream()), "obj_pool_fwd")
+    check(lib().mas_obj_pool_fwd(_p(x), _p(y), C.byref(p), level, n, c, _DT[x.dtype], _stream()), "obj_pool_fwd")
     return y
 
 
 def pool_bwd(a, seed, dz, p: ObjPlan, level: int):
     n, c = a.shape[:2]
     dy = torch.empty_like(a)
-    check(lib().mas_obj_pool_bwd(_p(a), _p(seed), _p(dz), _p(dy), C.byref(p), level, n, c, _DT[a.dtype], ops._stream()), "obj_pool_bwd")
+    check(lib().mas_obj_pool_bwd(_p(a), _p(seed), _p(dz), _p(dy), C.byref(p), level, n, c, _DT[a.dtype], _stream()), "obj_pool_bwd")
     return dy
 
 
 def head_fwd(feat, w, p: ObjPlan, plan: Plan, level: int, partial):
     c = feat.shape[1]
-    check(lib().mas_obj_head_fwd(_p(feat), _p(w), C.byref(p), level, c, _DT[feat.dtype], plan.level_blocks(level), _p(partial), ops._stream()),
+    check(lib().mas_obj_head_fwd(_p(feat), _p(w), C.byref(p), level, c, _DT[feat.dtype], plan.level_blocks(level), _p(partial), _stream()),
           "obj_head_fwd")
 
 
 def finalize(partial, p: ObjPlan, device):
     out = torch.empty(1 + p.n_cells, dtype=torch.float32, device=device)
-    check(lib().mas_obj_finalize(_p(partial), C.byref(p), _p(out), ops._stream()), "obj_finalize")
+    check(lib().mas_obj_finalize(_p(partial), C.byref(p), _p(out), _stream()), "obj_finalize")
     return out
 
 
@@ -243,7 +229,7 @@ def head_bwd(feat, w, p: ObjPlan, level: int, dout):
     nc = p.n_canvas
     c, h, wd = feat.shape[1:]
     seed = _nhwc(nc, c, h, wd, feat.dtype, feat.device)
-    check(lib().mas_obj_head_bwd(_p(feat), _p(w), C.byref(p), level, c, _DT[feat.dtype], _p(dout), _p(seed), ops._stream()), "obj_head_bwd")
+    check(lib().mas_obj_head_bwd(_p(feat), _p(w), C.byref(p), level, c, _DT[feat.dtype], _p(dout), _p(seed), _stream()), "obj_head_bwd")
     return seed
 
 
@@ -343,8 +329,8 @@ class _ObjectLoss(torch.autograd.Function):
 def object_loss(lp, img, rec, bbox_obj, dtype=None):
     """The object-aware term on the HIP path: -> [1 + n_cells] fp32 (the loss, then every used crop's LPIPS in (image, box)
     order), or None when no box is used (nothing launched)."""
-    ops._require_cuda(img, "ObjectLoss")
-    ops._require_cuda(rec, "ObjectLoss")
+    _require_cuda(img, "ObjectLoss")
+    _require_cuda(rec, "ObjectLoss")
     if img.shape != rec.shape:
         raise ValueError(f"ObjectLoss: images {tuple(img.shape)} and reconstructions {tuple(rec.shape)} differ")
     plan = make_plan(bbox_obj, min(img.shape[0], rec.shape[0]))

@@ -16,10 +16,9 @@ from typing import Optional
 import torch
 
 from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, SEG_NCHW, SEG_NHWC, SEG_U8, WLAYOUT_K64, WLAYOUT_UP2, \
-    ConvDesc, PackItem, PackTileItem, check, lib
+    ConvDesc, PackItem, PackTileItem, _DT, _ptr, _require_cuda, _stream, check, lib
 from .seglabels import SegLabels
 
-_DT = {torch.float32: F32, torch.bfloat16: BF16}
 _state = {"compute_dtype": torch.bfloat16 if os.environ.get("MAS_COMPUTE_DTYPE", "bf16") == "bf16" else torch.float32}
 
 
@@ -47,19 +46,6 @@ def set_launch_hook(fn) -> None:
 def last_kernel() -> str:
     """the kernel the process's last launch ran (``mas_last_kernel``): the library dispatches on shape; tests assert the choice"""
     return lib().mas_last_kernel().decode()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _require_cuda(t: torch.Tensor, what: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: the MI355X path needs a GPU tensor (no CPU fallback); got device {t.device}")
 
 
 def nhwc(x: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -356,7 +342,7 @@ def set_save_activations(on: bool) -> None:
 
 def _gn_act_ok(c: int, dtype: torch.dtype) -> bool:
     epu = 8 if dtype == torch.bfloat16 else 4
-    return c % epu == 0 and 256 % (c // epu) == 0 and getattr(lib(), "mas_gn_act", None) is not None
+    return c % epu == 0 and 256 % (c // epu) == 0
 
 
 def gn_act(x: torch.Tensor, ss: torch.Tensor, act: int) -> torch.Tensor:

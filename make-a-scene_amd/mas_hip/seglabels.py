@@ -19,7 +19,9 @@ from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
-MAX_PLANES = 8            # MAS_SEG_MAX_PLANES
+from . import SEG_MAX_PLANES
+
+MAX_PLANES = SEG_MAX_PLANES   # MAS_SEG_MAX_PLANES of include/mas_hip.h
 MAX_GROUP = 255
 REFERENCE_THRESHOLDS = (None, None, 0.2, 0.2)     # reference log_utils.py:61-67: face and edges are gated by `sigmoid > 0.2`
 

@@ -24,10 +24,12 @@ def test_library_exports_every_declared_symbol():
         build.build(verbose=False)
     L = ctypes.CDLL(mas_hip.LIB_PATH)
     syms = _header_symbols()
-    assert len(syms) >= 15
+    assert len(syms) >= 125
     for s in syms:
         assert hasattr(L, s), f"{s} declared in include/mas_hip.h but not exported"
-    assert sorted(mas_hip.EXPORTS) == syms, "ctypes binding and header disagree"
+    # EXPORTS is derived from the header (mas_hip/_header.py); the names here come from this file's own regular expression, and
+    # tests/test_header_binding_cpu.py pins the derived types against hand-written ones
+    assert sorted(mas_hip.EXPORTS) == syms and len(mas_hip.EXPORTS) >= 125, "ctypes binding and header disagree"
     assert mas_hip.lib().mas_abi_version() == mas_hip.ABI_VERSION
 
 

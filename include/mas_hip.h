@@ -148,6 +148,23 @@ int    mas_adam_multi_ex(const MasAdamItem* items_device, int n_items, int total
                          int decoupled_wd, void* stream);
 int    mas_grad_scale_multi(const MasAdamItem* items_device, int n_items, int total_blocks, const float* scale_device, void* stream);
 
+/* ---- An exponential moving average of the weights inside the Adam launch, a guard against a non-finite gradient norm, and the swap that
+ * puts the averaged weights in front of the kernels (what torch._foreach_lerp_ after step(), a host read of the norm, and
+ * `w.data.copy_(ema)` do; additions under ABI 10).  Both entries walk the MasAdamItem table above and take a second DEVICE array of n_items
+ * pointers beside it: entry i belongs to item i, fp32 of n elements.
+ *   mas_adam_multi_ema: mas_adam_multi_ex, and after the update of an element e = fma(1 - ema_decay, p_new - e, e) -- torch.lerp(e, p_new,
+ *     1 - ema_decay), 1 - ema_decay rounded to fp32 once -- with e = ema_device[i]; e is read with p, g, m, v and written with p, m, v (36
+ *     bytes per element; the vector path needs all five pointers 16-byte aligned).  A NULL entry: that item keeps no average; ema_device
+ *     itself may be NULL.  grad_norm_device non-NULL (normally `out` of mas_grad_clip_coef, with grad_scale_device = out + 1): every
+ *     work-group reads *grad_norm_device once, and when it is NaN or +-inf returns before its first store -- p, m, v and e of EVERY item keep
+ *     their bits; the caller's step count is its own business.  Both NULL is mas_adam_multi_ex.  ema_decay outside [0, 1) or NaN: MAS_EINVAL.
+ *   mas_swap_multi: p and other_device[i] exchange their n elements (p, n, first_block of the items are read; g, m, v are not); items with
+ *     a NULL entry are left alone.  Twice is the identity.                                                                              */
+int    mas_adam_multi_ema(const MasAdamItem* items_device, float* const* ema_device, int n_items, int total_blocks, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, double bias_correction1, double bias_correction2,
+                          const float* grad_scale_device, int decoupled_wd, float ema_decay, const float* grad_norm_device, void* stream);
+int    mas_swap_multi(const MasAdamItem* items_device, float* const* other_device, int n_items, int total_blocks, void* stream);
+
 /* ---- GroupNorm statistics (replaces the reduction half of torch.nn.GroupNorm,
  * modules.py:40-41).  x: [N,HW,C] NHWC.  Outputs:
  *   mean_rstd [N][G][2] fp32, scale_shift [N][C][2] fp32 with

@@ -7,6 +7,10 @@
 // Arithmetic and its ORDER follow torch's fused kernel (torch/csrc ... FusedAdamMathFunctor, non-amsgrad, maximize = false):
 //   g' = g + wd * p;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g' g';  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
 // with bc1 = 1 - b1^t, bc2 = 1 - b2^t computed by the caller in double precision.
+// mas_adam_multi_ema keeps an exponential moving average of the weights in the same launch: e += (1 - decay) (p_new - e), one more read and
+// one more write of 4 bytes per element (36 bytes: 3.43 GB for VQ-IMG, 0.54 ms at 6.3 TB/s; as a pass of its own after the step it is 40
+// bytes and a launch per tensor), and returns before its first store when the gradient norm it is handed is not finite.
+// mas_swap_multi exchanges p with another tensor per item over the same table (the EMA weights in front of the kernels, and back).
 #include "mas_common.h"
 #include "../../include/mas_hip.h"
 #include <math.h>
@@ -15,25 +19,45 @@ namespace {
 
 constexpr int ADAM_NT = 256, ADAM_PER_BLOCK = 4096;     // 4 x float4 per thread and tensor
 
-// the item that owns work-group b (items in ascending first_block order)
-__device__ __forceinline__ MasAdamItem item_of_block(const MasAdamItem* __restrict__ items, int n_items, int b) {
+// the index of the item that owns work-group b (items in ascending first_block order); the EMA instantiations and the swap look their
+// second table up with it
+__device__ __forceinline__ int item_index_of_block(const MasAdamItem* __restrict__ items, int n_items, int b) {
     int lo = 0, hi = n_items - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (items[mid].first_block <= b) lo = mid; else hi = mid - 1;
     }
-    return items[lo];
+    return lo;
 }
+
+__device__ __forceinline__ MasAdamItem item_of_block(const MasAdamItem* __restrict__ items, int n_items, int b) {
+    return items[item_index_of_block(items, n_items, b)];
+}
+
+// NaN or +-inf, from the bits (holds under any floating-point option the file is built with)
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
 // SCALE: every gradient is multiplied by *grad_scale as it is loaded (the clip coefficient of mas_grad_clip_coef; g itself is not written).
 // DECOUPLED: AdamW -- p -= lr wd p ahead of the moments, no wd p term in g (torch's fused functor in its ADAMW mode).
-// <false, false> is the plain Adam step: neither `grad_scale` nor `lr` is read.
-template <bool SCALE, bool DECOUPLED>
+// <false, false, false> is the plain Adam step: neither `grad_scale` nor `lr` is read.
+// EMA: the instantiations behind mas_adam_multi_ema; without it the three trailing arguments are not read and the code is what it was.
+//   guard: `grad_norm` non-null and *grad_norm NaN or +-inf (one uniform read per work-group): return before anything is stored.
+//   average: ema[i] non-null (`ema` itself may be null): e = fma(ema_w, p_new - e, e) after the update of an element, ema_w = 1 - decay; e is
+//   loaded with p, g, m, v and stored with p, m, v.  Five 4 x float4 arrays are 80 data registers: 120 / 122 VGPRs and four waves per SIMD
+//   (the other instantiations: 94 and five).  EMA_GROUPS = 2 (two halves of 2 x float4 per tensor) is 96 VGPRs and five waves with half
+//   the loads in flight per lane.
+constexpr int EMA_GROUPS = 4;
+template <bool SCALE, bool DECOUPLED, bool EMA>
 __global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* __restrict__ items, int n_items, float step_size, float inv_bc2_sqrt,
                                                              float b1, float b2, float eps, float wd,     // (inv_bc2_sqrt: sqrt(bias_correction2) itself)
-                                                             const float* __restrict__ grad_scale, float lr) {
+                                                             const float* __restrict__ grad_scale, float lr, float* const* __restrict__ ema,
+                                                             float ema_w, const float* __restrict__ grad_norm) {
     const int b = blockIdx.x;
-    const MasAdamItem it = item_of_block(items, n_items, b);
+    if constexpr (EMA) {
+        if (grad_norm != nullptr && not_finite(*grad_norm)) return;
+    }
+    const int idx = item_index_of_block(items, n_items, b);
+    const MasAdamItem it = items[idx];
     const long long base = (long long)(b - it.first_block) * ADAM_PER_BLOCK;
     const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
     float gs = 1.0f;
@@ -49,6 +73,46 @@ __global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* 
     };
     const bool vec = ((reinterpret_cast<uintptr_t>(it.p) | reinterpret_cast<uintptr_t>(it.g) | reinterpret_cast<uintptr_t>(it.m) |
                        reinterpret_cast<uintptr_t>(it.v)) & 15) == 0;
+    if constexpr (EMA) {
+        float* const ema_t = ema != nullptr ? ema[idx] : nullptr;
+        if (ema_t != nullptr) {
+            if (vec && (reinterpret_cast<uintptr_t>(ema_t) & 15) == 0 && base + ADAM_PER_BLOCK <= it.n) {
+                for (int h = 0; h < 4; h += EMA_GROUPS) {
+                    f32x4 p[EMA_GROUPS], g[EMA_GROUPS], m[EMA_GROUPS], v[EMA_GROUPS], a[EMA_GROUPS];
+#pragma unroll
+                    for (int k = 0; k < EMA_GROUPS; ++k) {
+                        const long long i = base + (long long)((h + k) * ADAM_NT + threadIdx.x) * 4;
+                        p[k] = *reinterpret_cast<const f32x4*>(it.p + i); g[k] = *reinterpret_cast<const f32x4*>(it.g + i);
+                        m[k] = *reinterpret_cast<const f32x4*>(it.m + i); v[k] = *reinterpret_cast<const f32x4*>(it.v + i);
+                        a[k] = *reinterpret_cast<const f32x4*>(ema_t + i);
+                    }
+#pragma unroll
+                    for (int k = 0; k < EMA_GROUPS; ++k) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float pp = p[k][e], mm = m[k][e], vv = v[k][e];
+                            upd(pp, g[k][e], mm, vv);
+                            p[k][e] = pp; m[k][e] = mm; v[k][e] = vv; a[k][e] = fmaf(ema_w, pp - a[k][e], a[k][e]);
+                        }
+                        const long long i = base + (long long)((h + k) * ADAM_NT + threadIdx.x) * 4;
+                        *reinterpret_cast<f32x4*>(it.p + i) = p[k]; *reinterpret_cast<f32x4*>(it.m + i) = m[k];
+                        *reinterpret_cast<f32x4*>(it.v + i) = v[k]; *reinterpret_cast<f32x4*>(ema_t + i) = a[k];
+                    }
+                }
+            } else {                                 // a tensor's last block, or unaligned storage: element by element
+                for (int k = threadIdx.x; k < ADAM_PER_BLOCK; k += ADAM_NT) {
+                    const long long i = base + k;
+                    if (i < it.n) {
+                        float pp = it.p[i], mm = it.m[i], vv = it.v[i];
+                        const float aa = ema_t[i];
+                        upd(pp, it.g[i], mm, vv);
+                        it.p[i] = pp; it.m[i] = mm; it.v[i] = vv; ema_t[i] = fmaf(ema_w, pp - aa, aa);
+                    }
+                }
+            }
+            return;
+        }
+    }
     if (vec && base + ADAM_PER_BLOCK <= it.n) {
         f32x4 p[4], g[4], m[4], v[4];
 #pragma unroll
@@ -153,22 +217,52 @@ __global__ __launch_bounds__(ADAM_NT) void grad_scale_multi_kernel(const MasAdam
     }
 }
 
+// p <-> other[i], element for element, for every item whose `other` entry is not null
+__global__ __launch_bounds__(ADAM_NT) void swap_multi_kernel(const MasAdamItem* __restrict__ items, float* const* __restrict__ other, int n_items) {
+    const int b = blockIdx.x;
+    const int idx = item_index_of_block(items, n_items, b);
+    const MasAdamItem it = items[idx];
+    float* const q = other[idx];
+    if (q == nullptr) return;
+    const long long base = (long long)(b - it.first_block) * ADAM_PER_BLOCK;
+    if (((reinterpret_cast<uintptr_t>(it.p) | reinterpret_cast<uintptr_t>(q)) & 15) == 0 && base + ADAM_PER_BLOCK <= it.n) {
+        f32x4 x[4], y[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long long i = base + (long long)(k * ADAM_NT + threadIdx.x) * 4;
+            x[k] = *reinterpret_cast<const f32x4*>(it.p + i); y[k] = *reinterpret_cast<const f32x4*>(q + i);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long long i = base + (long long)(k * ADAM_NT + threadIdx.x) * 4;
+            *reinterpret_cast<f32x4*>(it.p + i) = y[k]; *reinterpret_cast<f32x4*>(q + i) = x[k];
+        }
+    } else {
+        for (int k = threadIdx.x; k < ADAM_PER_BLOCK; k += ADAM_NT) {
+            const long long i = base + k;
+            if (i < it.n) { const float x = it.p[i], y = q[i]; it.p[i] = y; q[i] = x; }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int mas_adam_blocks(long long numel) { return numel <= 0 ? 0 : (int)((numel + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK); }
 
 namespace {
 
-template <bool SCALE, bool DECOUPLED>
+template <bool SCALE, bool DECOUPLED, bool EMA = false>
 int adam_launch(const char* name, const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
-                float weight_decay, double bias_correction1, double bias_correction2, const float* grad_scale_device, void* stream) {
+                float weight_decay, double bias_correction1, double bias_correction2, const float* grad_scale_device, void* stream,
+                float* const* ema_device = nullptr, float ema_w = 0.0f, const float* grad_norm_device = nullptr) {
     MAS_ENTER();
     if (!items_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "%s: empty batch", name);
     if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) MAS_FAIL(MAS_EINVAL, "%s: bias corrections must be positive (step >= 1)", name);
     const float step_size = (float)((double)lr / bias_correction1);
     const float inv_bc2_sqrt = (float)sqrt(bias_correction2);      // (passed as the divisor, like torch's bias_correction2_sqrt)
-    hipLaunchKernelGGL((adam_multi_kernel<SCALE, DECOUPLED>), dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
-                       items_device, n_items, step_size, inv_bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale_device, lr);
+    hipLaunchKernelGGL((adam_multi_kernel<SCALE, DECOUPLED, EMA>), dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
+                       items_device, n_items, step_size, inv_bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale_device, lr, ema_device, ema_w,
+                       grad_norm_device);
     MAS_CHECK_LAUNCH(name);
     return MAS_OK;
 }
@@ -192,6 +286,33 @@ extern "C" int mas_adam_multi_ex(const MasAdamItem* items_device, int n_items, i
     if (grad_scale_device) return dec ? MAS_ADAM_EX(true, true) : MAS_ADAM_EX(true, false);
     return MAS_ADAM_EX(false, true);
 #undef MAS_ADAM_EX
+}
+
+extern "C" int mas_adam_multi_ema(const MasAdamItem* items_device, float* const* ema_device, int n_items, int total_blocks, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, double bias_correction1, double bias_correction2,
+                                  const float* grad_scale_device, int decoupled_wd, float ema_decay, const float* grad_norm_device, void* stream) {
+    MAS_ENTER();
+    if (!items_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "adam_multi_ema: empty batch");
+    if (!(ema_decay >= 0.0f && ema_decay < 1.0f)) MAS_FAIL(MAS_EINVAL, "adam_multi_ema: ema_decay must be in [0, 1)");
+    if (!ema_device && !grad_norm_device)
+        return mas_adam_multi_ex(items_device, n_items, total_blocks, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2,
+                                 grad_scale_device, decoupled_wd, stream);
+    const bool dec = decoupled_wd != 0;
+    const float ema_w = 1.0f - ema_decay;
+#define MAS_ADAM_EMA(S, D) adam_launch<S, D, true>("adam_multi_ema", items_device, n_items, total_blocks, lr, beta1, beta2, eps, weight_decay, \
+                                                   bias_correction1, bias_correction2, grad_scale_device, stream, ema_device, ema_w, grad_norm_device)
+    if (grad_scale_device) return dec ? MAS_ADAM_EMA(true, true) : MAS_ADAM_EMA(true, false);
+    return dec ? MAS_ADAM_EMA(false, true) : MAS_ADAM_EMA(false, false);
+#undef MAS_ADAM_EMA
+}
+
+extern "C" int mas_swap_multi(const MasAdamItem* items_device, float* const* other_device, int n_items, int total_blocks, void* stream) {
+    MAS_ENTER();
+    if (!items_device || !other_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "swap_multi: null or empty arguments");
+    hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream), items_device,
+                       other_device, n_items);
+    MAS_CHECK_LAUNCH("swap_multi");
+    return MAS_OK;
 }
 
 extern "C" int mas_grad_sqnorm_multi(const MasAdamItem* items_device, int n_items, int total_blocks, double* partials, void* stream) {

@@ -14,7 +14,26 @@ torch.nn.utils.clip_grad_norm_'s coefficient ``min(m / (norm + 1e-6), 1)``: one 
 table (``mas_grad_sqnorm_multi``, fp64 sums), one launch for the coefficient (``mas_grad_clip_coef``), and the Adam launch multiplies
 each gradient by that device scalar as it loads it (``mas_adam_multi_ex``).  Gradients are not modified, nothing is read on the host;
 ``opt.grad_norm`` (before clipping) and ``opt.clip_coef`` are 0-dim fp32 device tensors, valid until the next step.
-``clip_grad_norm_(parameters, max_norm)`` is the standalone form for callers that keep another optimizer."""
+``clip_grad_norm_(parameters, max_norm)`` is the standalone form for callers that keep another optimizer.
+
+``ema_decay=d`` on either keeps an exponential moving average of every parameter in ``state[p]["ema"]`` (fp32, a clone of ``p`` taken
+before its first update), updated in the Adam launch itself (``mas_adam_multi_ema``): ``ema = lerp(ema, p_new, 1 - d)`` at every step
+that updates ``p``; a parameter without a gradient at a step keeps its average as it is.  ``ema_warmup=True`` uses
+``min(d, (1 + k) / (10 + k))`` at this optimizer's ``k``-th step (computed on the host; ``k`` travels in ``state_dict()`` as
+``param_groups[0]["ema_step"]``, a key torch's optimizers carry along and do not read).  ``state_dict()`` holds ``"ema"`` per parameter and
+still loads into torch.optim.Adam / AdamW; a state without it (torch's, or this optimizer's without ``ema_decay``) loads here and the
+average starts from the weights at the next step.  ``opt.swap_ema()`` is the context manager under which the parameters hold the averaged
+weights (one ``mas_swap_multi`` launch per device, then ``ops.invalidate_weight_cache()``; the same again on exit restores both bit for
+bit; storage does not move).  ``opt.ema_state_dict(module)`` is ``module.state_dict()`` with the averaged weights in place of the
+parameters: the checkpoint to evaluate or sample from.  Data-parallel runs need nothing more: the average is a function of the parameters,
+which are identical across ranks.
+
+``skip_nonfinite=True`` does not apply a step whose global gradient norm is NaN or infinite: the norm launches run (with or without
+``max_grad_norm``), the Adam launch reads the norm on the device and stores nothing when it is not finite, so ``p``, both moments and the
+average keep their bits.  Nothing is read on the host: ``opt.grad_norm`` is set as with clipping, ``opt.step_skipped`` computes a 0-dim
+bool device tensor when asked, and ``state["step"]`` advances on a skipped step too -- the bias corrections run one step ahead after a
+skip."""
+import contextlib
 import ctypes as C
 import math
 
@@ -25,13 +44,14 @@ from . import AdamItem, check, lib
 _RING = 4
 
 
-def _table(tables, tkey, device, items):
-    """The item table on the device (``tables[tkey]``: one ring of staging buffers per key).  Gradient
+def _table(tables, tkey, device, items, tail=b""):
+    """The item table on the device (``tables[tkey]``: one ring of staging buffers per key), followed by the bytes ``tail`` (the array of
+    EMA / swap pointers, one per item: the same copy and the same byte comparison cover both).  Gradient
     tensors are usually fresh allocations every step (``zero_grad(set_to_none=True)``), so the table changes every step: it goes through a ring of pinned staging buffers with an asynchronous copy each, and the
     host only waits for the copy issued ``_RING`` steps ago -- never for the step in flight (a wait on the previous step's copy
     would serialise the host behind the whole backward: measured, +9 ms of wall time per step)."""
     arr = (AdamItem * len(items))(*items)
-    raw = bytes(memoryview(arr))
+    raw = bytes(memoryview(arr)) + tail
     ent = tables.get(tkey)
     if ent is not None and ent["raw"] == raw:
         return ent["slots"][ent["cur"]][1]
@@ -68,6 +88,25 @@ def _check_max_norm(max_norm, who):
     return max_norm
 
 
+_FLT_MAX = 3.4028234663852886e38       # as max_norm: min(FLT_MAX / (norm + 1e-6), 1) is exactly 1 for every finite norm
+
+
+def _check_ema_decay(d, who):
+    d = float(d)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"{who}: ema_decay must be in [0, 1), got {d}")
+    return d
+
+
+def _ema_weight(decay):
+    """``1 - decay`` as the kernel forms it: both rounded to fp32"""
+    return C.c_float(1.0 - C.c_float(decay).value).value
+
+
+def _pointers(ptrs):
+    return bytes(memoryview((C.c_void_p * len(ptrs))(*ptrs)))
+
+
 def _one_device(grads, who):
     devices = {g.device for g in grads}
     if len(devices) > 1:
@@ -97,7 +136,8 @@ class Adam(torch.optim.Optimizer):
     _decoupled_wd = 0
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False,
-                 capturable=False, differentiable=False, fused=None, foreach=None, max_grad_norm=None):
+                 capturable=False, differentiable=False, fused=None, foreach=None, max_grad_norm=None, ema_decay=None, ema_warmup=False,
+                 skip_nonfinite=False):
         name = f"mas_hip.optim.{type(self).__name__}"
         if amsgrad or maximize or capturable or differentiable:
             raise NotImplementedError(f"{name}: amsgrad / maximize / capturable / differentiable are not implemented")
@@ -105,20 +145,41 @@ class Adam(torch.optim.Optimizer):
             raise ValueError(f"{name}: invalid hyper-parameter")
         # (an attribute, not a key of `defaults`: the clip is global over all groups, and state_dict() stays torch.optim.Adam's)
         self.max_grad_norm = None if max_grad_norm is None else _check_max_norm(max_grad_norm, name)
-        self.grad_norm = self.clip_coef = None      # 0-dim fp32 tensors after a clipped step
+        self.grad_norm = self.clip_coef = None      # 0-dim fp32 tensors after a clipped (or guarded) step
+        self.ema_decay = None if ema_decay is None else _check_ema_decay(ema_decay, name)     # attributes like max_grad_norm: all groups
+        self.ema_warmup, self.skip_nonfinite = bool(ema_warmup), bool(skip_nonfinite)
+        self._swapped = False                       # inside swap_ema()
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                                       capturable=False, differentiable=False, fused=None, foreach=None))
         self._tables = {}            # device index -> ring of (pinned staging, device table, event) slots + the bytes of the current table
         self._clip_bufs = {}         # device -> fp64 partial sums of the norm launches
         self._clip_out = {}          # device -> (norm, coefficient) fp32
+        if self.ema_decay is not None:
+            self.param_groups[0]["ema_step"] = 0     # steps taken with the average on (ema_warmup's k); saved and loaded with the groups
 
-    def _table(self, tkey, device, items):
-        return _table(self._tables, tkey, device, items)
+    def _table(self, tkey, device, items, tail=b""):
+        return _table(self._tables, tkey, device, items, tail)
+
+    def _ema_decay_now(self):
+        """this step's decay (None: no average), and the step counter of ``ema_warmup`` advanced"""
+        if self.ema_decay is None:
+            return None
+        g0 = self.param_groups[0]
+        k = int(g0.get("ema_step", 0))               # (absent after loading a state saved without an average)
+        g0["ema_step"] = k + 1
+        return min(self.ema_decay, (1.0 + k) / (10.0 + k)) if self.ema_warmup else self.ema_decay
+
+    @property
+    def step_skipped(self):
+        """0-dim bool tensor on the gradients' device: the last step's gradient norm was not finite (with ``skip_nonfinite`` that step was
+        not applied).  Computed when asked; None before the first step that computes a norm."""
+        return None if self.grad_norm is None else ~torch.isfinite(self.grad_norm)
 
     def _collect(self, group):
         """Creates missing state, advances `step`, and sorts the group's parameters that have a gradient: (device, step number) -> items
         for the kernel (parameters on different step counts take separate launches), the number of blocks per key, and the
-        (parameter, state, step) triples that take the torch expression (another dtype / device / layout)."""
+        (parameter, state, step) triples that take the torch expression (another dtype / device / layout).  With ``ema_decay`` the state
+        holds ``ema`` and the kernel's items carry its pointer as the attribute ``ema`` (0: none)."""
         by_key, first, slow = {}, {}, []
         for p in group["params"]:
             if p.grad is None:
@@ -130,6 +191,9 @@ class Adam(torch.optim.Optimizer):
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self.ema_decay is not None and "ema" not in st:       # with the rest of the state, or at the first step after loading a state without it
+                st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+            ema = st["ema"] if self.ema_decay is not None else None
             if st["step"].device.type != "cpu":          # a state loaded from torch.optim.Adam(fused=True / capturable=True) keeps `step` on
                 st["step"] = st["step"].detach().to("cpu", torch.float32)   # the device: one sync here instead of one per step and parameter
             st["step"] += 1
@@ -137,7 +201,8 @@ class Adam(torch.optim.Optimizer):
             if p.numel() == 0:
                 continue                                 # (torch.optim.Adam accepts empty parameters: nothing to update)
             native = (p.is_cuda and p.dtype == torch.float32 and p.grad.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()
-                      and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous() and p.grad.device == p.device)
+                      and st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous() and p.grad.device == p.device
+                      and (ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.device == p.device)))
             if not native:
                 slow.append((p, st, t))
                 continue
@@ -145,13 +210,28 @@ class Adam(torch.optim.Optimizer):
             it = AdamItem()
             it.p, it.g, it.m, it.v, it.n = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
             it.first_block = first.get(key, 0)
+            it.ema = 0 if ema is None else ema.data_ptr()
             first[key] = it.first_block + lib().mas_adam_blocks(p.numel())
             by_key.setdefault(key, []).append(it)
         return by_key, first, slow
 
-    def _launch(self, table, n_items, blocks, hyper, t, scale, stream):
+    def _item_table(self, tkey, device, items):
+        """the device table of ``items`` with, under ``ema_decay``, the array of their EMA pointers behind it (its address: second value)"""
+        if self.ema_decay is None:
+            return self._table(tkey, device, items), None
+        table = self._table(tkey, device, items, _pointers([it.ema for it in items]))
+        return table, table.data_ptr() + C.sizeof(AdamItem) * len(items)
+
+    def _launch(self, table, n_items, blocks, hyper, t, scale, stream, ema=None, decay=None, norm=None):
+        """``ema``: device address of the EMA pointer array with this step's ``decay``; ``norm``: the device norm the guard reads"""
         lr, b1, b2, eps, wd = hyper
-        if scale is None and not self._decoupled_wd:
+        if ema is not None or norm is not None:
+            check(lib().mas_adam_multi_ema(C.c_void_p(table.data_ptr()), None if ema is None else C.cast(C.c_void_p(ema), C.POINTER(C.c_void_p)),
+                                           n_items, blocks, lr, b1, b2, eps, wd, 1.0 - b1 ** t, 1.0 - b2 ** t,
+                                           None if scale is None else C.c_void_p(scale.data_ptr()), self._decoupled_wd,
+                                           0.0 if decay is None else decay, None if norm is None else C.c_void_p(norm.data_ptr()), stream),
+                  "adam_multi_ema")
+        elif scale is None and not self._decoupled_wd:
             check(lib().mas_adam_multi(C.c_void_p(table.data_ptr()), n_items, blocks, lr, b1, b2, eps, wd, 1.0 - b1 ** t, 1.0 - b2 ** t, stream),
                   "adam_multi")
         else:
@@ -164,28 +244,34 @@ class Adam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._swapped:
+            raise RuntimeError(f"mas_hip.optim.{type(self).__name__}: step() inside swap_ema(): the parameters hold the averaged weights")
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        if self.max_grad_norm is not None:
-            self._clipped_step()
+        decay = self._ema_decay_now()
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            self._clipped_step(decay)
             return loss
         for group in self.param_groups:
             hyper = self._hyper(group)
             by_key, first, slow = self._collect(group)
             for p, st, t in slow:
-                self._torch_update(p, p.grad, st, t, *hyper)
+                self._torch_update(p, p.grad, st, t, *hyper, decay=decay)
             for (device, t), items in by_key.items():
                 with torch.cuda.device(device):
                     ordinal = [k for k in by_key if k[0] == device].index((device, t))      # 0 unless parameters of the group sit on different step counts
-                    table = self._table((device.index, ordinal), device, items)
+                    table, ema = self._item_table((device.index, ordinal), device, items)
                     stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-                    self._launch(table, len(items), first[(device, t)], hyper, t, None, stream)
+                    self._launch(table, len(items), first[(device, t)], hyper, t, None, stream, ema, decay)
         return loss
 
-    def _clipped_step(self):
-        """The tables of ALL groups first, the norm launches over them, one coefficient launch, then the Adam launches with that scalar."""
+    def _clipped_step(self, decay=None):
+        """The tables of ALL groups first, the norm launches over them, one coefficient launch, then the Adam launches with that scalar.
+        ``skip_nonfinite`` without ``max_grad_norm`` takes the same route for the norm (the coefficient launch with FLT_MAX: exactly 1
+        for every finite norm) and hands the Adam launch no scale at all, so the step keeps the bits of the unclipped one."""
+        max_norm = _FLT_MAX if self.max_grad_norm is None else self.max_grad_norm
         name = f"mas_hip.optim.{type(self).__name__}"
         device = _one_device([p.grad for group in self.param_groups for p in group["params"] if p.grad is not None and p.numel()], name)
         launches, slow = [], []              # (hyper, step number, items, blocks) per kernel launch; (hyper, parameter, state, step) for torch
@@ -197,24 +283,35 @@ class Adam(torch.optim.Optimizer):
         if device is None:
             return
         if device.type != "cuda":
-            self.grad_norm, self.clip_coef = _cpu_norm_coef([p.grad for _, p, _, _ in slow], self.max_grad_norm)
+            self.grad_norm, self.clip_coef = _cpu_norm_coef([p.grad for _, p, _, _ in slow], max_norm)
         else:
             with torch.cuda.device(device):
                 stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
                 out = self._clip_out.get(device)
                 if out is None:
                     out = self._clip_out[device] = torch.zeros(2, dtype=torch.float32, device=device)
-                tables = [(self._table(("clip", device.index, i), device, items), len(items), blocks)
-                          for i, (_, _, items, blocks) in enumerate(launches)]
+                tables, emas = [], []
+                for i, (_, _, items, blocks) in enumerate(launches):
+                    table, ema = self._item_table(("clip", device.index, i), device, items)
+                    tables.append((table, len(items), blocks))
+                    emas.append(ema)
                 extra = torch.stack([p.grad.double().pow(2).sum() for _, p, _, _ in slow]) if slow else None
-                _norm_coef_launches(tables, out, _partials(self._clip_bufs, device, sum(b for _, _, b in tables)), extra, self.max_grad_norm, stream)
-                for (hyper, t, _, _), (table, n_items, blocks) in zip(launches, tables):
-                    self._launch(table, n_items, blocks, hyper, t, out[1], stream)
+                _norm_coef_launches(tables, out, _partials(self._clip_bufs, device, sum(b for _, _, b in tables)), extra, max_norm, stream)
+                scale = None if self.max_grad_norm is None else out[1]
+                for (hyper, t, _, _), (table, n_items, blocks), ema in zip(launches, tables, emas):
+                    self._launch(table, n_items, blocks, hyper, t, scale, stream, ema, decay, out[0] if self.skip_nonfinite else None)
                 self.grad_norm, self.clip_coef = out[0], out[1]
+        skip = ~torch.isfinite(self.grad_norm) if self.skip_nonfinite else None
         for hyper, p, st, t in slow:
-            self._torch_update(p, p.grad * self.clip_coef.to(p.grad.dtype), st, t, *hyper)
+            g = p.grad if self.max_grad_norm is None else p.grad * self.clip_coef.to(p.grad.dtype)
+            self._torch_update(p, g, st, t, *hyper, decay=decay, skip=skip)
 
-    def _torch_update(self, p, g, st, t, lr, b1, b2, eps, wd):
+    def _torch_update(self, p, g, st, t, lr, b1, b2, eps, wd, decay=None, skip=None):
+        """the kernel's formulas as torch expressions.  ``decay``: this step's EMA decay; ``skip``: a 0-dim bool tensor on any device --
+        where it is True the four tensors get their old bits back (a ``where`` on the device: nothing is read on the host)"""
+        held = [st["exp_avg"], st["exp_avg_sq"]] + ([st["ema"]] if decay is not None else [])
+        if skip is not None:
+            old = [x.detach().clone() for x in [p] + held]
         if wd != 0.0:
             if self._decoupled_wd:
                 p.mul_(1.0 - lr * wd)
@@ -224,6 +321,70 @@ class Adam(torch.optim.Optimizer):
         st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1.0 - b2)
         denom = (st["exp_avg_sq"].sqrt() / math.sqrt(1.0 - b2 ** t)).add_(eps)
         p.addcdiv_(st["exp_avg"], denom, value=-lr / (1.0 - b1 ** t))
+        if decay is not None:
+            st["ema"].lerp_(p.detach().to(st["ema"].dtype), _ema_weight(decay))
+        if skip is not None:
+            for x, o in zip([p] + held, old):
+                x.copy_(torch.where(skip.to(x.device), o, x))
+
+    def _ema_pairs(self):
+        return [(p, self.state[p]["ema"]) for group in self.param_groups for p in group["params"] if "ema" in self.state.get(p, ())]
+
+    @torch.no_grad()
+    def _swap(self):
+        """p <-> state[p]["ema"] for every parameter that has one: one mas_swap_multi launch per device, a temporary for the rest"""
+        per_device = {}
+        for p, e in self._ema_pairs():
+            if p.numel() == 0:
+                continue
+            if (p.is_cuda and e.device == p.device and p.dtype == torch.float32 and e.dtype == torch.float32 and p.is_contiguous()
+                    and e.is_contiguous()):
+                per_device.setdefault(p.device, []).append((p, e))
+            else:
+                tmp = p.detach().clone()
+                p.detach().copy_(e)
+                e.copy_(tmp)
+        for device, pairs in per_device.items():
+            items, blocks = [], 0
+            for p, _ in pairs:
+                it = AdamItem()
+                it.p, it.n, it.first_block = p.data_ptr(), p.numel(), blocks
+                blocks += lib().mas_adam_blocks(p.numel())
+                items.append(it)
+            with torch.cuda.device(device):
+                table = self._table(("swap", device.index), device, items, _pointers([e.data_ptr() for _, e in pairs]))
+                other = C.cast(C.c_void_p(table.data_ptr() + C.sizeof(AdamItem) * len(items)), C.POINTER(C.c_void_p))
+                check(lib().mas_swap_multi(C.c_void_p(table.data_ptr()), other, len(items), blocks,
+                                           C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "swap_multi")
+        from . import ops                            # (ops binds the whole library: not needed to construct or step an optimizer)
+        ops.invalidate_weight_cache()
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Inside, the parameters hold the averaged weights and ``state[p]["ema"]`` the live ones; packed weight images and bf16 shadows
+        are invalidated on entry and on exit, so every kernel sees the weights that are there.  After exit both are restored bit for
+        bit.  No storage moves (captured decode graphs stay valid).  Entering twice, or ``step()`` inside, raises."""
+        name = f"mas_hip.optim.{type(self).__name__}"
+        if self._swapped:
+            raise RuntimeError(f"{name}: swap_ema() is already active")
+        if self.ema_decay is None:
+            raise RuntimeError(f"{name}: swap_ema() needs ema_decay")
+        self._swap()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swapped = False
+            self._swap()
+
+    def ema_state_dict(self, module):
+        """``module.state_dict()`` with every parameter that has an average replaced by a clone of it; buffers and parameters without one
+        are unchanged (the averaged weights are in the parameters themselves inside ``swap_ema()``: the result is the same)"""
+        sd = module.state_dict()
+        for name, p in module.named_parameters(remove_duplicate=False):
+            if name in sd and "ema" in self.state.get(p, ()):
+                sd[name] = (p if self._swapped else self.state[p]["ema"]).detach().clone()
+        return sd
 
 
 class AdamW(Adam):

@@ -580,6 +580,41 @@ int mas_seg_classify(const void* x, int x_dtype, int x_layout, const int* groups
 int mas_seg_agreement(const unsigned char* pred, const unsigned char* target, const int* groups, int n_groups, int value_channels,
                       int N, int H, int W, long long* counts, void* stream);
 
+/* mas_img_bytes, mas_img_agreement*, mas_code_usage (additions under ABI 10): the VQ-IMG read-out -- float images to uint8 pictures, the
+ *   squared error and SSIM between two pictures, and how often each code of the codebook is used.
+ *   mas_img_bytes: x [N, C, H, W], fp32 or bf16, dense MAS_SEG_NCHW or MAS_SEG_NHWC, element alignment only, 1 <= C <=
+ *     MAS_IMG_MAX_CHANNELS -> out uint8 [N, H, W, C] (interleaved).  With s = (float)(255.0 / (hi - lo)) and (float)lo, per element in fp32,
+ *     every operation rounded on its own (no fused multiply-add):  t = (x - lo) * s;  t = fmin(fmax(t, 0), 255), a NaN gives 0;
+ *     byte = rint(t), half to even.  lo < hi, both finite (else MAS_EINVAL).  x is read once, in 16-byte loads where it is 16-byte aligned
+ *     (NCHW: and H W a multiple of the unit), with head and tail element by element (NHWC).
+ *   mas_img_agreement: a, b = two pictures uint8 [N, H, W, C] ->
+ *       sse[n] += sum over H W C of (a - b)^2, device int64 [N] (64-bit integer atomics: exact in any order; zero it first);
+ *       partials[n][ty][tx] = the fp64 sum of the SSIM map over tile (ty, tx) of image n, device fp64 [mas_img_agreement_blocks()].
+ *     SSIM is Wang et al. 2004 in its "valid" form on the bytes 0 .. 255: `window` = HOST array of MAS_IMG_SSIM_WINDOW fp64 weights g (the
+ *     caller normalises exp(-(i - 5)^2 / (2 1.5^2)) to sum 1; the 2-D window is g x g), C1 = (0.01 255)^2, C2 = (0.03 255)^2, no padding:
+ *     for every channel and each of the (H - 10)(W - 10) window positions mu_a, mu_b, E[a^2], E[b^2], E[ab] under the window,
+ *     var_a = E[a^2] - mu_a^2, var_b likewise, cov = E[ab] - mu_a mu_b, value = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)
+ *     (var_a + var_b + C2)), unclamped.  The separable sums (11 horizontal taps, then 11 vertical), the five maps and the value are fp64.
+ *     A tile is MAS_IMG_SSIM_TILE x MAS_IMG_SSIM_TILE window positions; an extent below the window still has one tile per row / column
+ *     (it carries the squared error).  Nothing outside the pictures is read.
+ *   mas_img_agreement_blocks: the number of tiles = the fp64 sums `partials` must hold (negative: an error code).
+ *   mas_img_agreement_reduce: ssim[n] = (the tiles of image n added in a fixed order) / (C (H - 10)(W - 10)), device fp64 [N]; NaN when
+ *     H or W is below the window.  Tile sums and their order do not depend on the grid: the same pictures give the same bits.
+ *   mas_code_usage: indices = n device integers of index_bytes 8 (int64) or 4 (int32) -> counts, device int64 [K + 1], ADDED to what it
+ *     holds: counts[k] for 0 <= k < K, counts[K] = the indices outside [0, K).  The range check comes before any indexing.  Work-group
+ *     histograms in LDS while K + 1 <= MAS_CODE_USAGE_LDS_BINS, global 64-bit integer atomics beyond.  n <= 2^32 - 1.
+ *   All: no host synchronisation (they capture into a graph), grids from the shape and the CU count, 64-bit offsets, no float atomics.
+ *     Null arguments, an empty shape: MAS_EINVAL.  C > MAS_IMG_MAX_CHANNELS, H W > 2^30: MAS_EUNSUPPORTED.  A workspace of another
+ *     size than mas_img_agreement_blocks says: MAS_EWORKSPACE.  sse, partials, ssim, counts 8-byte aligned.                            */
+enum { MAS_IMG_SSIM_TILE = 16, MAS_IMG_SSIM_WINDOW = 11, MAS_IMG_MAX_CHANNELS = 4, MAS_CODE_USAGE_LDS_BINS = 12288 };
+int mas_img_bytes(const void* x, int x_dtype, int x_layout, int N, int C, int H, int W, double lo, double hi, unsigned char* out,
+                  void* stream);
+int mas_img_agreement_blocks(int N, int C, int H, int W);
+int mas_img_agreement(const unsigned char* a, const unsigned char* b, int N, int C, int H, int W, const double* window, long long* sse,
+                      double* partials, int n_partials, void* stream);
+int mas_img_agreement_reduce(const double* partials, int n_partials, int N, int C, int H, int W, double* ssim, void* stream);
+int mas_code_usage(const void* indices, int index_bytes, long long n, int K, long long* counts, void* stream);
+
 /* mas_layernorm_pair_* (ABI v9): the sandwich LayerNorm + residual of one sub-block and the pre-LayerNorm of the next as ONE pass,
  *   xnew = residual + LN1(h),  y2 = LN2(xnew)      (reference models/transformer.py:201-203 + :205, and :207-209 + :197 of the next layer
  *   or the final LayerNorm :264) -- the row stays in registers between the two: 12 B per element instead of 16, bit for bit the values

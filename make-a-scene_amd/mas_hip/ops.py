@@ -15,8 +15,8 @@ from typing import Optional
 
 import torch
 
-from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, SEG_NCHW, SEG_NHWC, SEG_U8, WLAYOUT_K64, WLAYOUT_UP2, \
-    ConvDesc, PackItem, PackTileItem, _DT, _ptr, _require_cuda, _stream, check, lib
+from . import ACT_AFFINE, ACT_AFFINE_SILU, ACT_NONE, ATTN_DECODE_MAX_SPLITS, BF16, F32, IMG_SSIM_WINDOW, SEG_NCHW, SEG_NHWC, SEG_U8, WLAYOUT_K64, \
+    WLAYOUT_UP2, ConvDesc, PackItem, PackTileItem, _DT, _ptr, _require_cuda, _stream, check, lib
 from .seglabels import SegLabels
 
 _state = {"compute_dtype": torch.bfloat16 if os.environ.get("MAS_COMPUTE_DTYPE", "bf16") == "bf16" else torch.float32}
@@ -2388,4 +2388,98 @@ def seg_agreement(pred, target, out=None):
         raise ValueError("seg_agreement: out must be a SegAgreement of the labels' layout on their device")
     b, _, h, w = p_planes.shape
     check(lib().mas_seg_agreement(_ptr(p_planes), _ptr(t_planes), groups, ng, nv, b, h, w, _ptr(out.counts), _stream()), "seg_agreement")
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# VQ-IMG read-out: float images to pictures, squared error + SSIM, codebook usage (img_metrics.hip)
+# --------------------------------------------------------------------------- #
+def _check_image(x, what: str, name: str = "x"):
+    """a float image ``[N, C, H, W]`` the byte kernel takes (its device is the caller's to check, after every other argument)"""
+    from .imgmetrics import MAX_CHANNELS
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty tensor [N, C, H, W], got {tuple(getattr(x, 'shape', ()))}")
+    if x.dtype not in _DT:
+        raise RuntimeError(f"{what}: {name} dtype {x.dtype} not supported (float32 / bfloat16)")
+    if x.shape[1] > MAX_CHANNELS:
+        raise ValueError(f"{what}: {name} {tuple(x.shape)} has {x.shape[1]} channels (1 .. {MAX_CHANNELS})")
+
+
+def _image_bytes(x: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+    x, xl = _seg_dense(x.detach())
+    n, c, h, w = x.shape
+    out = torch.empty((n, h, w, c), dtype=torch.uint8, device=x.device)
+    check(lib().mas_img_bytes(_ptr(x), _DT[x.dtype], xl, n, c, h, w, lo, hi, _ptr(out), _stream()), "img_bytes")
+    return out
+
+
+def image_bytes(x: torch.Tensor, lo: float = -1.0, hi: float = 1.0) -> torch.Tensor:
+    """A float image ``[N, C, H, W]`` (fp32 or bf16, C in 1 .. 4) -> the picture ``uint8 [N, H, W, C]``, interleaved and contiguous: what an
+    image writer takes as it is (``mas_img_bytes``).  Per element in fp32, each operation rounded on its own: ``t = (x - lo) * s`` with
+    ``s = float32(255 / (hi - lo))``, clamped to 0 .. 255 (a NaN gives 0), rounded half to even.  Dense NCHW or channels_last memory is
+    read in place, once; anything else (a slice) is made dense first.  Nothing synchronises with the host."""
+    from .imgmetrics import byte_range
+    lo, hi = byte_range(lo, hi, "image_bytes")
+    _check_image(x, "image_bytes")
+    _require_cuda(x, "image_bytes")
+    return _image_bytes(x, lo, hi)
+
+
+def image_agreement(a: torch.Tensor, b: torch.Tensor, lo: float = -1.0, hi: float = 1.0):
+    """Squared error and SSIM between two batches of pictures -> ``mas_hip.imgmetrics.ImageAgreement`` (per image ``sse`` int64, ``ssim``
+    float64, ``elements``).  ``a`` and ``b`` are each a float image ``[N, C, H, W]`` (turned into bytes by ``image_bytes(., lo, hi)``) or
+    a ``uint8 [N, H, W, C]`` picture (taken as it is); the two need not share dtype or memory layout, only the picture's shape.  SSIM is
+    Wang et al. 2004 in its "valid" form on the bytes (11 x 11 Gaussian window, sigma 1.5, no padding), computed in fp64; NaN for pictures
+    smaller than the window.  The squared error is an integer: exact.  The same pictures give the same bits; no host synchronisation."""
+    from .imgmetrics import MAX_CHANNELS, ImageAgreement, byte_range, ssim_window
+    lo, hi = byte_range(lo, hi, "image_agreement")
+    pics = []
+    for name, t in (("a", a), ("b", b)):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.uint8:
+            if t.dim() != 4 or t.numel() == 0:
+                raise ValueError(f"image_agreement: the picture {name} must be a non-empty uint8 tensor [N, H, W, C], got {tuple(t.shape)}")
+            if t.shape[3] > MAX_CHANNELS:
+                raise ValueError(f"image_agreement: the picture {name} {tuple(t.shape)} has {t.shape[3]} channels (1 .. {MAX_CHANNELS})")
+            pics.append((tuple(t.shape), t))
+        else:
+            _check_image(t, "image_agreement", name)
+            n, c, h, w = t.shape
+            pics.append(((n, h, w, c), t))
+    (sa, ta), (sb, tb) = pics
+    if sa != sb or ta.device != tb.device:
+        raise ValueError(f"image_agreement: pictures [N, H, W, C] {sa} ({ta.device}) and {sb} ({tb.device}) differ")
+    _require_cuda(ta, "image_agreement")
+    pa, pb = (t.contiguous() if t.dtype == torch.uint8 else _image_bytes(t, lo, hi) for t in (ta, tb))
+    n, h, w, c = sa
+    dev = pa.device
+    tiles = lib().mas_img_agreement_blocks(n, c, h, w)
+    check(min(tiles, 0), "img_agreement_blocks")
+    sse = torch.zeros(n, dtype=torch.int64, device=dev)
+    ssim = torch.empty(n, dtype=torch.float64, device=dev)
+    partials = torch.empty(tiles, dtype=torch.float64, device=dev)
+    window = (C.c_double * IMG_SSIM_WINDOW)(*ssim_window())
+    check(lib().mas_img_agreement(_ptr(pa), _ptr(pb), n, c, h, w, window, _ptr(sse), _ptr(partials), tiles, _stream()), "img_agreement")
+    check(lib().mas_img_agreement_reduce(_ptr(partials), tiles, n, c, h, w, _ptr(ssim), _stream()), "img_agreement_reduce")
+    return ImageAgreement(sse, ssim, torch.full((n,), c * h * w, dtype=torch.int64, device=dev))
+
+
+def code_usage(indices: torch.Tensor, n_embed: int, out=None):
+    """How often each of ``n_embed`` codes occurs in ``indices`` (int64 or int32, any shape) -> ``mas_hip.imgmetrics.CodeUsage``
+    (``mas_code_usage``).  Indices outside ``[0, n_embed)`` are counted in the extra last slot and index nothing.  ``out``: a ``CodeUsage``
+    of the same size on the same device that the counts are ADDED to (and which is returned); without it a zeroed one is made.  Integer
+    counting: exact, the same in any order; no host synchronisation."""
+    from .imgmetrics import CodeUsage
+    if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.int64, torch.int32) or indices.numel() == 0:
+        raise ValueError(f"code_usage: indices must be a non-empty int64 or int32 tensor, got {getattr(indices, 'dtype', type(indices))} "
+                         f"{tuple(getattr(indices, 'shape', ()))}")
+    n_embed = int(n_embed)
+    if n_embed < 1:
+        raise ValueError(f"code_usage: n_embed = {n_embed} must be positive")
+    if out is not None and (not isinstance(out, CodeUsage) or out.n_embed != n_embed or out.counts.device != indices.device):
+        raise ValueError(f"code_usage: out must be a CodeUsage of {n_embed} codes on the indices' device")
+    _require_cuda(indices, "code_usage")
+    if out is None:
+        out = CodeUsage(n_embed, device=indices.device)
+    idx = indices.detach().contiguous()
+    check(lib().mas_code_usage(_ptr(idx), idx.element_size(), idx.numel(), n_embed, _ptr(out.counts), _stream()), "code_usage")
     return out

@@ -73,6 +73,37 @@ class VQBASE(nn.Module):
         quant, _ = self.encode(x)
         return SegLabels.from_logits(self.decode(quant), layout, thresholds)
 
+    @torch.no_grad()
+    def decode_to_images(self, code_b, lo=-1.0, hi=1.0):
+        """VQ-IMG tokens -> pictures ``uint8 [B, H, W, C]``: ``decode_code`` and then ``ops.image_bytes`` with the range ``[lo, hi]`` the
+        model was trained in.  ``eval()`` mode only, like ``decode_to_labels``."""
+        if self.training:
+            raise RuntimeError("decode_to_images: decode with the frozen model in eval() mode")
+        from mas_hip import ops
+        from mas_hip.imgmetrics import byte_range
+        lo, hi = byte_range(lo, hi, "decode_to_images")
+        return ops.image_bytes(self.decode_code(code_b), lo, hi)
+
+    @torch.no_grad()
+    def reconstruction_metrics(self, x, lo=-1.0, hi=1.0, usage=None):
+        """images ``x`` -> ``(ImageAgreement, CodeUsage)`` of their reconstruction (``mas_hip.imgmetrics``): one pass of encoder ->
+        quant_conv -> lookup, keeping the indices, then post_quant_conv -> decoder; ``ops.image_agreement(reconstruction, x, lo, hi)`` and
+        ``ops.code_usage(indices, n_embed, out=usage)`` -- pass the ``CodeUsage`` of the previous batch as ``usage`` to accumulate over a
+        validation set.  Nothing synchronises with the host.  ``eval()`` mode only."""
+        if self.training:
+            raise RuntimeError("reconstruction_metrics: measure the frozen model in eval() mode")
+        from mas_hip import ops
+        from mas_hip.imgmetrics import CodeUsage, byte_range
+        from mas_hip.seglabels import SegLabels
+        if isinstance(x, SegLabels):
+            raise TypeError("reconstruction_metrics: pictures only; for a segmentation map use reconstruct_labels + ops.seg_agreement")
+        lo, hi = byte_range(lo, hi, "reconstruction_metrics")
+        n_embed = self.quantize.codebook_size
+        if usage is not None and (not isinstance(usage, CodeUsage) or usage.n_embed != n_embed):
+            raise ValueError(f"reconstruction_metrics: usage must be a CodeUsage of the codebook's {n_embed} codes")
+        quant, _, idx = self.quantize(self.quant_conv(self.encoder(x)))
+        return ops.image_agreement(self.decode(quant), x, lo, hi), ops.code_usage(idx, n_embed, out=usage)
+
     def forward(self, input):
         quant, diff = self.encode(input)
         dec = self.decode(quant)

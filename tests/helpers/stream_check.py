@@ -91,11 +91,12 @@ def main():
         wp = ops.pack_conv_weight(wt.to(dev), False, torch.bfloat16)
         y = ops.conv_fwd_raw(cl(x), ss.to(dev) if act else None, wp, b.to(dev), cl(res) if has_res else None,
                              n, h, w, cin, ho, wo, cout, 3, 1, t, l, act, ups, torch.bfloat16)
+        kern = ops.last_kernel()
         torch.cuda.synchronize()
         err = float((y.float().cpu() - ref).abs().max() / ref.abs().max())
-        ok = err < 1e-2
+        ok = err < 1e-2 and kern == "conv3x3_stream"
         bad += not ok
-        print(("ok   " if ok else "FAIL ") + f"{case}: max-rel {err:.3e}", flush=True)
+        print(("ok   " if ok else "FAIL ") + f"{case}: max-rel {err:.3e} kernel {kern}", flush=True)
     # determinism: the same launch twice is bitwise identical (no order-dependent accumulation in this kernel)
     y2 = ops.conv_fwd_raw(cl(x), None, wp, b.to(dev), None, n, h, w, cin, ho, wo, cout, 3, 1, t, l, 0, ups, torch.bfloat16)
     y3 = ops.conv_fwd_raw(cl(x), None, wp, b.to(dev), None, n, h, w, cin, ho, wo, cout, 3, 1, t, l, 0, ups, torch.bfloat16)

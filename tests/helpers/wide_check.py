@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Runs in a child process of tests/test_gpu_wide.py with MAS_CONV_WIDE_MIN_TILES_PER_CU=0 (read once per process), so that
+"""Runs in a child process of tests/test_gpu_wide.py with MAS_CONV_WIDE_MIN_TILES_PER_CU=0 MAS_CONV_UP2=0 (read once per process), so that
 SMALL shapes take the wide 3x3 kernel (conv3x3_wide.hip: 16x32-pixel tiles, 32-channel chunks, K32 weight image) and can be
-compared with a CPU fp32 convolution of the same bf16-rounded operands.  Prints one line per case; exits non-zero on a mismatch.
+compared with a CPU fp32 convolution of the same bf16-rounded operands.  Prints one line per case; exits non-zero on a mismatch,
+or when a case ran another kernel (``ops.last_kernel()``; without MAS_CONV_UP2=0 the Upsample-fold cases take the sub-pixel kernel).
 
 `wide_check.py multi` (run with MAS_CONV_WGS_PER_CU=1: the grid is then ONE work-group per CU): shapes with MORE tiles than
 work-groups, so every work-group really walks 2-3 tiles through the persistent loop bench.py's B=32 launches run (next-tile plan,
@@ -106,12 +107,13 @@ def main():
         lay = ops._preferred_layout(d)
         y = ops.conv_fwd_raw(cl(x), ss.to(dev) if act else None, ops.ConvWeight(param.to(dev), tr), b.to(dev), cl(res) if has_res else None,
                              n, h, w, cin, ho, wo, cout, 3, 1, t, l, act, ups, torch.bfloat16)
+        kern = ops.last_kernel()                # (a preferred K32 layout is not enough: conv_fwd_raw turns an Upsample fold into the sub-pixel kernel when it may)
         torch.cuda.synchronize()
         err = float((y.float().cpu() - ref).abs().max() / ref.abs().max())
-        ok = err < 1e-2 and lay == mas_hip.WLAYOUT_K32
+        ok = err < 1e-2 and lay == mas_hip.WLAYOUT_K32 and kern == "conv3x3_wide"
         extra = ""
         bad += not ok
-        print(("ok   " if ok else "FAIL ") + f"{case}: max-rel {err:.3e} layout {'K32 (wide kernel)' if lay else 'K64 (NOT the wide kernel)'}" + extra, flush=True)
+        print(("ok   " if ok else "FAIL ") + f"{case}: max-rel {err:.3e} layout {'K32 (wide kernel)' if lay else 'K64 (NOT the wide kernel)'} kernel {kern}" + extra, flush=True)
     # determinism: the same launch twice is bitwise identical
     y2 = ops.conv_fwd_raw(cl(x), None, ops.ConvWeight(param.to(dev), tr), b.to(dev), None, n, h, w, cin, ho, wo, cout, 3, 1, t, l, 0, ups, torch.bfloat16)
     y3 = ops.conv_fwd_raw(cl(x), None, ops.ConvWeight(param.to(dev), tr), b.to(dev), None, n, h, w, cin, ho, wo, cout, 3, 1, t, l, 0, ups, torch.bfloat16)

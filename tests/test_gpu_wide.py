@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_wide_kernel_small_shapes_vs_cpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    env = dict(os.environ, MAS_CONV_WIDE_MIN_TILES_PER_CU="0", MAS_CONV_WIDE_ANY_WIDTH="1")
+    # (MAS_CONV_UP2=0: the helper's Upsample-fold cases would otherwise take the sub-pixel kernel, which has tests/test_gpu_up2.py)
+    env = dict(os.environ, MAS_CONV_WIDE_MIN_TILES_PER_CU="0", MAS_CONV_WIDE_ANY_WIDTH="1", MAS_CONV_UP2="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "wide_check.py")], env=env,
                        capture_output=True, text=True, timeout=600)
     print(r.stdout[-4000:])
@@ -31,7 +32,7 @@ def test_wide_kernel_persistent_multi_tile_walk_vs_cpu():
     change mid-walk, cross-tile DMA, vmcnt(32) store wait.  The helper asserts tiles > grid from the launch geometry."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    env = dict(os.environ, MAS_CONV_WIDE_MIN_TILES_PER_CU="0", MAS_CONV_WIDE_ANY_WIDTH="1", MAS_CONV_WGS_PER_CU="1")
+    env = dict(os.environ, MAS_CONV_WIDE_MIN_TILES_PER_CU="0", MAS_CONV_WIDE_ANY_WIDTH="1", MAS_CONV_UP2="0", MAS_CONV_WGS_PER_CU="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "wide_check.py"), "multi"], env=env,
                        capture_output=True, text=True, timeout=900)
     print(r.stdout[-4000:])

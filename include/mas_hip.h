@@ -165,6 +165,23 @@ int    mas_adam_multi_ema(const MasAdamItem* items_device, float* const* ema_dev
                           const float* grad_scale_device, int decoupled_wd, float ema_decay, const float* grad_norm_device, void* stream);
 int    mas_swap_multi(const MasAdamItem* items_device, float* const* other_device, int n_items, int total_blocks, void* stream);
 
+/* ---- The Adam step with everything that changes from step to step read from DEVICE memory, so that the launches can be captured into a
+ * graph once and replayed (additions under ABI 10).
+ *   mas_adam_multi_dev: mas_adam_multi_ema with the learning rate (*lr_device, fp32), the step count of item i (*step_device[i], fp32: the
+ *     number of steps ALREADY taken, so this step is t = *step_device[i] + 1; one pointer per item beside the table, like ema_device) and the
+ *     EMA counter (*ema_count_device, fp32) read on the device.  Two launches: a small one (one thread per item) writes item i's record
+ *     scalars_device[4 i ..] = {(float)(lr / (1 - beta1^t)), (float)sqrt(1 - beta2^t), lr, ema_w}, the powers, the division and the root in
+ *     fp64 from the fp64 betas as the host entries' callers form them; the Adam launch reads its item's record.  scalars_device: 4 n_items
+ *     floats, 16-byte aligned, owned by the caller.  ema_w = 1 - (float)ema_decay, or with ema_count_device non-NULL
+ *     1 - (float)min(ema_decay, (1 + k) / (10 + k)), k = *ema_count_device.  ema_device, grad_scale_device, decoupled_wd and
+ *     grad_norm_device are mas_adam_multi_ema's.  The entry advances nothing.
+ *   mas_adam_advance_dev: counters[0 .. n) += 1 (fp32), one launch, to be issued BEHIND the step's Adam launches.                       */
+int    mas_adam_multi_dev(const MasAdamItem* items_device, float* const* ema_device, const float* const* step_device, int n_items,
+                          int total_blocks, const float* lr_device, double beta1, double beta2, float eps, float weight_decay,
+                          const float* grad_scale_device, int decoupled_wd, double ema_decay, const float* ema_count_device,
+                          const float* grad_norm_device, float* scalars_device, void* stream);
+int    mas_adam_advance_dev(float* counters, int n, void* stream);
+
 /* ---- GroupNorm statistics (replaces the reduction half of torch.nn.GroupNorm,
  * modules.py:40-41).  x: [N,HW,C] NHWC.  Outputs:
  *   mean_rstd [N][G][2] fp32, scale_shift [N][C][2] fp32 with

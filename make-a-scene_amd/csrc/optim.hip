@@ -46,12 +46,15 @@ __device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x)
 //   loaded with p, g, m, v and stored with p, m, v.  Five 4 x float4 arrays are 80 data registers: 120 / 122 VGPRs and four waves per SIMD
 //   (the other instantiations: 94 and five).  EMA_GROUPS = 2 (two halves of 2 x float4 per tensor) is 96 VGPRs and five waves with half
 //   the loads in flight per lane.
+// DEV: the instantiations behind mas_adam_multi_dev (always with EMA).  step_size, sqrt(bc2), lr and ema_w come from item idx's record of
+//   four floats in `dev` (written by adam_dev_scalars_kernel in front of this launch) instead of the arguments: one uniform 16-byte load per
+//   work-group.  Everything below that load is the code of the other instantiations.
 constexpr int EMA_GROUPS = 4;
-template <bool SCALE, bool DECOUPLED, bool EMA>
+template <bool SCALE, bool DECOUPLED, bool EMA, bool DEV = false>
 __global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* __restrict__ items, int n_items, float step_size, float inv_bc2_sqrt,
                                                              float b1, float b2, float eps, float wd,     // (inv_bc2_sqrt: sqrt(bias_correction2) itself)
                                                              const float* __restrict__ grad_scale, float lr, float* const* __restrict__ ema,
-                                                             float ema_w, const float* __restrict__ grad_norm) {
+                                                             float ema_w, const float* __restrict__ grad_norm, const float* __restrict__ dev) {
     const int b = blockIdx.x;
     if constexpr (EMA) {
         if (grad_norm != nullptr && not_finite(*grad_norm)) return;
@@ -59,6 +62,10 @@ __global__ __launch_bounds__(ADAM_NT) void adam_multi_kernel(const MasAdamItem* 
     const int idx = item_index_of_block(items, n_items, b);
     const MasAdamItem it = items[idx];
     const long long base = (long long)(b - it.first_block) * ADAM_PER_BLOCK;
+    if constexpr (DEV) {
+        const f32x4 s = *reinterpret_cast<const f32x4*>(dev + 4 * (long long)idx);
+        step_size = s[0]; inv_bc2_sqrt = s[1]; lr = s[2]; ema_w = s[3];
+    }
     const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
     float gs = 1.0f;
     if constexpr (SCALE) gs = *grad_scale;
@@ -245,24 +252,61 @@ __global__ __launch_bounds__(ADAM_NT) void swap_multi_kernel(const MasAdamItem* 
     }
 }
 
+// ---- the step on the device ---------------------------------------------------------------------------------------------------------
+// One thread per item, in front of the Adam launch of mas_adam_multi_dev: rec[4 i ..] = {step_size, sqrt(bc2), lr, ema_w} of item i from its
+// step count on the device (t = *step[i] + 1: the count is advanced AFTER the step), the learning rate on the device and the EMA counter k
+// on the device.  The formulas and their precision are adam_launch's on the host: bc = 1 - beta^t in fp64 from the caller's fp64 betas,
+// step_size = (float)(lr / bc1), (float)sqrt(bc2); ema_w = 1 - (float)min(d, (1 + k) / (10 + k)) with the minimum in fp64 and the
+// subtraction in fp32 (mas_adam_multi_ema's 1.0f - ema_decay).  Two fp64 pow per parameter and step, not two per work-group: the Adam
+// kernel keeps its registers, and a model of 150 tensors computes 300 powers instead of two in each of its tens of thousands of work-groups.
+__global__ __launch_bounds__(ADAM_NT) void adam_dev_scalars_kernel(const float* const* __restrict__ step, int n_items, const float* __restrict__ lr_dev,
+                                                                   double b1, double b2, double ema_decay, const float* __restrict__ ema_count,
+                                                                   float* __restrict__ rec) {
+    const int i = blockIdx.x * ADAM_NT + threadIdx.x;
+    if (i >= n_items) return;
+    const double t = (double)*step[i] + 1.0;
+    const float lr = *lr_dev;
+    double d = ema_decay;
+    if (ema_count != nullptr) {
+        const double k = (double)*ema_count, w = (1.0 + k) / (10.0 + k);
+        d = w < d ? w : d;
+    }
+    f32x4 r;
+    r[0] = (float)((double)lr / (1.0 - pow(b1, t)));
+    r[1] = (float)sqrt(1.0 - pow(b2, t));
+    r[2] = lr;
+    r[3] = 1.0f - (float)d;
+    *reinterpret_cast<f32x4*>(rec + 4 * (long long)i) = r;
+}
+
+// counters[i] += 1 (fp32: exact up to 2^24 steps, torch's own `step` tensors are fp32 too).  A launch of its own BEHIND the step's Adam
+// launches: no work-group reads a counter that another one is writing (mas_decode_advance is the precedent).
+__global__ __launch_bounds__(ADAM_NT) void adam_advance_dev_kernel(float* __restrict__ counters, int n) {
+    const int i = blockIdx.x * ADAM_NT + threadIdx.x;
+    if (i < n) counters[i] += 1.0f;
+}
+
 }  // namespace
 
 extern "C" int mas_adam_blocks(long long numel) { return numel <= 0 ? 0 : (int)((numel + ADAM_PER_BLOCK - 1) / ADAM_PER_BLOCK); }
 
 namespace {
 
-template <bool SCALE, bool DECOUPLED, bool EMA = false>
+// DEV: `dev_scalars` (4 floats per item, device) replaces lr / the bias corrections / ema_w, none of which is read; the caller has issued
+// adam_dev_scalars_kernel on the same stream
+template <bool SCALE, bool DECOUPLED, bool EMA = false, bool DEV = false>
 int adam_launch(const char* name, const MasAdamItem* items_device, int n_items, int total_blocks, float lr, float beta1, float beta2, float eps,
                 float weight_decay, double bias_correction1, double bias_correction2, const float* grad_scale_device, void* stream,
-                float* const* ema_device = nullptr, float ema_w = 0.0f, const float* grad_norm_device = nullptr) {
+                float* const* ema_device = nullptr, float ema_w = 0.0f, const float* grad_norm_device = nullptr,
+                const float* dev_scalars = nullptr) {
     MAS_ENTER();
     if (!items_device || n_items <= 0 || total_blocks <= 0) MAS_FAIL(MAS_EINVAL, "%s: empty batch", name);
     if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) MAS_FAIL(MAS_EINVAL, "%s: bias corrections must be positive (step >= 1)", name);
     const float step_size = (float)((double)lr / bias_correction1);
     const float inv_bc2_sqrt = (float)sqrt(bias_correction2);      // (passed as the divisor, like torch's bias_correction2_sqrt)
-    hipLaunchKernelGGL((adam_multi_kernel<SCALE, DECOUPLED, EMA>), dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((adam_multi_kernel<SCALE, DECOUPLED, EMA, DEV>), dim3((unsigned)total_blocks), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
                        items_device, n_items, step_size, inv_bc2_sqrt, beta1, beta2, eps, weight_decay, grad_scale_device, lr, ema_device, ema_w,
-                       grad_norm_device);
+                       grad_norm_device, dev_scalars);
     MAS_CHECK_LAUNCH(name);
     return MAS_OK;
 }
@@ -304,6 +348,37 @@ extern "C" int mas_adam_multi_ema(const MasAdamItem* items_device, float* const*
     if (grad_scale_device) return dec ? MAS_ADAM_EMA(true, true) : MAS_ADAM_EMA(true, false);
     return dec ? MAS_ADAM_EMA(false, true) : MAS_ADAM_EMA(false, false);
 #undef MAS_ADAM_EMA
+}
+
+extern "C" int mas_adam_multi_dev(const MasAdamItem* items_device, float* const* ema_device, const float* const* step_device, int n_items,
+                                  int total_blocks, const float* lr_device, double beta1, double beta2, float eps, float weight_decay,
+                                  const float* grad_scale_device, int decoupled_wd, double ema_decay, const float* ema_count_device,
+                                  const float* grad_norm_device, float* scalars_device, void* stream) {
+    MAS_ENTER();
+    if (!items_device || !step_device || !lr_device || !scalars_device || n_items <= 0 || total_blocks <= 0)
+        MAS_FAIL(MAS_EINVAL, "adam_multi_dev: null or empty arguments");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) MAS_FAIL(MAS_EINVAL, "adam_multi_dev: betas must be in [0, 1)");
+    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) MAS_FAIL(MAS_EINVAL, "adam_multi_dev: ema_decay must be in [0, 1)");
+    if ((reinterpret_cast<uintptr_t>(scalars_device) & 15) != 0) MAS_FAIL(MAS_EINVAL, "adam_multi_dev: scalars_device must be 16-byte aligned");
+    hipLaunchKernelGGL(adam_dev_scalars_kernel, dim3((unsigned)((n_items + ADAM_NT - 1) / ADAM_NT)), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
+                       step_device, n_items, lr_device, beta1, beta2, ema_decay, ema_count_device, scalars_device);
+    MAS_CHECK_LAUNCH("adam_multi_dev (scalars)");
+    const bool dec = decoupled_wd != 0;
+    // (bias corrections of 1: only adam_launch's argument check reads them; the kernel takes its scalars from scalars_device)
+#define MAS_ADAM_DEV(S, D) adam_launch<S, D, true, true>("adam_multi_dev", items_device, n_items, total_blocks, 0.0f, (float)beta1, (float)beta2, eps, \
+                                                         weight_decay, 1.0, 1.0, grad_scale_device, stream, ema_device, 0.0f, grad_norm_device, scalars_device)
+    if (grad_scale_device) return dec ? MAS_ADAM_DEV(true, true) : MAS_ADAM_DEV(true, false);
+    return dec ? MAS_ADAM_DEV(false, true) : MAS_ADAM_DEV(false, false);
+#undef MAS_ADAM_DEV
+}
+
+extern "C" int mas_adam_advance_dev(float* counters, int n, void* stream) {
+    MAS_ENTER();
+    if (!counters || n <= 0) MAS_FAIL(MAS_EINVAL, "adam_advance_dev: null or empty arguments");
+    hipLaunchKernelGGL(adam_advance_dev_kernel, dim3((unsigned)((n + ADAM_NT - 1) / ADAM_NT)), dim3(ADAM_NT), 0, reinterpret_cast<hipStream_t>(stream),
+                       counters, n);
+    MAS_CHECK_LAUNCH("adam_advance_dev");
+    return MAS_OK;
 }
 
 extern "C" int mas_swap_multi(const MasAdamItem* items_device, float* const* other_device, int n_items, int total_blocks, void* stream) {

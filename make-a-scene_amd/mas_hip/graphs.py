@@ -1,0 +1,190 @@
+"""``GraphedTrainStep``: a whole training step -- zero_grad, the refresh of stale weight images and bf16 shadows, forward, backward,
+``optimizer.step()`` -- captured once into ONE graph and replayed, so that a step costs the host one graph launch instead of the
+~1200 kernel launches of a stage-2 step.  Opt-in; nothing else in the package changes behaviour.
+
+    opt  = mas_hip.optim.AdamW(model.parameters(), lr=4.5e-4, device_step=True)
+    step = mas_hip.graphs.GraphedTrainStep(lambda t, s, i: model.token_loss(t, s, i), opt, (text, seg, img),
+                                           amp_dtype=torch.bfloat16, modules=[model])
+    for text, seg, img in loader:
+        loss = step(text, seg, img)          # copies the inputs into the static ones, replays; the static 0-dim loss, no host read
+
+What it needs and what it does:
+
+* the optimizer is ``mas_hip.optim.Adam`` / ``AdamW`` with ``device_step=True`` (its step count, bias corrections, learning rate and
+  EMA counter live on the device; anything else raises here).
+* CONSTRUCTION TRAINS: it runs ``warmup >= 1`` real training steps on ``example_inputs`` on a side stream (they settle the GEMM choices,
+  every workspace and the optimizer state), then captures the step there.  The capture itself executes nothing.
+* warm-up and capture run under ``torch.autocast("cuda", amp_dtype, cache_enabled=False)`` when ``amp_dtype`` is given (autocast off
+  otherwise), and with the convolution weight-gradient side stream off (``ops.wgrad_stream_off``): the graph is one stream without branches.
+* the stamps of the weight caches are made stale just before the capture, so the refresh launches are part of the graph even when the
+  caches happen to be fresh; every replay recomputes them from the weights of that moment.  The graph keeps the cached images it reads
+  alive, and after every replay the caches are told that the weights moved (what the optimizer's post-step hook does), so an eager
+  forward, ``generate()``, ``swap_ema()`` or a checkpoint between replays sees the current weights.
+* before every replay, on the host: ``optimizer.sync_hyperparameters()`` (a changed learning rate reaches the device without a new
+  capture), and a comparison of what the capture baked in -- ``optimizer.state_generation``, ``betas`` / ``eps`` / ``weight_decay``, the
+  clip / EMA / guard settings, the inputs' shapes and dtypes, the compute dtype, ``training`` of every module under ``modules=`` --
+  with what is there now.  When one differs the step is RECAPTURED lazily (no warm-up step runs then: a recapture changes no value);
+  ``step.captures`` counts captures.
+* dropout needs nothing: its ``{seed, offset}`` is drawn by ``torch.randint`` on the device, and a replay advances the generator.
+* the returned loss is the graph's static tensor: the next call overwrites it.
+* ``nn.Embedding`` lookups of more than a few thousand indices must go through ``graphs.embedding(module, idx)`` (``MakeAScene`` does):
+  ATen's backward for them reads a count on the host and faults when replayed.  Under a capture the helper sums ATen's dense backward
+  over slices of the indices, so a replayed step differs from an eager one in the order of those additions -- and not at all inside
+  ``graphs.embedding_grad_in_chunks()``.
+
+Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collectives run on other streams; ``reducer=`` raises), gradient
+accumulation across calls (every replay starts from ``zero_grad``), inputs that are not tensors, and a ``loss_fn`` that reads anything on
+the host."""
+import contextlib
+
+import torch
+import torch.nn.functional as F
+
+from . import ops, optim
+
+# nn.Embedding's backward cannot be captured beyond a few thousand indices: above 3072 of them ATen sorts the indices and counts the
+# distinct ones with a thrust call that hands the count to the HOST (on ROCm; its fast kernel covers the smaller cases), so a capture
+# bakes in whatever the host read without the kernel having run, and the replay faults.  Below, the same ATen backward is called on
+# slices of at most this many indices -- the size every slice of which takes the fast kernel -- and the slices' dense results are added.
+EMBEDDING_GRAD_CHUNK = 2048
+_chunks_always = False
+
+
+class _EmbeddingGradInChunks(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, idx):
+        ctx.save_for_backward(idx)
+        ctx.rows = weight.shape[0]
+        return F.embedding(idx, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        flat, g = idx.reshape(-1), dy.reshape(-1, dy.shape[-1])
+        total = None
+        for a in range(0, flat.numel(), EMBEDDING_GRAD_CHUNK):
+            part = torch.ops.aten.embedding_dense_backward(g[a:a + EMBEDDING_GRAD_CHUNK], flat[a:a + EMBEDDING_GRAD_CHUNK], ctx.rows, -1, False)
+            total = part if total is None else total.add_(part)
+        return total, None
+
+
+def embedding(module, idx):
+    """``module(idx)`` for an ``nn.Embedding``, with a backward that a graph can capture at any number of indices: under a capture (or
+    inside ``embedding_grad_in_chunks()``) and above ``EMBEDDING_GRAD_CHUNK`` indices the weight gradient is the sum of ATen's own dense
+    backward over slices of the indices -- the eager result up to the order of the additions.  Everywhere else it IS ``module(idx)``."""
+    if not (idx.is_cuda and idx.numel() > EMBEDDING_GRAD_CHUNK and torch.is_grad_enabled() and module.weight.requires_grad
+            and (_chunks_always or torch.cuda.is_current_stream_capturing())):
+        return module(idx)
+    if module.padding_idx is not None or module.max_norm is not None or module.scale_grad_by_freq or module.sparse:
+        raise NotImplementedError("mas_hip.graphs.embedding: padding_idx / max_norm / scale_grad_by_freq / sparse embeddings cannot be "
+                                  f"captured above {EMBEDDING_GRAD_CHUNK} indices")
+    return _EmbeddingGradInChunks.apply(module.weight, idx)
+
+
+@contextlib.contextmanager
+def embedding_grad_in_chunks():
+    """inside, ``embedding()`` takes its capture-safe backward in eager code too: what a replayed step computes, step by step"""
+    global _chunks_always
+    old, _chunks_always = _chunks_always, True
+    try:
+        yield
+    finally:
+        _chunks_always = old
+
+
+class GraphedTrainStep:
+    def __init__(self, loss_fn, optimizer, example_inputs, *, amp_dtype=None, warmup=1, modules=(), reducer=None):
+        if reducer is not None:
+            raise NotImplementedError("GraphedTrainStep: a gradient reducer runs collectives on other streams, which one captured stream "
+                                      "cannot hold; train data-parallel runs eagerly")
+        if not isinstance(optimizer, optim.Adam) or not optimizer.device_step:
+            raise TypeError("GraphedTrainStep: the optimizer must be mas_hip.optim.Adam / AdamW with device_step=True (a step whose count, "
+                            f"bias corrections and learning rate live on the device), got {type(optimizer).__name__}"
+                            + ("" if not isinstance(optimizer, optim.Adam) else " with device_step=False"))
+        if int(warmup) < 1:
+            raise ValueError("GraphedTrainStep: warmup must be at least 1 (the capture needs every buffer and GEMM choice settled)")
+        if isinstance(example_inputs, torch.Tensor):
+            example_inputs = (example_inputs,)
+        self.loss_fn, self.optimizer, self.amp_dtype = loss_fn, optimizer, amp_dtype
+        self.modules = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
+        self.captures = 0
+        self.graph = self.loss = self._sig = self._keep = None
+        self._check_inputs(example_inputs)
+        self._side = torch.cuda.Stream(device=example_inputs[0].device)
+        self._static = [x.detach().clone() for x in example_inputs]
+        self._capture(int(warmup))
+
+    @staticmethod
+    def _check_inputs(inputs):
+        if not inputs or not all(isinstance(x, torch.Tensor) and x.is_cuda for x in inputs):
+            raise TypeError("GraphedTrainStep: the inputs must be CUDA tensors")
+
+    def _autocast(self):
+        if self.amp_dtype is None:
+            return torch.autocast("cuda", enabled=False, cache_enabled=False)
+        return torch.autocast("cuda", dtype=self.amp_dtype, cache_enabled=False)
+
+    def _signature(self, inputs):
+        """everything a capture bakes in that the host can still change"""
+        opt = self.optimizer
+        return (opt.state_generation,
+                tuple((tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), len(g["params"])) for g in opt.param_groups),
+                opt.max_grad_norm, opt.ema_decay, opt.ema_warmup, opt.skip_nonfinite, ops.compute_dtype(),
+                tuple((tuple(x.shape), x.dtype, x.device) for x in inputs),
+                tuple(m.training for mod in self.modules for m in mod.modules()))
+
+    def _train_step(self):
+        self.optimizer.zero_grad(set_to_none=True)
+        loss = self.loss_fn(*self._static)
+        loss.backward()
+        self.optimizer.step()
+        return loss
+
+    def _capture(self, warmup):
+        opt = self.optimizer
+        self.graph = self.loss = None                       # (a recapture: the old graph's memory goes first)
+        main = torch.cuda.current_stream(self._side.device)
+        opt.init_state()
+        self._side.wait_stream(main)
+        with contextlib.ExitStack() as stack:
+            stack.enter_context(torch.cuda.stream(self._side))
+            stack.enter_context(ops.wgrad_stream_off())
+            with self._autocast():
+                for _ in range(warmup):
+                    self._train_step()
+            opt.zero_grad(set_to_none=True)
+            opt.init_state()
+            ops._note_optimizer_step(opt)                   # every derived copy of a parameter is stale now: its refresh gets captured
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=self._side), self._autocast():
+                loss = self._train_step()
+        main.wait_stream(self._side)
+        # the images the graph reads: kept alive here (invalidate_weight_cache() / swap_ema() drop the caches' own references)
+        self._keep = [e[2] for e in ops._bf16_shadows.params.values()] + [e[2] for e in ops._pack_cache.store.values()] + \
+                     [e[2] for e in ops._pack_cache.derived.values()]
+        # nothing ran, but the caches stamped as fresh whatever they "refreshed" inside the capture (this model's images and any other stale
+        # one in the process): none of those stamps describes a refresh that happened
+        for e in ops._bf16_shadows.params.values():
+            e[1] = None
+        for e in ops._pack_cache.store.values():
+            e[1] = None
+        ops._pack_cache.derived.clear()
+        self.graph, self.loss = graph, loss.detach()
+        self._sig = self._signature(self._static)
+        self.captures += 1
+
+    def __call__(self, *inputs):
+        self._check_inputs(inputs)
+        if self._signature(inputs) != self._sig:
+            if len(inputs) != len(self._static) or any(x.shape != s.shape or x.dtype != s.dtype or x.device != s.device
+                                                       for x, s in zip(inputs, self._static)):
+                self.graph = self.loss = None
+                self._static = [x.detach().clone() for x in inputs]
+            self._capture(0)
+        self.optimizer.sync_hyperparameters()
+        for s, x in zip(self._static, inputs):
+            if x is not s:
+                s.copy_(x, non_blocking=True)
+        self.graph.replay()
+        ops._note_optimizer_step(self.optimizer)
+        return self.loss

@@ -706,6 +706,18 @@ def zero_stuff2x(x, hout, wout):
 # reissues a side-pool block only to a later side-stream allocation, which is made behind that node's ``side.wait_stream(current)`` on the
 # same host thread -- after the join that followed every earlier use.
 _WGRAD_STREAM = os.environ.get("MAS_WGRAD_STREAM", "1") == "1"
+
+
+@contextlib.contextmanager
+def wgrad_stream_off():
+    """Inside, every weight gradient stays on the current stream whatever MAS_WGRAD_STREAM says (and ``wgrad_cus()`` is 0): what is
+    captured into a graph there is one stream without branches (``mas_hip.graphs``)."""
+    global _WGRAD_STREAM
+    old, _WGRAD_STREAM = _WGRAD_STREAM, False
+    try:
+        yield
+    finally:
+        _WGRAD_STREAM = old
 # The CU budget of the weight-gradient grid (``MasConvDesc.wgrad_cus``: 0 = all CUs, -1 = three quarters, n > 0 = n), per device.
 # MAS_WGRAD_CUS, read once here, is the user's override.  Otherwise -1 while the side stream is on -- with a persistent work-group on every
 # CU the tiny finalize launch between the two GroupNorm passes is not placed until the weight gradient retires -- and 0 for a device whose

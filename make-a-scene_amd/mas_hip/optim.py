@@ -1,7 +1,8 @@
 """``mas_hip.optim.Adam``: torch.optim.Adam's update (reference train.py:99-103) for fp32 CUDA parameters as ONE kernel launch per
 step over all parameters of all groups that share hyper-parameters (``mas_adam_multi``).  Same arithmetic, same state layout
 (``state[p] = {"step", "exp_avg", "exp_avg_sq"}``: ``state_dict()`` / ``load_state_dict()`` interchange with torch.optim.Adam), same
-constructor arguments; ``amsgrad`` / ``maximize`` / ``capturable`` / ``differentiable`` are not implemented and raise.
+constructor arguments; ``amsgrad`` / ``maximize`` / ``capturable`` / ``differentiable`` are not implemented and raise (what
+``capturable=True`` is asked for -- a step that a graph can capture -- is ``device_step=True`` here: see below).
 
 It is a ``torch.optim.Optimizer``: the process-wide post-step hook of ``mas_hip.ops`` sees its steps, so packed weight images and
 bf16 shadows are refreshed exactly as with torch's optimizers.  Parameters that are not fp32 CUDA tensors (none in the reference's
@@ -32,7 +33,29 @@ which are identical across ranks.
 ``max_grad_norm``), the Adam launch reads the norm on the device and stores nothing when it is not finite, so ``p``, both moments and the
 average keep their bits.  Nothing is read on the host: ``opt.grad_norm`` is set as with clipping, ``opt.step_skipped`` computes a 0-dim
 bool device tensor when asked, and ``state["step"]`` advances on a skipped step too -- the bias corrections run one step ahead after a
-skip."""
+skip.
+
+``device_step=True`` (keyword only, off by default) keeps everything that changes from step to step on the device, so that ``step()`` can
+be captured into a graph and replayed (``mas_hip.graphs.GraphedTrainStep``), and an eager step reads nothing on the host either:
+
+* ``state[p]["step"]`` is a 0-dim fp32 device tensor -- the layout of ``torch.optim.Adam(capturable=True / fused=True)``, with which
+  ``state_dict()`` interchanges -- and all of them are views into ONE fp32 vector, element 0 of which is ``ema_warmup``'s counter ``k``; one
+  ``mas_adam_advance_dev`` launch behind the Adam launches adds 1 to all of them (a step skipped by ``skip_nonfinite`` advances them too).
+  ``param_groups[0]["ema_step"]`` is filled from the vector in ``state_dict()`` only: one host read, never under a capture.
+* the kernel (``mas_adam_multi_dev``) reads ``lr`` from a device fp32 scalar per group and forms the bias corrections from the device step
+  count.  ``group["lr"]`` stays what the caller put there (a float or a 0-dim tensor: LR schedulers work unchanged);
+  ``sync_hyperparameters()`` pushes changed values to the device scalars on the current stream (a no-op when nothing changed; every eager
+  ``step()`` calls it; it never runs under a capture, where a copy node would rewrite the old value at every replay -- whoever replays
+  calls it before).  ``betas``, ``eps`` and ``weight_decay`` are launch arguments: a change after a capture needs a new capture.
+* ``init_state()`` creates the state of every parameter and every buffer a step needs (moments, average, step vector, norm buffers, the
+  staging memory of a capture's tables); ``step()`` under a capture raises when something is missing instead of allocating what a replay
+  would not re-create.  Tables uploaded under a capture get memory of their own that is never rewritten or freed while the optimizer lives.
+* there is no torch-expression path: a parameter that is not a contiguous fp32 CUDA tensor with an fp32 gradient raises at ``step()``, and
+  all parameters live on one device.
+* ``load_state_dict()`` copies the loaded values INTO the existing state tensors where shapes match (storage does not move: a captured graph
+  stays valid), and like ``add_param_group()`` bumps ``opt.state_generation``.
+
+``max_grad_norm``, ``ema_decay``, ``ema_warmup``, ``skip_nonfinite``, ``swap_ema()`` and ``ema_state_dict()`` mean what they mean without it."""
 import contextlib
 import ctypes as C
 import math
@@ -132,15 +155,25 @@ def _norm_coef_launches(tables, out, partials, extra, max_norm, stream):
                                    0 if extra is None else extra.numel(), max_norm, C.c_void_p(out.data_ptr()), stream), "grad_clip_coef")
 
 
+_ARENA_ALIGN = 256
+
+
 class Adam(torch.optim.Optimizer):
     _decoupled_wd = 0
+    state_generation = 0             # bumped by load_state_dict() and add_param_group(): whoever holds a captured step compares it
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, maximize=False,
                  capturable=False, differentiable=False, fused=None, foreach=None, max_grad_norm=None, ema_decay=None, ema_warmup=False,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, device_step=False):
         name = f"mas_hip.optim.{type(self).__name__}"
         if amsgrad or maximize or capturable or differentiable:
-            raise NotImplementedError(f"{name}: amsgrad / maximize / capturable / differentiable are not implemented")
+            raise NotImplementedError(f"{name}: amsgrad / maximize / capturable / differentiable are not implemented"
+                                      + (" (a step that a graph can capture is device_step=True)" if capturable else ""))
+        self.device_step = bool(device_step)        # an attribute like max_grad_norm: state_dict() stays torch.optim.Adam's
+        self._dev = None                            # device_step: the step vector, the lr scalars and the launch buffers (_dev_prepare)
+        self._lr_pushed = None                      # the learning rates the device scalars hold
+        self._lr_staging = []                       # [pinned buffer, event of its last copy]
+        self._arenas = []                           # capture-time tables: [pinned bytes, device bytes, bytes used], never rewritten or freed
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or not 0.0 <= weight_decay:
             raise ValueError(f"{name}: invalid hyper-parameter")
         # (an attribute, not a key of `defaults`: the clip is global over all groups, and state_dict() stays torch.optim.Adam's)
@@ -250,6 +283,9 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.device_step:
+            self._step_dev()
+            return loss
         decay = self._ema_decay_now()
         if self.max_grad_norm is not None or self.skip_nonfinite:
             self._clipped_step(decay)
@@ -326,6 +362,239 @@ class Adam(torch.optim.Optimizer):
         if skip is not None:
             for x, o in zip([p] + held, old):
                 x.copy_(torch.where(skip.to(x.device), o, x))
+
+    # ---- device_step=True ------------------------------------------------------------------------------------------------------------
+    def _who(self):
+        return f"mas_hip.optim.{type(self).__name__}(device_step=True)"
+
+    def _dev_prepare(self, create):
+        """The buffers of the device path -- the vector of counters (element 0: ``ema_warmup``'s ``k``, element 1 + i: the step count of the
+        i-th parameter in group order), one learning rate per group, four launch scalars per parameter, the norm launches' output and partial
+        sums -- made when missing or when parameters or groups were added (the counters move over; ``create`` False, under a capture: raises)."""
+        params = [p for group in self.param_groups for p in group["params"]]
+        d = self._dev
+        if d is not None and d["n"] == len(params) and d["n_groups"] == len(self.param_groups):
+            return d
+        for i, p in enumerate(params):
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError(f"{self._who()}: parameter {i} of shape {tuple(p.shape)} ({p.dtype}, {p.device}"
+                                   f"{'' if p.is_contiguous() else ', not contiguous'}) is not a contiguous fp32 CUDA tensor; this mode has no other path")
+        devices = sorted({str(p.device) for p in params})
+        if len(devices) != 1:
+            raise NotImplementedError(f"{self._who()}: the parameters must live on one device, got {devices}")
+        if not create:
+            raise RuntimeError(f"{self._who()}: step() under a graph capture before init_state(): the step vector does not exist yet")
+        device = params[0].device
+        vec = torch.zeros(1 + len(params), dtype=torch.float32, device=device)
+        if d is not None:
+            vec[:1 + d["n"]].copy_(d["vec"])                 # (add_param_group appends: the slots of the old parameters stay)
+        elif self.ema_decay is not None:
+            vec[0] = float(self.param_groups[0].get("ema_step", 0))
+        out = torch.zeros(2, dtype=torch.float32, device=device)
+        self._clip_out[device] = out
+        blocks = sum(lib().mas_adam_blocks(p.numel()) for p in params)
+        self._dev = d = dict(n=len(params), n_groups=len(self.param_groups), device=device, vec=vec, views=[vec[1 + i] for i in range(len(params))],
+                             slot={p: i for i, p in enumerate(params)}, lr=torch.zeros(len(self.param_groups), dtype=torch.float32, device=device),
+                             scalars=torch.zeros(4 * len(params), dtype=torch.float32, device=device), out=out, norm=out[0], coef=out[1],
+                             partials=_partials(self._clip_bufs, device, blocks), table_bytes=sum(
+                                 -(-(len(g["params"]) * (C.sizeof(AdamItem) + 16)) // _ARENA_ALIGN) * _ARENA_ALIGN for g in self.param_groups))
+        self._lr_pushed = None
+        return d
+
+    def _dev_state(self, p, d, create):
+        """``state[p]`` with ``step`` the parameter's view into the vector and both moments (and the average) in place; a state that came from
+        elsewhere (loaded before the first step, a host ``step``) is adopted: its count is copied into the view"""
+        st = self.state[p]
+        i = d["slot"][p]
+        view = d["views"][i]
+        if st.get("step") is view and "exp_avg" in st and "exp_avg_sq" in st and (self.ema_decay is None or "ema" in st):
+            return st
+        if not create:
+            raise RuntimeError(f"{self._who()}: step() under a graph capture would create optimizer state for parameter {i} of shape "
+                               f"{tuple(p.shape)}, which a replay would not re-create: call init_state() before the capture")
+        if st.get("step") is not view:
+            if "step" in st:
+                view.copy_(torch.as_tensor(st["step"], dtype=torch.float32))
+            st["step"] = view
+        for key in ("exp_avg", "exp_avg_sq"):
+            if key not in st:
+                st[key] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if self.ema_decay is not None and "ema" not in st:
+            st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+        for key in ("exp_avg", "exp_avg_sq") + (("ema",) if self.ema_decay is not None else ()):
+            t = st[key]
+            if not (t.dtype == torch.float32 and t.is_contiguous() and t.device == p.device and t.shape == p.shape):
+                raise RuntimeError(f"{self._who()}: state `{key}` of parameter {i} of shape {tuple(p.shape)} is not a contiguous fp32 tensor on {p.device}")
+        return st
+
+    @torch.no_grad()
+    def init_state(self):
+        """Creates everything a step needs, for EVERY parameter (with or without a gradient now): both moments, the average, the step
+        vector, the learning-rate scalars (and pushes them), the norm buffers, and staging memory for the tables of one more capture.  Call
+        it before capturing ``step()``; calling it again is cheap and changes no value."""
+        if not self.device_step:
+            raise RuntimeError(f"mas_hip.optim.{type(self).__name__}: init_state() belongs to device_step=True")
+        d = self._dev_prepare(True)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._who()}: init_state() under a graph capture")
+        for group in self.param_groups:
+            for p in group["params"]:
+                self._dev_state(p, d, True)
+        if not self._arenas or self._arenas[-1][0].numel() - self._arenas[-1][2] < d["table_bytes"]:
+            cap = max(2 * d["table_bytes"], 1 << 16)
+            self._arenas.append([torch.empty(cap, dtype=torch.uint8, pin_memory=True), torch.empty(cap, dtype=torch.uint8, device=d["device"]), 0])
+        with torch.cuda.device(d["device"]):
+            self.sync_hyperparameters()
+
+    def sync_hyperparameters(self):
+        """Pushes the groups' learning rates to the device scalars the kernel reads, on the current stream, when one of them differs from
+        what was pushed last; returns whether it did.  ``group["lr"]`` may be a float or a 0-dim tensor (a CUDA tensor is read on the
+        host here).  Not under a capture: a captured copy would rewrite the value of the capture at every replay."""
+        if not self.device_step:
+            return False
+        vals = tuple(float(group["lr"]) for group in self.param_groups)
+        if vals == self._lr_pushed:
+            return False
+        self._push_lr(vals)
+        self._lr_pushed = vals
+        return True
+
+    def _push_lr(self, vals):
+        """one asynchronous copy through a pinned buffer whose last copy has run (or a new one)"""
+        d = self._dev_prepare(True)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._who()}: the learning rate changed under a graph capture; call sync_hyperparameters() before it")
+        slot = next((s for s in self._lr_staging if s[0].numel() == len(vals) and s[1].query()), None)
+        if slot is None:
+            slot = [torch.empty(len(vals), dtype=torch.float32, pin_memory=True), torch.cuda.Event()]
+            self._lr_staging.append(slot)
+        slot[0].copy_(torch.tensor(vals, dtype=torch.float32))
+        d["lr"].copy_(slot[0], non_blocking=True)
+        slot[1].record()
+
+    def _capture_table(self, raw):
+        """``raw`` on the device through memory that belongs to this upload alone: the copy node a capture records reads its pinned source
+        again at every replay"""
+        if not self._arenas or self._arenas[-1][0].numel() - self._arenas[-1][2] < len(raw):
+            raise RuntimeError(f"{self._who()}: no staging memory left for a table under a graph capture: call init_state() before every capture")
+        arena = self._arenas[-1]
+        pinned, dev, off = arena
+        C.memmove(pinned.data_ptr() + off, raw, len(raw))
+        dev[off:off + len(raw)].copy_(pinned[off:off + len(raw)], non_blocking=True)
+        arena[2] = off + -(-len(raw) // _ARENA_ALIGN) * _ARENA_ALIGN
+        return dev[off:off + len(raw)]
+
+    def _step_dev(self):
+        """The step with nothing read on the host: per group one mas_adam_multi_dev over the parameters that have a gradient (each with its
+        own step count), the norm launches in front when clipping or guarding, the advance launch(es) behind."""
+        capturing = self._capturing_now()
+        d = self._dev_prepare(not capturing)
+        device = d["device"]
+        with torch.cuda.device(device):
+            if not capturing:
+                self.sync_hyperparameters()
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            launches, advance, first_item = [], [0] if self.ema_decay is not None else [], 0
+            for gi, group in enumerate(self.param_groups):
+                items, steps, blocks = [], [], 0
+                for p in group["params"]:
+                    g = p.grad
+                    if g is None:
+                        continue
+                    if g.is_sparse:
+                        raise RuntimeError("mas_hip.optim.Adam does not support sparse gradients")
+                    st = self._dev_state(p, d, not capturing)
+                    if not (g.dtype == torch.float32 and g.is_contiguous() and g.device == p.device and p.is_contiguous()):
+                        raise RuntimeError(f"{self._who()}: the gradient of parameter {d['slot'][p]} of shape {tuple(p.shape)} ({g.dtype}, {g.device}) is "
+                                           "not a contiguous fp32 tensor on the parameter's device; this mode has no other path")
+                    advance.append(1 + d["slot"][p])
+                    if p.numel() == 0:
+                        continue
+                    it = AdamItem()
+                    it.p, it.g, it.m, it.v, it.n = p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+                    it.first_block = blocks
+                    it.ema = st["ema"].data_ptr() if self.ema_decay is not None else 0
+                    blocks += lib().mas_adam_blocks(p.numel())
+                    items.append(it)
+                    steps.append(st["step"].data_ptr())
+                if items:
+                    tail = _pointers([it.ema for it in items]) + _pointers(steps)
+                    if capturing:
+                        arr = (AdamItem * len(items))(*items)
+                        table = self._capture_table(bytes(memoryview(arr)) + tail)
+                    else:
+                        table = self._table(("dev", gi), device, items, tail)
+                    launches.append((gi, group, table, len(items), blocks, first_item))
+                    first_item += len(items)
+            guard = self.max_grad_norm is not None or self.skip_nonfinite
+            if guard and launches:
+                _norm_coef_launches([(t, n, b) for _, _, t, n, b, _ in launches], d["out"], d["partials"], None,
+                                    _FLT_MAX if self.max_grad_norm is None else self.max_grad_norm, stream)
+                self.grad_norm, self.clip_coef = d["norm"], d["coef"]
+            ptr = lambda a: C.cast(C.c_void_p(a), C.POINTER(C.c_void_p))
+            for gi, group, table, n_items, blocks, first in launches:
+                base = table.data_ptr() + C.sizeof(AdamItem) * n_items
+                b1, b2 = group["betas"]
+                check(lib().mas_adam_multi_dev(
+                    C.c_void_p(table.data_ptr()), ptr(base) if self.ema_decay is not None else None, ptr(base + 8 * n_items), n_items, blocks,
+                    C.c_void_p(d["lr"].data_ptr() + 4 * gi), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                    C.c_void_p(d["coef"].data_ptr()) if self.max_grad_norm is not None else None, self._decoupled_wd,
+                    0.0 if self.ema_decay is None else self.ema_decay, C.c_void_p(d["vec"].data_ptr()) if self.ema_warmup and self.ema_decay is not None else None,
+                    C.c_void_p(d["norm"].data_ptr()) if self.skip_nonfinite else None, C.c_void_p(d["scalars"].data_ptr() + 16 * first), stream),
+                    "adam_multi_dev")
+            advance.sort()
+            k = 0
+            while k < len(advance):                          # runs of neighbouring counters: one launch when every parameter has a gradient
+                e = k
+                while e + 1 < len(advance) and advance[e + 1] == advance[e] + 1:
+                    e += 1
+                check(lib().mas_adam_advance_dev(C.c_void_p(d["vec"].data_ptr() + 4 * advance[k]), e - k + 1, stream), "adam_advance_dev")
+                k = e + 1
+
+    @staticmethod
+    def _capturing_now():
+        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self.state_generation = self.state_generation + 1
+
+    def state_dict(self):
+        """torch.optim.Optimizer.state_dict(); with ``device_step`` the ``step`` entries are copies (not views of the shared vector) and
+        ``param_groups[0]["ema_step"]`` is read from the device here (one host read: not under a capture)"""
+        if self.device_step and self._dev is not None and self.ema_decay is not None:
+            self.param_groups[0]["ema_step"] = int(self._dev["vec"][0])
+        sd = super().state_dict()
+        if self.device_step:                                 # (the packed state holds the optimizer's own dicts: new ones, not new entries)
+            sd["state"] = {k: {**st, "step": st["step"].clone()} if torch.is_tensor(st.get("step")) else st for k, st in sd["state"].items()}
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict().  With ``device_step`` the loaded values are copied INTO the state tensors that exist
+        (same shape), so their storage does not move; a parameter the loaded state does not hold starts over (zero moments and count, the
+        average from the weights) in place too.  Bumps ``state_generation``."""
+        self.state_generation = self.state_generation + 1
+        if not self.device_step:
+            return super().load_state_dict(state_dict)
+        params = [p for group in self.param_groups for p in group["params"]]
+        old = {p: dict(self.state[p]) for p in params if p in self.state and len(self.state[p])}
+        super().load_state_dict(state_dict)
+        for p, mine in old.items():
+            new = dict(self.state[p]) if p in self.state else {}
+            for key, t in mine.items():
+                v = new.get(key)
+                if v is None:                                # not in the loaded state: as at the first step
+                    t.copy_(p.detach()) if key == "ema" else t.zero_()
+                elif key == "step" or (torch.is_tensor(v) and v.shape == t.shape):
+                    t.copy_(torch.as_tensor(v, dtype=t.dtype))
+                    new[key] = t
+            for key, t in mine.items():
+                new.setdefault(key, t)
+            self.state[p] = new
+        if self._dev is not None and self.ema_decay is not None:
+            self._dev["vec"][0] = float(self.param_groups[0].get("ema_step", 0))
+        self._lr_pushed = None                               # (the groups are the loaded ones)
 
     def _ema_pairs(self):
         return [(p, self.state[p]["ema"]) for group in self.param_groups for p in group["params"] if "ema" in self.state.get(p, ())]

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
-from mas_hip import ops
+from mas_hip import graphs, ops
 
 
 def gelu(x):
@@ -378,11 +378,12 @@ class MakeAScene(nn.Module):
 
     def _prompt_embeddings(self, text_tokens, seg_tokens):
         # zero padding -> unique per-position ids from the vocabulary tail (transformer.py:350-353)
-        text_range = (torch.arange(self.text_length) + (self.text_vocab_size - self.text_length)).to(self.device)
+        # (made on the device: a copy from pageable host memory cannot be captured into a graph, and an eager step does not wait for one)
+        text_range = torch.arange(self.text_length, device=self.device) + (self.text_vocab_size - self.text_length)
         text_tokens = torch.where(text_tokens == 0, text_range, text_tokens)
         text_pos = self.text_pos_embeddings(torch.arange(text_tokens.shape[1], device=self.device))
-        return torch.cat((self.text_token_embedding(text_tokens) + text_pos,
-                          self.seg_token_embedding(seg_tokens) + self.get_seg_pos_embeddings(seg_tokens)), dim=1)
+        return torch.cat((graphs.embedding(self.text_token_embedding, text_tokens) + text_pos,
+                          graphs.embedding(self.seg_token_embedding, seg_tokens) + self.get_seg_pos_embeddings(seg_tokens)), dim=1)
 
     @property
     def decode_graph_captures(self):
@@ -574,7 +575,7 @@ class MakeAScene(nn.Module):
     def forward(self, text_tokens, seg_tokens, img_tokens):
         embeddings = self._prompt_embeddings(text_tokens, seg_tokens)
         if img_tokens is not None:
-            embeddings = torch.cat((embeddings, self.image_token_embedding(img_tokens) + self.get_image_pos_embeddings(img_tokens)), dim=1)
+            embeddings = torch.cat((embeddings, graphs.embedding(self.image_token_embedding, img_tokens) + self.get_image_pos_embeddings(img_tokens)), dim=1)
         # transformer.py:366-370 builds tril-with-bidirectional-prefix, which the layers multiply by tril again: causal
         transformer_output, _ = self.transformer(embeddings, None, cache=None, use_cache=False)
         logits = self.to_logits(transformer_output)
@@ -584,7 +585,7 @@ class MakeAScene(nn.Module):
         """the logits ``forward`` returns, from the ``image_length`` hidden rows that predict an image token alone: LayerNorm and Linear
         are row-wise, so slicing BEFORE ``to_logits`` gives the values of ``forward``'s slice without the third of the GEMM it throws away"""
         embeddings = self._prompt_embeddings(text_tokens, seg_tokens)
-        embeddings = torch.cat((embeddings, self.image_token_embedding(img_tokens) + self.get_image_pos_embeddings(img_tokens)), dim=1)
+        embeddings = torch.cat((embeddings, graphs.embedding(self.image_token_embedding, img_tokens) + self.get_image_pos_embeddings(img_tokens)), dim=1)
         transformer_output, _ = self.transformer(embeddings, None, cache=None, use_cache=False)
         return self.to_logits(transformer_output[:, -self.image_length - 1:-1, :])
 

@@ -785,6 +785,35 @@ int mas_obj_finalize(const float* partial, const MasObjPlan* p, float* out, void
 int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, const float* dout, void* seed,
                      void* stream);
 
+/* ---- Codebook reservoir (make-a-scene_amd/csrc/reservoir.hip; Codebook.enable_device_reservoir).  The reference's reservoir of latent
+ * rows (models/modules.py:477-481: 10 random positions per image appended, then a random subset of reservoir_size rows kept), stated
+ * on sets and kept wholly on the device, so that a training step holding it can be captured into a graph.  An addition inside ABI 10.
+ *   z     fp32 [B, HW, D] (the NHWC latent), read only;      buf   fp32 [R, D], rows [0, c) held;
+ *   state int32 {c, calls}: rows held and the number of calls so far (the Philox counter); zero both to empty the reservoir;
+ *   plan  int32 [2 * 10 * B] workspace: {destination slot or -1, source row of z} per candidate, written by the first launch and read
+ *         by the second;   seed: fixed by the caller for the reservoir's life.   The host reads nothing: c after k calls of batch B is
+ *         min(R, 10 B k).
+ * One call, with n = 10 B, m = c + n, calls = state[1]:
+ *   positions   pos_j = P(j), j = 0 .. 9, P a keyed bijection of [0, HW): 10 distinct positions, the same for every image of the batch
+ *               (the reference's one randperm(HW)[:10]).  Candidate i = 10 b + j is row b * HW + pos_j of z, copied bit for bit.
+ *   m <= R      candidate i goes to slot c + i.
+ *   m >  R      the rows Q(t), t = 0 .. m - R - 1, of the m rows {old slots 0 .. c-1, candidate i as c + i} are dropped, Q a keyed
+ *               bijection of [0, m): a pseudo-random (m - R)-subset, distinct by construction.  The surviving candidates, in the order
+ *               of i, take the free slots c, c + 1, .. R - 1 first and then the slots of the dropped old rows in the order of t.
+ *   then        state = {min(R, m), calls + 1}, stored by the one planning work-group after a barrier behind its last read of them.
+ * Keyed bijection of [0, N): h = the smallest value >= 1 with 4^h >= N; x = (l << h) | r; four balanced Feistel rounds
+ *   (l, r) <- (r, l ^ (F(r, round) & (2^h - 1))), F = word x of Philox4x32-10 at counter (r, round, stream, calls) under the key
+ *   (lo32(seed), hi32(seed)), stream 0 for P and 1 for Q; the result is walked round its cycle (applied again) until it is below N.
+ *   Every lane computes its own index; no lane waits for another's draw.
+ * Two launches on `stream`: one work-group that plans (block scans in LDS rank the survivors and the dropped slots), then 64 lanes per
+ * candidate row copying with 16-byte loads and stores.  A state outside 0 <= c <= R holds nothing new and is left as it is.
+ * Checked on the host before anything is launched: HW >= 10, 10 B <= R, D % 4 == 0, pointers given and z / buf 16-byte aligned
+ * (MAS_EINVAL); 10 B <= MAS_RESERVOIR_MAX_CANDIDATES, R + 10 B <= 2^30, B HW <= 2^30 (MAS_EUNSUPPORTED).                          */
+#define MAS_RESERVOIR_PER_IMAGE 10
+#define MAS_RESERVOIR_MAX_CANDIDATES 2048
+int mas_reservoir_collect(const float* z, float* buf, int32_t* state, int32_t* plan, long long seed, int R, int B, int HW, int D,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,9 +32,25 @@ What it needs and what it does:
   over slices of the indices, so a replayed step differs from an eager one in the order of those additions -- and not at all inside
   ``graphs.embedding_grad_in_chunks()``.
 
-Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collectives run on other streams; ``reducer=`` raises), gradient
-accumulation across calls (every replay starts from ``zero_grad``), inputs that are not tensors, and a ``loss_fn`` that reads anything on
-the host."""
+The VQ-SEG step needs two more things, both opt-in; without a codebook and with ``accumulate=1`` the code above runs as is:
+
+* ``codebooks=`` (default: every ``Codebook`` found under ``modules=``): each must have its device reservoir on
+  (``Codebook.enable_device_reservoir()``), else this raises.  A codebook's training forward has three shapes -- no collect and
+  unquantised, collect and unquantised, collect + lookup -- chosen by its call counter.  The host's half of a call (``Codebook.tick``:
+  the counter, and the re-initialisation when it is due) runs eagerly BEFORE the replay; the captured forward does not tick.  The phase
+  the call is in is part of the signature, so a phase change recaptures lazily: three captures over a run.
+* ``accumulate=k`` > 1: the optimizer steps on calls k, 2k, ... on the sum of the k calls' gradients (unaveraged, as the reference's
+  loop; the reference itself steps on calls 1, k+1, ...).  Two graphs per phase share the static inputs and one memory pool: a micro-step
+  (forward, backward ADDING into the gradients that are there) and a closing step (the same, ``optimizer.step()``, the gradients
+  zeroed in place).  The gradients are the tensors the warm-up calls left, at stable addresses; a parameter that had no gradient
+  then keeps ``.grad = None`` (AdamW does not decay it) until a capture shows that it receives one -- the embedding when the lookup
+  begins -- at which point it gets a persistent zero tensor and the capture is taken again.  The returned loss is the call's own.
+* in this mode CONSTRUCTION TRAINS TOO -- the ``warmup`` calls are real training calls, they tick the codebooks' counters and count
+  towards ``accumulate`` (``step.calls``) -- but nothing is captured before the first call (``step.captures == 0`` until then).
+
+Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collectives run on other streams; ``reducer=`` raises), steps
+with more than one optimizer or backward pass (VQ-IMG's), inputs that are not tensors, and a ``loss_fn`` that reads anything on the
+host."""
 import contextlib
 
 import torch
@@ -93,7 +109,12 @@ def embedding_grad_in_chunks():
 
 
 class GraphedTrainStep:
-    def __init__(self, loss_fn, optimizer, example_inputs, *, amp_dtype=None, warmup=1, modules=(), reducer=None):
+    def __init__(self, loss_fn, optimizer, example_inputs, *, amp_dtype=None, warmup=1, modules=(), reducer=None, codebooks=None,
+                 accumulate=1):
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int):
+            raise TypeError(f"GraphedTrainStep: accumulate must be an integer (calls per optimizer step), got {accumulate!r}")
+        if accumulate < 1:
+            raise ValueError(f"GraphedTrainStep: accumulate must be at least 1, got {accumulate}")
         if reducer is not None:
             raise NotImplementedError("GraphedTrainStep: a gradient reducer runs collectives on other streams, which one captured stream "
                                       "cannot hold; train data-parallel runs eagerly")
@@ -109,10 +130,25 @@ class GraphedTrainStep:
         self.modules = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
         self.captures = 0
         self.graph = self.loss = self._sig = self._keep = None
+        if codebooks is None:                                 # (duck-typed: models imports this package, not the other way round)
+            seen = []
+            for mod in self.modules:
+                seen += [m for m in mod.modules() if hasattr(m, "enable_device_reservoir") and not any(m is s for s in seen)]
+            codebooks = seen
+        self.codebooks = [codebooks] if isinstance(codebooks, torch.nn.Module) else list(codebooks)
+        for cb in self.codebooks:
+            if not getattr(cb, "device_reservoir", False):
+                raise RuntimeError("GraphedTrainStep: a Codebook without its device reservoir cannot be captured (its reservoir is kept by CPU "
+                                   "permutations and a growing tensor): call codebook.enable_device_reservoir() first")
+        self.accumulate, self.calls = accumulate, 0
+        self._graphs, self._cb_rows = {}, []
         self._check_inputs(example_inputs)
         self._side = torch.cuda.Stream(device=example_inputs[0].device)
         self._static = [x.detach().clone() for x in example_inputs]
-        self._capture(int(warmup))
+        if not self.codebooks and accumulate == 1:
+            self._capture(int(warmup))
+        else:
+            self._warm_up(int(warmup))
 
     @staticmethod
     def _check_inputs(inputs):
@@ -131,7 +167,8 @@ class GraphedTrainStep:
                 tuple((tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), len(g["params"])) for g in opt.param_groups),
                 opt.max_grad_norm, opt.ema_decay, opt.ema_warmup, opt.skip_nonfinite, ops.compute_dtype(),
                 tuple((tuple(x.shape), x.dtype, x.device) for x in inputs),
-                tuple(m.training for mod in self.modules for m in mod.modules()))
+                tuple(m.training for mod in self.modules for m in mod.modules()),
+                tuple((cb.training, cb.phase()) for cb in self.codebooks))
 
     def _train_step(self):
         self.optimizer.zero_grad(set_to_none=True)
@@ -154,14 +191,30 @@ class GraphedTrainStep:
                     self._train_step()
             opt.zero_grad(set_to_none=True)
             opt.init_state()
-            ops._note_optimizer_step(opt)                   # every derived copy of a parameter is stale now: its refresh gets captured
+            self._stale_for_capture()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=self._side), self._autocast():
                 loss = self._train_step()
         main.wait_stream(self._side)
+        self._settle_caches()
+        self.graph, self.loss = graph, loss.detach()
+        self._sig = self._signature(self._static)
+        self.captures += 1
+
+    def _stale_for_capture(self):
+        """Every derived copy of a parameter is made stale, so that its refresh gets captured.  The refresh of the packed convolution
+        weights reads an item table that is uploaded from pageable memory when the set of stale images is new, which a capture cannot
+        hold: the same refresh runs eagerly first (twice: the first one also takes whatever else in the process was stale, the second
+        one uploads the table of this step's images alone; it changes no value, and does nothing for a model without convolutions)."""
+        for _ in range(2):
+            ops._note_optimizer_step(self.optimizer)
+            ops._pack_cache._refresh_stale(self._side.device)
+        ops._note_optimizer_step(self.optimizer)
+
+    def _settle_caches(self):
         # the images the graph reads: kept alive here (invalidate_weight_cache() / swap_ema() drop the caches' own references)
         self._keep = [e[2] for e in ops._bf16_shadows.params.values()] + [e[2] for e in ops._pack_cache.store.values()] + \
-                     [e[2] for e in ops._pack_cache.derived.values()]
+                     [e[2] for e in ops._pack_cache.derived.values()] + [t[1] for t in ops._pack_cache._tables.values()]
         # nothing ran, but the caches stamped as fresh whatever they "refreshed" inside the capture (this model's images and any other stale
         # one in the process): none of those stamps describes a refresh that happened
         for e in ops._bf16_shadows.params.values():
@@ -169,12 +222,122 @@ class GraphedTrainStep:
         for e in ops._pack_cache.store.values():
             e[1] = None
         ops._pack_cache.derived.clear()
-        self.graph, self.loss = graph, loss.detach()
+
+    # ---- codebook phases and gradient accumulation (codebooks under modules=, or accumulate > 1) -----------------------------------------
+    @contextlib.contextmanager
+    def _ticked(self):
+        """inside, the codebooks' forward leaves the host-side tick (call counter, re-initialisation) to ``_tick``"""
+        old = [cb._ticked_outside for cb in self.codebooks]
+        for cb in self.codebooks:
+            cb._ticked_outside = True
+        try:
+            yield
+        finally:
+            for cb, o in zip(self.codebooks, old):
+                cb._ticked_outside = o
+
+    def _tick(self):
+        self.calls += 1
+        for cb in self.codebooks:
+            if cb.training:
+                cb.tick()
+        return self.calls % self.accumulate == 0            # a closing call: the optimizer steps
+
+    def _step(self, closing):
+        """one call: with accumulate == 1 the step of ``_train_step``; else forward and backward ADDING into the gradients that are there,
+        and on a closing call ``optimizer.step()`` and the gradients zeroed in place (they stay where the captured kernels write)"""
+        if self.accumulate == 1:
+            return self._train_step()
+        loss = self.loss_fn(*self._static)
+        loss.backward()
+        if closing:
+            self.optimizer.step()
+            grads = [p.grad for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+            if grads:
+                torch._foreach_zero_(grads)
+        return loss
+
+    def _warm_up(self, warmup):
+        """``warmup`` real training calls, eager, under the conditions of the capture; nothing is captured before the first call"""
+        main = torch.cuda.current_stream(self._side.device)
+        self.optimizer.init_state()
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._ticked():
+            for _ in range(warmup):
+                closing = self._tick()
+                with self._autocast():
+                    self._step(closing)
+        main.wait_stream(self._side)
+
+    def _capture_phase(self):
+        """the graphs of the phase the codebooks are in now: one step when accumulate == 1, else a micro-step and a closing step that share
+        the static inputs and one memory pool.  Executes nothing."""
+        opt, k = self.optimizer, self.accumulate
+        self.graph = self.loss = None
+        self._graphs = {}                                   # (the old phase's graphs and their memory go first)
+        main = torch.cuda.current_stream(self._side.device)
+        params = [p for g in opt.param_groups for p in g["params"]]
+        rows = [cb._dev["c"] for cb in self.codebooks]
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._ticked():
+            if k == 1:
+                opt.zero_grad(set_to_none=True)
+            pool = None                                     # the closing step's graph shares the micro-step's memory pool
+            for closing in ((True,) if k == 1 else (False, True)):
+                for attempt in range(2):
+                    opt.init_state()
+                    self._stale_for_capture()
+                    without = [p for p in params if p.requires_grad and p.grad is None] if k > 1 else []
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, pool=pool, stream=self._side), self._autocast():
+                        loss = self._step(closing)
+                    self._cb_rows = [cb._dev.get("last_n", 0) if cb.training and cb.phase() >= 1 else 0 for cb in self.codebooks]
+                    for cb, c in zip(self.codebooks, rows):  # the capture's forward counted rows that no kernel collected
+                        cb._dev["c"] = c
+                        cb.reservoir = cb._dev["buf"][:c]
+                    fresh = [p for p in without if p.grad is not None]
+                    if not fresh:
+                        break
+                    # autograd installed a tensor of the graph's pool as these gradients (the embedding at the start of the lookup phase):
+                    # they become persistent zeros that the capture, taken again, adds into
+                    if attempt:
+                        raise RuntimeError("GraphedTrainStep: gradients appeared at the second capture that the first one did not produce")
+                    del graph, loss
+                    for p in fresh:
+                        p.grad = torch.zeros_like(p)
+                self._graphs[closing] = (graph, loss.detach())
+                pool = graph.pool()
+                self.captures += 1
+        main.wait_stream(self._side)
+        self._settle_caches()
         self._sig = self._signature(self._static)
-        self.captures += 1
+
+    def _call_phased(self, inputs):
+        closing = self._tick()                              # eager, before the replay: the counter, and a due re-initialisation
+        if self._signature(inputs) != self._sig:
+            if len(inputs) != len(self._static) or any(x.shape != s.shape or x.dtype != s.dtype or x.device != s.device
+                                                       for x, s in zip(inputs, self._static)):
+                self._graphs = {}
+                self._static = [x.detach().clone() for x in inputs]
+            self._capture_phase()
+        self.optimizer.sync_hyperparameters()
+        for s, x in zip(self._static, inputs):
+            if x is not s:
+                s.copy_(x, non_blocking=True)
+        graph, loss = self._graphs[closing]
+        graph.replay()
+        for cb, n in zip(self.codebooks, self._cb_rows):
+            if n:
+                cb._note_collected(n)
+        if closing:
+            ops._note_optimizer_step(self.optimizer)
+        self.loss = loss
+        return loss
 
     def __call__(self, *inputs):
         self._check_inputs(inputs)
+        if self.codebooks or self.accumulate > 1:
+            return self._call_phased(inputs)
         if self._signature(inputs) != self._sig:
             if len(inputs) != len(self._static) or any(x.shape != s.shape or x.dtype != s.dtype or x.device != s.device
                                                        for x, s in zip(inputs, self._static)):

@@ -219,6 +219,9 @@ class _PackCache:
         sig = (device.index, raw)
         hit = self._tables.get(which)
         if hit is None or hit[0] != sig:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("packed-weight cache: a graph capture would upload a new item table (a copy from pageable memory, which a "
+                                   "capture cannot hold): refresh the same set of stale images once before capturing, as GraphedTrainStep does")
             hit = self._tables[which] = (sig, torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device))
         return hit[1]
 
@@ -1183,6 +1186,48 @@ def vq_lookup(z, codebook, beta):
     cp = torch.nn.functional.pad(codebook.float(), (0, dp - d))
     zq, loss, idx = _VQ.apply(zp, cp, beta)
     return zq[:, :d], loss * (dp / d), idx
+
+
+RESERVOIR_PER_IMAGE = 10
+
+
+def reservoir_plan_elems(batch_size: int) -> int:
+    """int32 elements of ``reservoir_collect``'s ``plan`` workspace for a batch"""
+    return 2 * RESERVOIR_PER_IMAGE * int(batch_size)
+
+
+def reservoir_collect(z, buf, state, seed, plan=None):
+    """One step of the codebook's device reservoir (``mas_reservoir_collect``; the rule and the construction: include/mas_hip.h, "Codebook
+    reservoir").  ``z`` fp32 ``[B, D, H, W]``-logical in NHWC memory (or ``[B, HW, D]`` contiguous), ``buf`` fp32 ``[R, D]``, ``state``
+    int32 ``{rows held, calls}`` on the device, ``seed`` a Python integer fixed for the reservoir's life, ``plan`` an int32 workspace of
+    ``reservoir_plan_elems(B)`` elements (a capture passes a static one; allocated here when None).  Two launches, nothing read on the
+    host.  Shapes are checked before the device is touched: HW >= 10, 10 B <= R, D % 4 == 0."""
+    if z.dim() == 4:
+        b, d, hw = z.shape[0], z.shape[1], z.shape[2] * z.shape[3]
+        flat = z.permute(0, 2, 3, 1)
+    elif z.dim() == 3:
+        b, hw, d = z.shape
+        flat = z
+    else:
+        raise ValueError(f"reservoir_collect: z must be [B, D, H, W] or [B, HW, D], got {tuple(z.shape)}")
+    if buf.dim() != 2 or buf.shape[1] != d:
+        raise ValueError(f"reservoir_collect: buf {tuple(buf.shape)} against latent rows of {d} elements")
+    r = buf.shape[0]
+    if hw < RESERVOIR_PER_IMAGE or RESERVOIR_PER_IMAGE * b > r or d % 4 or b < 1:
+        raise ValueError(f"reservoir_collect: needs HW >= {RESERVOIR_PER_IMAGE}, 10 * B <= R and D % 4 == 0; got B={b}, HW={hw}, D={d}, R={r}")
+    _require_cuda(z, "reservoir_collect")
+    if not (flat.is_contiguous() and z.dtype == torch.float32 and buf.dtype == torch.float32 and buf.is_contiguous() and buf.device == z.device):
+        raise RuntimeError("reservoir_collect: z must be fp32 in NHWC memory and buf a contiguous fp32 tensor on the same device")
+    if not (state.dtype == torch.int32 and state.numel() >= 2 and state.is_contiguous() and state.device == z.device):
+        raise RuntimeError("reservoir_collect: state must be a contiguous int32 tensor {rows held, calls} on z's device")
+    if plan is None:
+        plan = torch.empty(reservoir_plan_elems(b), dtype=torch.int32, device=z.device)
+    elif not (plan.dtype == torch.int32 and plan.numel() >= reservoir_plan_elems(b) and plan.is_contiguous() and plan.device == z.device):
+        raise RuntimeError(f"reservoir_collect: plan must be a contiguous int32 tensor of at least {reservoir_plan_elems(b)} elements on z's device")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    check(lib().mas_reservoir_collect(_ptr(z), _ptr(buf), _ptr(state), _ptr(plan), seed - (1 << 64) if seed >= 1 << 63 else seed, r, b, hw, d,
+                                      _stream()), "reservoir_collect")
+    return plan
 
 
 # --------------------------------------------------------------------------- #

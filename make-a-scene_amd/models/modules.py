@@ -37,6 +37,7 @@ from mas_hip import ops
 _MAS_SYNCBN = int(os.environ.get("MAS_SYNCBN", "2"))
 _EXCHANGE_AT_WORLD_1 = os.environ.get("MAS_SYNCBN_EXCHANGE_AT_WORLD_1", "0") == "1"
 _RESERVOIR_ASYNC = os.environ.get("MAS_RESERVOIR_ASYNC", "1") == "1"          # 0: the codebook's reservoir permutations reach the GPU by a blocking copy
+_DEVICE_RESERVOIR = os.environ.get("MAS_DEVICE_RESERVOIR", "0") == "1"        # 1: every Codebook turns its device reservoir on at its first training forward
 
 
 def nonlinearity(x):
@@ -335,6 +336,69 @@ class Codebook(nn.Module):
         self.q_counter = 0
         self.reservoir_size = int(reservoir_size)
         self.reservoir = None
+        self._dev = None                  # the device reservoir (enable_device_reservoir): buffer, counters, seed, the host's mirror of c
+        self._ticked_outside = False      # mas_hip.graphs.GraphedTrainStep ticks before a replay: forward must not tick again
+
+    # ---- device reservoir (opt-in) ------------------------------------------------------------------------------------
+    def enable_device_reservoir(self, seed=None):
+        """Keeps the reservoir in a fixed ``[reservoir_size, codebook_dim]`` device buffer that one ``ops.reservoir_collect`` call per
+        step updates (csrc/reservoir.hip): no CPU permutation, no growing ``torch.cat``, nothing read on the host, so the step can be
+        captured into a graph.  ``seed``: the Philox key of the reservoir's draws; None draws one integer from torch's CPU generator
+        now.  Call it after the module is on its GPU; the buffer is allocated here, once.  In this mode a re-initialisation runs at
+        the START of its call (on the reservoir as the previous call left it: ``tick``), writes the centroids into the existing
+        embedding storage (``copy_``) and runs k-means with deterministic accumulation, so a run repeats bit for bit from its seeds.
+        ``MAS_DEVICE_RESERVOIR=1`` in the environment enables it at the first training forward.  Returns self."""
+        w = self.embedding.weight
+        if not w.is_cuda:
+            raise RuntimeError("Codebook.enable_device_reservoir: the module must be on its GPU first (no CPU fallback); "
+                               f"the embedding is on {w.device}")
+        if self.codebook_dim % 4:
+            raise ValueError(f"Codebook.enable_device_reservoir: codebook_dim {self.codebook_dim} is not a multiple of 4")
+        if self.reservoir_size < 10:
+            raise ValueError(f"Codebook.enable_device_reservoir: reservoir_size {self.reservoir_size} holds fewer than one image's 10 rows")
+        if self.reservoir is not None:
+            raise RuntimeError("Codebook.enable_device_reservoir: the host reservoir already holds rows; enable it before training")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self._dev = dict(seed=int(seed), c=0, plans={},
+                         buf=torch.zeros(self.reservoir_size, self.codebook_dim, dtype=torch.float32, device=w.device),
+                         state=torch.zeros(2, dtype=torch.int32, device=w.device))
+        self.reservoir = self._dev["buf"][:0]
+        return self
+
+    @property
+    def device_reservoir(self):
+        return self._dev is not None
+
+    def phase(self, q_counter=None):
+        """which of its three shapes a training forward at ``q_counter`` (default: now) takes: 0 no collect, unquantised; 1 collect,
+        unquantised; 2 collect + lookup"""
+        q = self.q_counter if q_counter is None else q_counter
+        return 0 if q <= self.q_start_collect else (1 if q < self.q_init else 2)
+
+    def _reinit_due(self):
+        q = self.q_counter
+        return self.q_init <= q < self.q_re_end and ((q - self.q_init) % self.q_re_step == 0 or q == self.q_init + self.q_re_end - 1)
+
+    def tick(self):
+        """the host's half of a device-reservoir training call: the call counter, and the re-initialisation when it is due"""
+        self.q_counter += 1
+        if self._reinit_due():
+            self._reinit_from_reservoir()
+
+    def _collect_device(self, z, batch_size):
+        dev = self._dev
+        plan = dev["plans"].get(batch_size)
+        if plan is None:
+            plan = dev["plans"][batch_size] = torch.empty(ops.reservoir_plan_elems(batch_size), dtype=torch.int32, device=z.device)
+        ops.reservoir_collect(z, dev["buf"], dev["state"], dev["seed"], plan)
+        self._note_collected(10 * batch_size)
+
+    def _note_collected(self, n):
+        """the host's mirror of the rows held: min(R, c + n) after a collecting call, no read-back"""
+        dev = self._dev
+        dev["c"], dev["last_n"] = min(self.reservoir_size, dev["c"] + n), n
+        self.reservoir = dev["buf"][:dev["c"]]
 
     @staticmethod
     def _randperm(n, device, keep=None):
@@ -376,14 +440,41 @@ class Codebook(nn.Module):
             pool = torch.cat(gathered, dim=0)
         else:
             pool = self.reservoir
+        if self._dev is not None:
+            # the cluster sums are index_add_: atomics in whatever order the device takes them unless torch is told otherwise
+            det, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+            torch.use_deterministic_algorithms(True, warn_only=True)
+            try:
+                cent = kmeans_fit(pool, self.codebook_size).detach().contiguous()
+            finally:
+                torch.use_deterministic_algorithms(det, warn_only=warn)
+            if world_size > 1:
+                dist.broadcast(cent, 0)
+            self.embedding.weight.data.copy_(cent)        # in place: a captured step keeps reading the same storage
+            return
         cent = kmeans_fit(pool, self.codebook_size).detach().contiguous()
         if world_size > 1:
             dist.broadcast(cent, 0)
         self.embedding.weight.data = cent
 
+    def _forward_device(self, z):
+        """training forward with the device reservoir: tick (unless GraphedTrainStep did), collect, lookup"""
+        if not self._ticked_outside:
+            self.tick()
+        phase = self.phase()
+        if phase >= 1:
+            self._collect_device(z, z.size(0))
+        if phase < 2:
+            return z, torch.zeros((), dtype=z.dtype, device=z.device), None
+        return ops.vq_lookup(z, self.embedding.weight, self.beta)
+
     def forward(self, z):
         z = ops.nhwc(z, torch.float32)                    # b c h w logical, NHWC memory: the flatten is a view
         batch_size = z.size(0)
+        if self.training and self._dev is None and _DEVICE_RESERVOIR and z.is_cuda:
+            self.enable_device_reservoir()
+        if self.training and self._dev is not None:
+            return self._forward_device(z)
         if self.training:
             self.q_counter += 1
             if self.q_counter > self.q_start_collect:

@@ -814,6 +814,33 @@ int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPlan* p, int 
 int mas_reservoir_collect(const float* z, float* buf, int32_t* state, int32_t* plan, long long seed, int R, int B, int HW, int D,
                           void* stream);
 
+/* ---- K-means re-initialisation (make-a-scene_amd/csrc/kmeans.hip; ops.kmeans_fit, models.kmeans.kmeans_fit(on_device=True),
+ * Codebook.enable_device_reservoir(device_kmeans=True)).  Lloyd's iterations of the codebook re-initialisation (reference
+ * models/modules.py:487-499 through fast_pytorch_kmeans; oracle/kmeans_oracle.py states the rule) as a fixed sequence of launches: the
+ * host enqueues max_iter iterations and reads nothing, the stop test runs on the device.  Additions inside ABI 10.
+ *   points    fp32 [M, D], read only;      centroids fp32 [K, D]: the initial centroids on entry, the final ones on return (in place);
+ *   assign    int64 [M]: the assignment of the last executed iteration, i.e. against the centroids BEFORE the last update;
+ *   info      int32 {iterations run, converged};      shift  fp64 [1]: the last sum (new - old)^2;
+ *   workspace mas_kmeans_workspace(M, K) bytes.
+ * One iteration:
+ *   assignment  mas_vq_argmin_fwd's own distance kernels (one copy of the device code): d = fl(fl(|x|^2 + |c|^2) - 2 dot), dot an
+ *               exact-fp32 FMA chain, the lowest index on ties.  |x|^2 is computed once per fit, |c|^2 once per iteration.
+ *   update      new centroid = sum / count of its points, an empty cluster becomes the ZERO vector.  A work-group owns 8 centroids; its
+ *               four waves scan a quarter of the assignments each in position order and add into their own fp32 accumulators, which are
+ *               folded in wave order: no atomics, the order is fixed, a fit repeats bit for bit.  Written in place.
+ *   advance     shift = sum (new - old)^2 over all K D elements (differences in fp32, squares and the sum in fp64, fixed order);
+ *               one work-group stores info = {iterations + 1, shift <= (double)tol} and shift.
+ *   skip        once `converged` is set every kernel of the remaining iterations returns before its first load: nothing more is written.
+ * mas_kmeans_init: centroid k = a bitwise copy of point row P(k), k = 0 .. K-1, P the keyed bijection of [0, M) of "Codebook
+ *   reservoir" above with stream 2, calls = draw and the key (lo32(seed), hi32(seed)): K distinct rows by construction.  init_idx
+ *   (int32 [K], may be null) receives P(k).
+ * Checked on the host before anything is launched: D in {32, 64, 128, 256} and M <= 2^30 (MAS_EUNSUPPORTED); 1 <= K <= M,
+ * max_iter >= 1, pointers given, points / centroids / workspace 16-byte aligned (MAS_EINVAL); the workspace size (MAS_EWORKSPACE).      */
+size_t mas_kmeans_workspace(int M, int K);
+int mas_kmeans_init(const float* points, int M, int K, int D, long long seed, int draw, float* centroids, int32_t* init_idx, void* stream);
+int mas_kmeans_fit(const float* points, float* centroids, int M, int K, int D, int max_iter, float tol, int64_t* assign, int32_t* info,
+                   double* shift, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1230,6 +1230,82 @@ def reservoir_collect(z, buf, state, seed, plan=None):
     return plan
 
 
+def _signed64(seed) -> int:
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def _kmeans_points(points, n_clusters, who: str):
+    """the checks that need no device, then the fp32 rows zero-padded to the next kernel width (as ``vq_lookup`` pads: zero dimensions
+    add nothing to a distance, a mean or a shift) -> (rows, true width)"""
+    if points.dim() != 2:
+        raise ValueError(f"{who}: points must be [M, D], got {tuple(points.shape)}")
+    m, d = points.shape
+    k = int(n_clusters)
+    if d < 1 or d > _VQ_DIMS[-1]:
+        raise ValueError(f"{who}: D={d} outside the kernel envelope: widths up to {_VQ_DIMS[-1]} (instantiated for {_VQ_DIMS}, narrower "
+                         f"ones zero-padded)")
+    if k < 1 or k > m:
+        raise ValueError(f"{who}: needs 1 <= n_clusters <= M distinct rows, got n_clusters={k}, M={m}")
+    if m > 1 << 30:
+        raise ValueError(f"{who}: M={m} beyond 2^30 rows")
+    _require_cuda(points, who)
+    pts = points.detach().float()
+    if d not in _VQ_DIMS:
+        pts = torch.nn.functional.pad(pts, (0, next(v for v in _VQ_DIMS if v >= d) - d))
+    pts = pts.contiguous()
+    if pts.data_ptr() % 16:
+        raise ValueError(f"{who}: points must be 16-byte aligned (the kernels read rows with 16-byte loads); the storage offset is "
+                         f"{points.storage_offset()} elements")
+    return pts, d
+
+
+def kmeans_init(points, n_clusters, seed, draw=0):
+    """The seeded initial centroids of ``kmeans_fit`` (``mas_kmeans_init``): row ``P(k)`` of ``points`` for k = 0 .. n_clusters-1, P the
+    keyed bijection of [0, M) of include/mas_hip.h ("Codebook reservoir") with stream 2, ``calls = draw`` and the key ``seed`` -- distinct
+    rows by construction, copied bit for bit.  -> (centroids fp32 ``[K, D]``, the rows drawn int32 ``[K]``).  Nothing read on the host."""
+    pts, d = _kmeans_points(points, n_clusters, "kmeans_init")
+    k = int(n_clusters)
+    cent = torch.empty(k, pts.shape[1], dtype=torch.float32, device=pts.device)
+    idx = torch.empty(k, dtype=torch.int32, device=pts.device)
+    check(lib().mas_kmeans_init(_ptr(pts), pts.shape[0], k, pts.shape[1], _signed64(seed), int(draw), _ptr(cent), _ptr(idx), _stream()),
+          "kmeans_init")
+    return (cent if pts.shape[1] == d else cent[:, :d].contiguous()), idx
+
+
+def kmeans_fit(points, n_clusters, *, init_idx=None, seed=None, draw=0, max_iter=100, tol=1e-4, return_shift=False):
+    """Lloyd's k-means of the codebook re-initialisation wholly on the device (``mas_kmeans_fit``, csrc/kmeans.hip; the rule:
+    oracle/kmeans_oracle.py): ``max_iter`` iterations are enqueued, the stop test ``sum (new - old)^2 <= tol`` runs on the device and
+    the iterations behind it return at once -- nothing is read on the host, so the call can be captured into a graph.  Every sum has a
+    fixed order: a fit repeats bit for bit.  Initial centroids: the rows ``init_idx`` (a gather), or the rows drawn from ``seed`` and
+    ``draw`` (``kmeans_init``).  -> (centroids fp32 ``[K, D]``, assign int64 ``[M]`` of the last executed iteration, info int32 ``{iterations
+    run, converged}`` on the device[, shift fp64 ``[1]``]).  Widths up to 256; other than 32 / 64 / 128 / 256 zero-padded."""
+    if (init_idx is None) == (seed is None):
+        raise ValueError("kmeans_fit: give either init_idx (rows to start from) or seed (rows drawn by the keyed bijection)")
+    if int(max_iter) < 1:
+        raise ValueError(f"kmeans_fit: max_iter={max_iter}, needs max_iter >= 1")
+    pts, d = _kmeans_points(points, n_clusters, "kmeans_fit")
+    m, dp = pts.shape
+    k = int(n_clusters)
+    if init_idx is not None:
+        if init_idx.numel() != k:
+            raise ValueError(f"kmeans_fit: {init_idx.numel()} initial rows for {k} clusters")
+        cent = pts.index_select(0, init_idx.to(device=pts.device, dtype=torch.int64).reshape(-1)).contiguous()
+    else:
+        cent = torch.empty(k, dp, dtype=torch.float32, device=pts.device)
+        check(lib().mas_kmeans_init(_ptr(pts), m, k, dp, _signed64(seed), int(draw), _ptr(cent), None, _stream()), "kmeans_init")
+    assign = torch.empty(m, dtype=torch.int64, device=pts.device)
+    info = torch.empty(2, dtype=torch.int32, device=pts.device)
+    shift = torch.empty(1, dtype=torch.float64, device=pts.device)
+    wsb = lib().mas_kmeans_workspace(m, k)
+    ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=pts.device)
+    check(lib().mas_kmeans_fit(_ptr(pts), _ptr(cent), m, k, dp, int(max_iter), float(tol), _ptr(assign), _ptr(info), _ptr(shift), _ptr(ws), wsb,
+                               _stream()), "kmeans_fit")
+    if dp != d:
+        cent = cent[:, :d].contiguous()
+    return (cent, assign, info, shift) if return_shift else (cent, assign, info)
+
+
 # --------------------------------------------------------------------------- #
 # SyncBatchNorm behind quant_conv (reference models/vqvae.py:15-16)
 # --------------------------------------------------------------------------- #

@@ -340,14 +340,17 @@ class Codebook(nn.Module):
         self._ticked_outside = False      # mas_hip.graphs.GraphedTrainStep ticks before a replay: forward must not tick again
 
     # ---- device reservoir (opt-in) ------------------------------------------------------------------------------------
-    def enable_device_reservoir(self, seed=None):
+    def enable_device_reservoir(self, seed=None, device_kmeans=None):
         """Keeps the reservoir in a fixed ``[reservoir_size, codebook_dim]`` device buffer that one ``ops.reservoir_collect`` call per
         step updates (csrc/reservoir.hip): no CPU permutation, no growing ``torch.cat``, nothing read on the host, so the step can be
         captured into a graph.  ``seed``: the Philox key of the reservoir's draws; None draws one integer from torch's CPU generator
         now.  Call it after the module is on its GPU; the buffer is allocated here, once.  In this mode a re-initialisation runs at
         the START of its call (on the reservoir as the previous call left it: ``tick``), writes the centroids into the existing
         embedding storage (``copy_``) and runs k-means with deterministic accumulation, so a run repeats bit for bit from its seeds.
-        ``MAS_DEVICE_RESERVOIR=1`` in the environment enables it at the first training forward.  Returns self."""
+        ``MAS_DEVICE_RESERVOIR=1`` in the environment enables it at the first training forward.  ``device_kmeans`` (None reads
+        ``MAS_KMEANS_DEVICE``, default off): the re-initialisation's k-means runs as ``ops.kmeans_fit`` (csrc/kmeans.hip) --
+        a fixed sequence of launches that reads nothing on the host, its sums in an order the kernels fix and its initial rows drawn from
+        this reservoir's seed and the call counter, so torch's process-wide determinism switch is left alone.  Returns self."""
         w = self.embedding.weight
         if not w.is_cuda:
             raise RuntimeError("Codebook.enable_device_reservoir: the module must be on its GPU first (no CPU fallback); "
@@ -360,7 +363,8 @@ class Codebook(nn.Module):
             raise RuntimeError("Codebook.enable_device_reservoir: the host reservoir already holds rows; enable it before training")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self._dev = dict(seed=int(seed), c=0, plans={},
+        from .kmeans import device_default
+        self._dev = dict(seed=int(seed), c=0, plans={}, device_kmeans=device_default() if device_kmeans is None else bool(device_kmeans),
                          buf=torch.zeros(self.reservoir_size, self.codebook_dim, dtype=torch.float32, device=w.device),
                          state=torch.zeros(2, dtype=torch.int32, device=w.device))
         self.reservoir = self._dev["buf"][:0]
@@ -440,6 +444,13 @@ class Codebook(nn.Module):
             pool = torch.cat(gathered, dim=0)
         else:
             pool = self.reservoir
+        if self._dev is not None and self._dev["device_kmeans"]:
+            # initial rows from the reservoir's seed at draw = q_counter: a resumed run draws what the uninterrupted one would
+            cent = kmeans_fit(pool, self.codebook_size, on_device=True, seed=self._dev["seed"], draw=self.q_counter).detach().contiguous()
+            if world_size > 1:
+                dist.broadcast(cent, 0)
+            self.embedding.weight.data.copy_(cent)        # in place: a captured step keeps reading the same storage
+            return
         if self._dev is not None:
             # the cluster sums are index_add_: atomics in whatever order the device takes them unless torch is told otherwise
             det, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()

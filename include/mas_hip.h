@@ -785,6 +785,46 @@ int mas_obj_finalize(const float* partial, const MasObjPlan* p, float* out, void
 int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, const float* dout, void* seed,
                      void* stream);
 
+/* -------------------------------------------------------------------------------------------
+ * Whole-image LPIPS-VGG16 (lpips.hip; mas_hip/lpips.py; losses.lpips.hip_path).  Additions inside ABI 10.  Everything of
+ * losses/lpips.py:LPIPS.forward that is not one of the thirteen convolutions (those go through mas_conv_fwd), on plain NHWC maps:
+ * no atlas, no tables.  One batch is [2 B, H, W, C]: the B real images first, then the B reconstructions; tensors of the backward
+ * are the rec half only, [B, ...].  Activations in `dtype` (MAS_BF16 / MAS_F32), arithmetic and sums in fp32, in a fixed order (no
+ * float atomics).  Nothing reads the host; every launch goes to `stream`.  Before anything is launched: null pointers, a dtype other
+ * than MAS_F32 / MAS_BF16, a size < 1, C % 8 != 0 (heads: C outside {64, 128, 256, 512}) are MAS_EINVAL; more than 2^30 pixels
+ * per image is MAS_EUNSUPPORTED.
+ *   mas_lpips_pack_fwd : canvas [2 B, H, W, 8] = (x - shift) / scale in channels 0..2 and 0 in channels 3..7, x = real for the
+ *                        first B images and fake for the rest (each fp32 or bf16, any element strides; equal N, H, W).
+ *   mas_lpips_pack_bwd : the adjoint: dfake (its own dtype and strides, written in full) = dcanvas [B, H, W, 8] (rec half,
+ *                        channels 0..2) / scale.
+ *   mas_lpips_relu_fwd : y = y < 0 ? 0 : y in place over n elements (n % 8 == 0): a NaN stays a NaN, as in F.relu.  (Its backward is
+ *                        mas_obj_relu_bwd.)
+ *   mas_lpips_pool_fwd : y [N, H / 2, W / 2, C] = the 2 x 2 / stride-2 max of x [N, H, W, C] (floor: an odd last row or column is
+ *                        in no window; H, W >= 2); a NaN in a window is its maximum, as in F.max_pool2d.
+ *   mas_lpips_pool_bwd : dy [N, H, W, C] = a > 0 ? seed + (dz [N, H / 2, W / 2, C] at the pixel's window if this pixel is the
+ *                        window's first maximum in row-major order, else 0) : 0; a is the ReLU output that was pooled; a pixel
+ *                        in no window gets the seed only; seed and dz may each be NULL.
+ *   mas_lpips_head_blocks : partial sums per image of one level: ceil(H W / (8192 / C)); negative on a bad argument.
+ *   mas_lpips_head_fwd : feat [2 B, H, W, C] -> partial[b * nblk + j], j < nblk = mas_lpips_head_blocks(H, W, C): fixed-order sums
+ *                        over 8192 / C pixels each of sum_c w_c (r_c / (|r| + 1e-10) - f_c / (|f| + 1e-10))^2 (r real, f rec); the
+ *                        difference is formed before it is squared, the pixel's channels stay in registers.
+ *   mas_lpips_finalize : out[b] = sum_l (sum_j partial_l[b][j]) / hw[l] over n_levels <= 8 levels, whose partials lie one level
+ *                        after the other ([B][blocks[l]] each).  hw and blocks are HOST arrays of n_levels int32.  One work-group
+ *                        per image; a level's sum is 256 strided chains folded by a tree (blocks[l] <= 2^18: no chain of more
+ *                        than 1024 additions).
+ *   mas_lpips_head_bwd : seed [B, H, W, C] = d (sum_b dout[b] out[b]) / d f at this level: coefficient dout[b] / (H W) (dout: B
+ *                        device floats); mas_obj_head_bwd's formula, its rule at |f| = 0 included (the 1 / |f| term is 0).    */
+int mas_lpips_pack_fwd(const MasFaceImage* real, const MasFaceImage* fake, const float* shift, const float* scale, void* canvas, int dtype,
+                       void* stream);
+int mas_lpips_pack_bwd(const void* dcanvas, int dtype, const float* scale, const MasFaceImage* dfake, void* stream);
+int mas_lpips_relu_fwd(void* y, long long n, int dtype, void* stream);
+int mas_lpips_pool_fwd(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
+int mas_lpips_pool_bwd(const void* a, const void* seed, const void* dz, void* dy, int N, int H, int W, int C, int dtype, void* stream);
+int mas_lpips_head_blocks(int H, int W, int C);
+int mas_lpips_head_fwd(const void* feat, const float* w, int B, int H, int W, int C, int dtype, float* partial, void* stream);
+int mas_lpips_finalize(const float* partial, int B, int n_levels, const int32_t* hw, const int32_t* blocks, float* out, void* stream);
+int mas_lpips_head_bwd(const void* feat, const float* w, int B, int H, int W, int C, int dtype, const float* dout, void* seed, void* stream);
+
 /* ---- Codebook reservoir (make-a-scene_amd/csrc/reservoir.hip; Codebook.enable_device_reservoir).  The reference's reservoir of latent
  * rows (models/modules.py:477-481: 10 random positions per image appended, then a random subset of reservoir_size rows kept), stated
  * on sets and kept wholly on the device, so that a training step holding it can be captured into a graph.  An addition inside ABI 10.

@@ -6,7 +6,9 @@ state_dict saved from the reference's module loads with ``strict=True``.  The th
 FLOPs: ~20 GFLOP per 256x256 image and pass -- run on libmas_hip's implicit-GEMM kernels in bf16 with fp32 accumulation, forward
 and data gradient (the network is frozen: no weight gradients); real and reconstructed images go through the stack as ONE batch.
 ReLU, the four 2x2 max-pools and the channel normalisation / squared difference / 1x1 linear heads / spatial mean of the distance
-are the reference's own torch expressions (elementwise and reduction passes).
+are the reference's own torch expressions (elementwise and reduction passes) -- unless the HIP path is switched on (``MAS_LPIPS_HIP=1``
+or ``hip_path(True)``; off by default): then ``LPIPS.forward`` is ``mas_hip.lpips.lpips_distance``, one autograd node that runs those
+passes on csrc/lpips.hip as well and differentiates the reconstruction half only (the envelope: INTEGRATION 3b).
 
 What the reference does at construction and this module cannot: it downloads ``vgg.pth`` and takes torchvision's pretrained VGG16
 (lpips.py:10-15,55,101).  There is no network here: weights come from ``MAS_LPIPS_CKPT`` (a state_dict with the keys above, e.g.
@@ -23,6 +25,29 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from models.modules import Conv2d
+
+_hip = {"on": os.environ.get("MAS_LPIPS_HIP", "0") == "1"}      # read once
+
+
+class hip_path:
+    """``hip_path(on)`` switches the HIP path of ``LPIPS.forward`` on or off for the process; used as ``with hip_path(on):`` the
+    previous setting comes back at the end of the block."""
+
+    def __init__(self, on=True):
+        self._before = _hip["on"]
+        _hip["on"] = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _hip["on"] = self._before
+        return False
+
+
+def hip_path_enabled() -> bool:
+    return _hip["on"]
+
 
 CKPT_PATHS = (os.environ.get("MAS_LPIPS_CKPT", ""), "/home/ubuntu/Make-A-Scene/weights/vgg.pth")      # lpips.py:15
 
@@ -153,7 +178,18 @@ class LPIPS(nn.Module):
             LPIPS._warned = True
             warnings.warn(msg)
 
+    def _takes_hip_path(self, real_x, fake_x):
+        """the switch is on and the call is inside the HIP path's envelope: GPU tensors, evaluation mode (the heads' Dropout is the
+        identity), ``real_x`` is data, equal [B, 3, H >= 16, W >= 16] shapes in fp32 / bf16"""
+        if not _hip["on"] or self.training or not (real_x.is_cuda and fake_x.is_cuda) or real_x.requires_grad:
+            return False
+        from mas_hip.lpips import envelope
+        return envelope(real_x, fake_x) is None
+
     def forward(self, real_x, fake_x):
+        if self._takes_hip_path(real_x, fake_x):
+            from mas_hip.lpips import lpips_distance
+            return lpips_distance(self, real_x, fake_x)
         b = real_x.shape[0]
         feats = self.vgg(self.scaling_layer(torch.cat([real_x, fake_x], dim=0)))            # one pass for both images
         total = 0

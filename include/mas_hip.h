@@ -881,6 +881,54 @@ int mas_kmeans_init(const float* points, int M, int K, int D, long long seed, in
 int mas_kmeans_fit(const float* points, float* centroids, int M, int K, int D, int max_iter, float tol, int64_t* assign, int32_t* info,
                    double* shift, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- Tail of the VQ-IMG objective (make-a-scene_amd/csrc/gan_loss.hip; losses.loss_img.hip_tail).  What follows the
+ * decoder, LPIPS and the discriminator in reference losses/loss_img.py:56-141, with nothing read on the host: the calls capture into a
+ * graph.  Additions inside ABI 10.  No atomics; every sum has one order, fixed by the shape and the CU count: results repeat bit for bit.
+ * Sums: a lane adds MAS_GAN_RUN = 8 fp32 terms as a fixed pairwise tree (each term is rounded once when it is formed and passes through
+ * three additions), everything beyond -- the lane's further runs, lanes, work-groups, the finalize -- is fp64, and the result is rounded
+ * once to fp32: for non-negative terms the error is below (3 + 1 + 1) 2^-24 relative, inside MAS_GAN_RUN 2^-24.
+ *   img, rec: [N, C, H, W], each fp32 or bf16 (MAS_F32 / MAS_BF16), each DENSE MAS_SEG_NCHW or MAS_SEG_NHWC on its own, read in place,
+ *     element alignment only, fewer than 2^31 elements (MAS_EUNSUPPORTED beyond).
+ *   mas_gan_l1_blocks: the work-groups of mas_gan_l1_fwd = the fp64 partial sums its workspace must hold (negative: an error code).
+ *   mas_gan_l1_fwd: partials[b] = work-group b's sum of |rec - img|.  A NaN in either input makes the sum NaN.
+ *   mas_gan_l1_finalize: ONE work-group -> out[0] = the sum, out[1] = sum / numel + perceptual_weight mean(perceptual[0 .. B-1])
+ *     (perceptual: B fp32 on the device, or NULL: the second term is 0) = the reference's nll_loss.
+ *   mas_gan_l1_bwd: coef = grad[0] / (float)numel, ONE fp32 division; drec = +coef where rec > img, -coef where rec < img, exactly 0
+ *     otherwise (equal -- torch.abs's subgradient -- or unordered), cast once to rec's dtype, in rec's layout.  dperceptual (B fp32, may
+ *     be NULL) = grad[0] * (perceptual_weight / (float)B).  grad: one fp32 on the device, the gradient with respect to out[1].
+ *   mas_gan_logits_fwd: ONE work-group over the PatchGAN logits (fp32, contiguous; real may be NULL) -> out[0] = -mean(fake),
+ *     out[1] = mean(relu(1 - real)), out[2] = mean(relu(1 + fake)), out[3] = gate 0.5 (out[1] + out[2]) before rounding, with
+ *     gate = global_step[0] >= disc_start ? disc_factor : 0 read on the device (global_step: one int64, may be NULL: gate = 0), and
+ *     out[4] = gate: five fp32.
+ *   mas_gan_logits_bwd: grad_gen = the gradient of out[0], grad_d = that of out[3] (each one fp32 on the device, or NULL), gate = the
+ *     forward's out + 4 (the counter may have moved since), all fp32:  c = (grad_d[0] * (0.5f * gate[0])) / (float)n;  dfake = (fake > -1 ? c : 0) - grad_gen[0] / (float)n_fake;  dreal = real < 1 ? -c : 0
+ *     (n = the tensor's own count): zero at the hinge knees, as ATen's relu backward.
+ *   mas_gan_combine_fwd: ONE work-group.  nll, g_loss, face, object: one fp32 each (face / object may be NULL); codebook: n_codebook
+ *     fp32, their mean is taken here; nll_grads, g_grads: n_grads fp32 each, the two gradients of the decoder's last weight.  In fp64:
+ *     d_weight = clamp(|nll_grads| / (|g_grads| + 1e-4), 0, 1e4) disc_weight, rounded to fp32; gate as above; c_g = d_weight * gate (fp32);
+ *     loss = nll + c_g g_loss + codebook_weight mean(codebook) + face + object, rounded once.  out = {loss, d_weight, c_g, gate}.
+ *     advance != 0: global_step[0] += 1 after it has been read.
+ *   mas_gan_combine_bwd: one lane.  grads[0] = grad[0] (nll, face, object), grads[1] = grad[0] * out[2] (g_loss), grads[2] = grad[0] *
+ *     (codebook_weight / (float)n_codebook) (every element of codebook); d_weight is a constant of the loss, as in the reference.
+ * Null or misaligned pointers, empty shapes, unknown codes: MAS_EINVAL.                                                              */
+enum { MAS_GAN_RUN = 8 };
+int mas_gan_l1_blocks(int N, int C, int H, int W);
+int mas_gan_l1_fwd(const void* img, int img_dtype, int img_layout, const void* rec, int rec_dtype, int rec_layout, int N, int C, int H,
+                   int W, double* partials, int n_partials, void* stream);
+int mas_gan_l1_finalize(const double* partials, int n_partials, long long numel, const float* perceptual, int B, float perceptual_weight,
+                        float* out, void* stream);
+int mas_gan_l1_bwd(const void* img, int img_dtype, int img_layout, const void* rec, int rec_dtype, int rec_layout, int N, int C, int H,
+                   int W, const float* grad, void* drec, float* dperceptual, int B, float perceptual_weight, void* stream);
+int mas_gan_logits_fwd(const float* fake, long long n_fake, const float* real, long long n_real, const long long* global_step,
+                       long long disc_start, float disc_factor, float* out, void* stream);
+int mas_gan_logits_bwd(const float* fake, long long n_fake, const float* real, long long n_real, const float* grad_gen, const float* grad_d,
+                       const float* gate, float* dfake, float* dreal, void* stream);
+int mas_gan_combine_fwd(const float* nll, const float* g_loss, const float* codebook, long long n_codebook, const float* face,
+                        const float* object, const float* nll_grads, const float* g_grads, long long n_grads, long long* global_step,
+                        long long disc_start, float disc_factor, float disc_weight, float codebook_weight, int advance, float* out,
+                        void* stream);
+int mas_gan_combine_bwd(const float* grad, const float* out, float codebook_weight, long long n_codebook, float* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,15 @@ opts out silently.  ``object_loss``: the object-aware term the reference left co
 default, as in the reference) keeps it a constant 0; ``"lpips"`` is ``losses.object_loss.ObjectLoss`` sharing the perceptual term's
 LPIPS weights; a callable(images, reconstructions, bbox_obj) is used as given.  The arithmetic below is the reference's line for
 line.  ``forward`` keeps the reference's signature and return shapes (optimizer_idx 0 -> ``loss, (nll_loss, object_loss,
-face_loss)``; 1 -> ``d_loss``)."""
+face_loss)``; 1 -> ``d_loss``).
+
+``hip_tail(True)`` / ``MAS_GAN_TAIL_HIP=1`` (off by default): what follows the networks -- the L1 term and its mean with the
+perceptual term, the generator and hinge terms over the logits, the norm / ratio / clamp of the adaptive weight, the gate and the sum --
+runs on csrc/gan_loss.hip as three autograd nodes (``mas_hip.gan_tail``), in fixed-order sums, and reads nothing on the host:
+``global_step`` may then be a 0-dim int64 device tensor (the gate ``global_step >= disc_start`` is evaluated on the device), which is
+what lets ``mas_hip.graphs.GraphedGanStep`` capture the whole step.  The two ``autograd.grad`` calls stay as they are.  With the switch
+off ``forward`` is the code below, unchanged, and a tensor ``global_step`` raises."""
+import os
 import warnings
 
 import torch
@@ -23,6 +31,29 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .discriminator import Discriminator, weights_init
+
+
+_hip = {"on": os.environ.get("MAS_GAN_TAIL_HIP", "0") == "1"}      # read once
+
+
+class hip_tail:
+    """``hip_tail(on)`` switches the HIP tail of ``VQLPIPSWithDiscriminator.forward`` on or off for the process; used as
+    ``with hip_tail(on):`` the previous setting comes back at the end of the block."""
+
+    def __init__(self, on=True):
+        self._before = _hip["on"]
+        _hip["on"] = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _hip["on"] = self._before
+        return False
+
+
+def hip_tail_enabled() -> bool:
+    return _hip["on"]
 
 
 def adopt_weight(weight, global_step, threshold=0, value=0.0):
@@ -43,6 +74,7 @@ def vanilla_d_loss(logits_real, logits_fake):
 
 class VQLPIPSWithDiscriminator(nn.Module):
     _face_warned = False
+    hip_tail = hip_tail                               # (mas_hip.graphs reaches the switch through the module it is handed)
 
     def __init__(self, disc_start, codebook_weight=1.0, pixelloss_weight=1.0, disc_factor=1.0, disc_weight=1.0, perceptual_weight=1.0,
                  perceptual_loss="lpips", face_loss="reference", object_loss=None):
@@ -82,6 +114,9 @@ class VQLPIPSWithDiscriminator(nn.Module):
         self.discriminator_iter_start = disc_start
         self.disc_factor = disc_factor
         self.discriminator_weight = disc_weight
+        self.advance_global_step = False              # HIP tail, tensor global_step: the generator half adds 1 to it after reading it
+        self.last_terms = None                        # HIP tail: the generator half's detached {"g_loss", "d_weight"}
+        self._dev_scalars = {}                        # HIP tail: per device, the int64 step scalar an int is written to, and a zero
 
     def calculate_adaptive_weight(self, nll_loss, g_loss, last_layer):
         nll_grads = torch.autograd.grad(nll_loss, last_layer.weight, retain_graph=True)[0]
@@ -92,6 +127,11 @@ class VQLPIPSWithDiscriminator(nn.Module):
 
     def forward(self, optimizer_idx, global_step, images, reconstructions, codebook_loss=None, bbox_obj=None, bbox_face=None,
                 last_layer=None):
+        if _hip["on"]:
+            return self._forward_hip(optimizer_idx, global_step, images, reconstructions, codebook_loss, bbox_obj, bbox_face, last_layer)
+        if isinstance(global_step, torch.Tensor):
+            raise TypeError("VQLPIPSWithDiscriminator: a tensor global_step belongs to the HIP tail (losses.loss_img.hip_tail(True) / "
+                            "MAS_GAN_TAIL_HIP=1); with the switch off the gate is a host comparison on a Python int")
         if optimizer_idx == 0:  # vqvae loss
             rec_loss = torch.abs(images.contiguous() - reconstructions.contiguous())
             if self.perceptual_loss is not None:
@@ -115,3 +155,46 @@ class VQLPIPSWithDiscriminator(nn.Module):
             logits_real = self.discriminator(images.contiguous().detach())
             logits_fake = self.discriminator(reconstructions.contiguous().detach())
             return disc_factor * hinge_d_loss(logits_real, logits_fake)
+
+    # ---- the tail on csrc/gan_loss.hip (hip_tail / MAS_GAN_TAIL_HIP=1) ---------------------------------------------------------
+    def _scalars(self, device):
+        s = self._dev_scalars.get(device)
+        if s is None:
+            s = self._dev_scalars[device] = (torch.zeros((), dtype=torch.int64, device=device), torch.zeros((), dtype=torch.float32, device=device))
+        return s
+
+    def _forward_hip(self, optimizer_idx, global_step, images, reconstructions, codebook_loss, bbox_obj, bbox_face, last_layer):
+        """the same objective with the L1 term, the logit terms, the adaptive weight, the gate and the sum on the kernels of
+        ``mas_hip.gan_tail``: nothing is read on the host.  ``global_step``: a Python int (written to this module's device scalar) or a
+        0-dim int64 tensor on the images' device, used as is."""
+        from mas_hip import gan_tail as T
+        step, zero = self._scalars(images.device)
+        if isinstance(global_step, torch.Tensor):
+            step = T.check_step(global_step, "VQLPIPSWithDiscriminator")
+        else:
+            step.fill_(int(global_step))
+        if optimizer_idx == 0:  # vqvae loss
+            p_loss = None
+            if self.perceptual_loss is not None:
+                p_loss = self.perceptual_loss(images.contiguous(), reconstructions.contiguous(), bbox_obj)
+            nll_loss = T.nll(images, reconstructions, p_loss, self.perceptual_weight)
+            face_loss = self.face_loss(images, reconstructions, bbox_face) if self.face_loss is not None else None
+            object_loss = None
+            if self.object_loss is not None:
+                if bbox_obj is None:
+                    raise ValueError("VQLPIPSWithDiscriminator: the object term needs bbox_obj (one list of boxes per image)")
+                object_loss = self.object_loss(images, reconstructions, bbox_obj)
+            g_loss = T.generator_term(self.discriminator(reconstructions.contiguous()))
+            nll_grads = torch.autograd.grad(nll_loss, last_layer.weight, retain_graph=True)[0]
+            g_grads = torch.autograd.grad(g_loss, last_layer.weight, retain_graph=True)[0]
+            loss, terms = T.combine(nll_loss, g_loss, codebook_loss, nll_grads, g_grads, step, disc_start=self.discriminator_iter_start,
+                                    disc_factor=self.disc_factor, disc_weight=self.discriminator_weight, codebook_weight=self.codebook_weight,
+                                    face_loss=face_loss, object_loss=object_loss,
+                                    advance=self.advance_global_step and isinstance(global_step, torch.Tensor))
+            self.last_terms = {"g_loss": g_loss.detach(), "d_weight": terms[0]}
+            zero = zero.to(images.dtype)
+            return loss, (nll_loss, zero if object_loss is None else object_loss, zero if face_loss is None else face_loss)
+        if optimizer_idx == 1:  # gan loss
+            logits_real = self.discriminator(images.contiguous().detach())
+            logits_fake = self.discriminator(reconstructions.contiguous().detach())
+            return T.hinge_d_loss(logits_real, logits_fake, step, self.discriminator_iter_start, self.disc_factor)

@@ -49,8 +49,9 @@ The VQ-SEG step needs two more things, both opt-in; without a code
   towards ``accumulate`` (``step.calls``) -- but nothing is captured before the first call (``step.captures == 0`` until then).
 
 Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collectives run on other streams; ``reducer=`` raises), steps
-with more than one optimizer or backward pass (VQ-IMG's), inputs that are not tensors, and a ``loss_fn`` that reads anything on the
-host."""
+with more than one optimizer or backward pass (the VQ-IMG step has its own class below, ``GraphedGanStep``), inputs that are not
+tensors, and a ``loss_fn`` that reads anything on the host."""
+import collections
 import contextlib
 
 import torch
@@ -127,6 +128,7 @@ class GraphedTrainStep:
         if isinstance(example_inputs, torch.Tensor):
             example_inputs = (example_inputs,)
         self.loss_fn, self.optimizer, self.amp_dtype = loss_fn, optimizer, amp_dtype
+        self._opts = [optimizer]
         self.modules = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
         self.captures = 0
         self.graph = self.loss = self._sig = self._keep = None
@@ -162,10 +164,9 @@ class GraphedTrainStep:
 
     def _signature(self, inputs):
         """everything a capture bakes in that the host can still change"""
-        opt = self.optimizer
-        return (opt.state_generation,
-                tuple((tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), len(g["params"])) for g in opt.param_groups),
-                opt.max_grad_norm, opt.ema_decay, opt.ema_warmup, opt.skip_nonfinite, ops.compute_dtype(),
+        return (tuple((opt.state_generation,
+                       tuple((tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), len(g["params"])) for g in opt.param_groups),
+                       opt.max_grad_norm, opt.ema_decay, opt.ema_warmup, opt.skip_nonfinite) for opt in self._opts), ops.compute_dtype(),
                 tuple((tuple(x.shape), x.dtype, x.device) for x in inputs),
                 tuple(m.training for mod in self.modules for m in mod.modules()),
                 tuple((cb.training, cb.phase()) for cb in self.codebooks))
@@ -207,9 +208,11 @@ class GraphedTrainStep:
         hold: the same refresh runs eagerly first (twice: the first one also takes whatever else in the process was stale, the second
         one uploads the table of this step's images alone; it changes no value, and does nothing for a model without convolutions)."""
         for _ in range(2):
-            ops._note_optimizer_step(self.optimizer)
+            for opt in self._opts:
+                ops._note_optimizer_step(opt)
             ops._pack_cache._refresh_stale(self._side.device)
-        ops._note_optimizer_step(self.optimizer)
+        for opt in self._opts:
+            ops._note_optimizer_step(opt)
 
     def _settle_caches(self):
         # the images the graph reads: kept alive here (invalidate_weight_cache() / swap_ema() drop the caches' own references)
@@ -257,10 +260,15 @@ class GraphedTrainStep:
                 torch._foreach_zero_(grads)
         return loss
 
+    @staticmethod
+    def _detached(loss):
+        return loss.detach()
+
     def _warm_up(self, warmup):
         """``warmup`` real training calls, eager, under the conditions of the capture; nothing is captured before the first call"""
         main = torch.cuda.current_stream(self._side.device)
-        self.optimizer.init_state()
+        for opt in self._opts:
+            opt.init_state()
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._ticked():
             for _ in range(warmup):
@@ -272,20 +280,22 @@ class GraphedTrainStep:
     def _capture_phase(self):
         """the graphs of the phase the codebooks are in now: one step when accumulate == 1, else a micro-step and a closing step that share
         the static inputs and one memory pool.  Executes nothing."""
-        opt, k = self.optimizer, self.accumulate
+        opts, k = self._opts, self.accumulate
         self.graph = self.loss = None
         self._graphs = {}                                   # (the old phase's graphs and their memory go first)
         main = torch.cuda.current_stream(self._side.device)
-        params = [p for g in opt.param_groups for p in g["params"]]
+        params = [p for opt in opts for g in opt.param_groups for p in g["params"]]
         rows = [cb._dev["c"] for cb in self.codebooks]
         self._side.wait_stream(main)
         with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._ticked():
             if k == 1:
-                opt.zero_grad(set_to_none=True)
+                for opt in opts:
+                    opt.zero_grad(set_to_none=True)
             pool = None                                     # the closing step's graph shares the micro-step's memory pool
             for closing in ((True,) if k == 1 else (False, True)):
                 for attempt in range(2):
-                    opt.init_state()
+                    for opt in opts:
+                        opt.init_state()
                     self._stale_for_capture()
                     without = [p for p in params if p.requires_grad and p.grad is None] if k > 1 else []
                     graph = torch.cuda.CUDAGraph()
@@ -305,7 +315,7 @@ class GraphedTrainStep:
                     del graph, loss
                     for p in fresh:
                         p.grad = torch.zeros_like(p)
-                self._graphs[closing] = (graph, loss.detach())
+                self._graphs[closing] = (graph, self._detached(loss))
                 pool = graph.pool()
                 self.captures += 1
         main.wait_stream(self._side)
@@ -320,7 +330,8 @@ class GraphedTrainStep:
                 self._graphs = {}
                 self._static = [x.detach().clone() for x in inputs]
             self._capture_phase()
-        self.optimizer.sync_hyperparameters()
+        for opt in self._opts:
+            opt.sync_hyperparameters()
         for s, x in zip(self._static, inputs):
             if x is not s:
                 s.copy_(x, non_blocking=True)
@@ -330,7 +341,8 @@ class GraphedTrainStep:
             if n:
                 cb._note_collected(n)
         if closing:
-            ops._note_optimizer_step(self.optimizer)
+            for opt in self._opts:
+                ops._note_optimizer_step(opt)
         self.loss = loss
         return loss
 
@@ -351,3 +363,120 @@ class GraphedTrainStep:
         self.graph.replay()
         ops._note_optimizer_step(self.optimizer)
         return self.loss
+
+
+class GanStepOut(collections.namedtuple("GanStepOut", "loss d_loss nll_loss g_loss d_weight")):
+    """what one call of ``GraphedGanStep`` returns: the graph's static 0-dim tensors, overwritten by the next call"""
+    __slots__ = ()
+
+
+class GraphedGanStep(GraphedTrainStep):
+    """The VQ-IMG training call -- one forward, the discriminator's backward, the generator's backward with the two ``autograd.grad``
+    calls of the adaptive weight, and on a closing call both Adams -- captured and replayed with ``GraphedTrainStep``'s machinery
+    (warm-up on the side stream, one stream without branches, stale weight caches, signature and lazy recapture, codebook phases ticked
+    eagerly before the replay, a micro-step and a closing-step graph under ``accumulate > 1``, persistent zeroed gradients).
+
+        gopt = mas_hip.optim.Adam(model.parameters(), lr=..., betas=(0.5, 0.9), device_step=True)
+        dopt = mas_hip.optim.Adam(loss.discriminator.parameters(), lr=..., betas=(0.5, 0.9), device_step=True)
+        step = mas_hip.graphs.GraphedGanStep(model, loss, gopt, dopt, example_images, accumulate=8, global_step=0)
+        out = step(images)          # out.loss, out.d_loss, out.nll_loss, out.g_loss, out.d_weight: static 0-dim tensors
+
+    One call, in the order of the reference's loop (train.py:84-103): ``model(images)``; the discriminator loss on detached tensors and
+    its ``backward()``; with ``requires_grad`` of the discriminator's parameters off (host flags, restored afterwards) the generator
+    loss and its ``backward()``; on calls k, 2k, ... ``dopt.step()``, ``gopt.step()`` and the gradients zeroed in place.
+
+    * ``loss`` is a ``losses.loss_img.VQLPIPSWithDiscriminator``; its tail runs with ``hip_tail`` on inside every call of this class,
+      whatever the process-wide switch says: the gate ``global_step >= disc_start`` is evaluated on the device, so the gate opening needs
+      no new capture.  ``step.global_step`` is the 0-dim int64 device counter the captured generator half advances by one per call;
+      ``step.set_global_step(n)`` writes it (a resumed run).  Calls made at construction (``warmup``) count.
+    * the signature holds both optimizers' ``state_generation``, hyperparameters and clip / EMA / guard settings, ``training`` of every
+      module of ``model`` and ``loss``, and the codebook phase; ``sync_hyperparameters()`` of both runs before each replay.
+    * refused at construction: an optimizer without ``device_step``, a codebook without its device reservoir, a ``reducer``, and a
+      ``face_loss`` / ``object_loss`` on the loss (their crops are cut from host box lists).  The perceptual term may be LPIPS with its
+      HIP path on or off, any capturable callable, or ``None``."""
+
+    def __init__(self, model, loss, gen_optimizer, disc_optimizer, example_images, *, amp_dtype=None, accumulate=1, global_step=0, warmup=1,
+                 reducer=None):
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int):
+            raise TypeError(f"GraphedGanStep: accumulate must be an integer (calls per optimizer step), got {accumulate!r}")
+        if accumulate < 1:
+            raise ValueError(f"GraphedGanStep: accumulate must be at least 1, got {accumulate}")
+        if reducer is not None:
+            raise NotImplementedError("GraphedGanStep: a gradient reducer runs collectives on other streams, which one captured stream cannot "
+                                      "hold; train data-parallel runs eagerly")
+        for name, opt in (("generator", gen_optimizer), ("discriminator", disc_optimizer)):
+            if not isinstance(opt, optim.Adam) or not opt.device_step:
+                raise TypeError(f"GraphedGanStep: the {name}'s optimizer must be mas_hip.optim.Adam / AdamW with device_step=True (a step whose "
+                                f"count, bias corrections and learning rate live on the device), got {type(opt).__name__}"
+                                + ("" if not isinstance(opt, optim.Adam) else " with device_step=False"))
+        for name in ("face_loss", "object_loss"):
+            if getattr(loss, name, None) is not None:
+                raise NotImplementedError(f"GraphedGanStep: the loss has a {name}, whose crops are cut from host box lists that a capture "
+                                          f"cannot hold; build the loss with {name}=None, or train eagerly")
+        if not hasattr(loss, "hip_tail") or not hasattr(loss, "discriminator"):
+            raise TypeError(f"GraphedGanStep: the loss must be a losses.loss_img.VQLPIPSWithDiscriminator, got {type(loss).__name__}")
+        if int(warmup) < 1:
+            raise ValueError("GraphedGanStep: warmup must be at least 1 (the capture needs every buffer and GEMM choice settled)")
+        self._check_inputs((example_images,))
+        self.model, self.loss_module, self.amp_dtype = model, loss, amp_dtype
+        self.gen_optimizer, self.disc_optimizer = gen_optimizer, disc_optimizer
+        self.optimizer, self._opts = gen_optimizer, [disc_optimizer, gen_optimizer]
+        self.modules = [model, loss]
+        self.captures = 0
+        self.graph = self.loss = self._sig = self._keep = None
+        self.codebooks = []
+        for mod in self.modules:
+            self.codebooks += [m for m in mod.modules() if hasattr(m, "enable_device_reservoir") and not any(m is s for s in self.codebooks)]
+        for cb in self.codebooks:
+            if not getattr(cb, "device_reservoir", False):
+                raise RuntimeError("GraphedGanStep: a Codebook without its device reservoir cannot be captured (its reservoir is kept by CPU "
+                                   "permutations and a growing tensor): call codebook.enable_device_reservoir() first")
+        self.accumulate, self.calls = accumulate, 0
+        self._graphs, self._cb_rows = {}, []
+        self._side = torch.cuda.Stream(device=example_images.device)
+        self._static = [example_images.detach().clone()]
+        self.global_step = torch.full((), int(global_step), dtype=torch.int64, device=example_images.device)
+        self._warm_up(int(warmup))
+
+    def set_global_step(self, n):
+        """writes the device counter (a resume); no capture depends on its value"""
+        self.global_step.fill_(int(n))
+
+    @staticmethod
+    def _detached(out):
+        return GanStepOut(*(t.detach() for t in out))
+
+    def _step(self, closing):
+        model, crit, images = self.model, self.loss_module, self._static[0]
+        if self.accumulate == 1:
+            for opt in self._opts:
+                opt.zero_grad(set_to_none=True)
+        disc = list(crit.discriminator.parameters())
+        flags, advance = [p.requires_grad for p in disc], crit.advance_global_step
+        with crit.hip_tail(True):
+            rec, q_loss = model(images)
+            d_loss = crit(1, self.global_step, images, rec)
+            d_loss.backward()
+            try:
+                for p in disc:
+                    p.requires_grad_(False)
+                crit.advance_global_step = True
+                loss, (nll_loss, _, _) = crit(0, self.global_step, images, rec, q_loss, last_layer=model.decoder.model[-1])
+                loss.backward()
+            finally:
+                crit.advance_global_step = advance
+                for p, f in zip(disc, flags):
+                    p.requires_grad_(f)
+        terms = crit.last_terms
+        if closing:
+            self.disc_optimizer.step()
+            self.gen_optimizer.step()
+            if self.accumulate > 1:
+                grads = [p.grad for opt in self._opts for g in opt.param_groups for p in g["params"] if p.grad is not None]
+                if grads:
+                    torch._foreach_zero_(grads)
+        return GanStepOut(loss, d_loss, nll_loss, terms["g_loss"], terms["d_weight"])
+
+    def __call__(self, images):
+        self._check_inputs((images,))
+        return self._call_phased((images,))

@@ -708,9 +708,28 @@ int mas_bn_bwd_apply_act(const void* x, const void* dy, const float* mean_rstd, 
  *   mas_face_l1_fwd   : out6[i] = alpha_i * sum |p0 - p1| / chw_i over the `half` row pairs (row q against row half + q) of feature i,
  *                       out6[5] = their sum; workspace of mas_face_l1_workspace(f) floats.  Two launches (partials, fixed-order fold).
  *   mas_face_l1_bwd   : seeds[i] [nb rows of feature i] = (dl6[i] + dl6[5]) * alpha_i * sign(p(row0 + k) - p(row0 + k - half)) / chw_i
- *                       (seeds: a HOST array of five device pointers; sign(0) = 0).                                                  */
+ *                       (seeds: a HOST array of five device pointers; sign(0) = 0).
+ *
+ * (Additions inside ABI v10.)  The same four passes with the rows read from a DEVICE table of fixed capacity, so that launch arguments,
+ * grids and every shape are the same whatever the boxes are (a captured graph replays them; the host rewrites the table before each replay):
+ *   The table: MAS_FACE_TABLE_INTS int32 on the device.  Slot s of MAS_FACE_SLOTS = 6 is the MasFaceRow at ints [10 s, 10 s + 10)
+ *     (its ten fields in order), valid[s] (!= 0: the slot holds a row) is int 60 + s, n_pairs int 66, int 67 is zero.  Row q < half of
+ *     the reference's cat([gt], [rec])[:6] sits in slot q, row half + q in slot 3 + q: pair q is (slot q, slot 3 + q) and is valid iff
+ *     q < n_pairs; every rec row sits in slots 3..5.  A slot is also taken as empty when its fields could not have passed the host's
+ *     checks (b outside the images, a size <= 0, a resized side below 254, a centre crop outside the resized crop, src not 0 / 1), and
+ *     n_pairs outside 0..3 is clamped.
+ *   mas_face_crop_fwd_dev : mas_face_crop_fwd into out [6][254][254][3]; an empty slot's row is written as zeros.
+ *   mas_face_l1_fwd_dev   : mas_face_l1_fwd over six rows per feature (f->half must be 3: p0 = rows 0..2, p1 = rows 3..5; workspace of
+ *                       mas_face_l1_workspace(f) floats); the elements of an invalid pair add exactly 0.0f, and the valid pairs are
+ *                       summed in the order mas_face_l1_fwd uses for half = n_pairs.
+ *   mas_face_l1_bwd_dev   : seeds[i] [3 rows of feature i] for slots 3..5: mas_face_l1_bwd's value where the pair is valid and the slot
+ *                       holds a rec row (src 1), zeros elsewhere.  Every element is written.
+ *   mas_face_crop_bwd_dev : mas_face_crop_bwd over slots 3, 4, 5 in that order (dfaces [3][254][254][3]), taking the slots that hold a
+ *                       rec row; drec is written in full (zeros without one).                                                        */
 #define MAS_FACE_SIZE 254
 #define MAS_FACE_MAX_ROWS 8
+#define MAS_FACE_SLOTS 6
+#define MAS_FACE_TABLE_INTS 68
 typedef struct { int32_t src, b, top, left, h, w, rh, rw, ct, cl; } MasFaceRow;
 typedef struct { void* data; int32_t dtype, N, C, H, W, pad_; int64_t sn, sc, sh, sw; } MasFaceImage;
 typedef struct { const float* weight; const float* bias; const float* mean; const float* var; int32_t C, off; float eps; int32_t pad_; } MasFaceBnItem;
@@ -732,6 +751,11 @@ int mas_face_subsample2x(const void* x, void* y, int dtype, int N, int H, int W,
 int mas_face_l1_workspace(const MasFaceFeats* f);
 int mas_face_l1_fwd(const MasFaceFeats* f, float* workspace, float* out6, void* stream);
 int mas_face_l1_bwd(const MasFaceFeats* f, int row0, int nb, const float* dl6, void* const* seeds, void* stream);
+int mas_face_crop_fwd_dev(const MasFaceImage* img, const MasFaceImage* rec, const int32_t* table_dev, void* out, int out_dtype,
+                          void* stream);
+int mas_face_l1_fwd_dev(const MasFaceFeats* f, const int32_t* table_dev, float* workspace, float* out6, void* stream);
+int mas_face_l1_bwd_dev(const MasFaceFeats* f, const int32_t* table_dev, const float* dl6, void* const* seeds, void* stream);
+int mas_face_crop_bwd_dev(const float* dfaces, const int32_t* table_dev, const MasFaceImage* drec, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * The object-aware term of the VQ-IMG objective (Make-A-Scene section 3.2): LPIPS-VGG16 on every object crop of a batch AT ONCE

@@ -10,7 +10,9 @@
 //   the 53 evaluation-mode BatchNorm affine pairs from the running statistics, one launch per forward (never cached: DDP's
 //     broadcast_buffers rewrites the buffers before every forward);
 //   the Bottleneck join relu(bn3(y3) + shortcut) and the ReLU-mask-times-scale backward passes;
-//   the feature L1 distances (fixed-order two-stage sums) and their gradient seeds.
+//   the feature L1 distances (fixed-order two-stage sums) and their gradient seeds;
+//   the crop, its adjoint and the L1 passes once more with the rows read from a device table of six fixed slots (*_dev): launch
+//     arguments, grids and shapes that do not depend on the boxes, for a captured graph.
 // Activations are NHWC in bf16 or fp32; arithmetic in fp32.
 #include "mas_common.h"
 
@@ -104,6 +106,113 @@ __global__ __launch_bounds__(NT) void crop_bwd_kernel(const float* __restrict__ 
         const float sy = (float)row.h / (float)row.rh, sx = (float)row.w / (float)row.rw;
         const float supy = sy >= 1.0f ? sy : 1.0f, supx = sx >= 1.0f ? sx : 1.0f;
         // resized indices i whose window [center - support, center + support) can hold the input index: center = s (i + 0.5)
+        const int ylo = max((int)floorf(((float)cy + 0.5f - supy) / sy - 0.5f) - 1, row.ct);
+        const int yhi = min((int)ceilf(((float)cy + 0.5f + supy) / sy - 0.5f) + 1, row.ct + FS - 1);
+        const int xlo = max((int)floorf(((float)cx + 0.5f - supx) / sx - 0.5f) - 1, row.cl);
+        const int xhi = min((int)ceilf(((float)cx + 0.5f + supx) / sx - 0.5f) + 1, row.cl + FS - 1);
+        const float* d = dfaces + (size_t)r * FS * FS * 3;
+        for (int i = ylo; i <= yhi; ++i) {
+            const float wy = tap_weight(make_taps(i, row.h, sy), cy);
+            if (wy == 0.0f) continue;
+            float h[3] = {0.0f, 0.0f, 0.0f};
+            for (int k = xlo; k <= xhi; ++k) {
+                const float wx = tap_weight(make_taps(k, row.w, sx), cx);
+                if (wx == 0.0f) continue;
+                const float* g = d + ((size_t)(i - row.ct) * FS + (k - row.cl)) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) h[c] += wx * g[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += wy * h[c];
+        }
+    }
+    TR* o = reinterpret_cast<TR*>(drec.data);
+    const long long base = (long long)b * drec.sn + (long long)y * drec.sh + (long long)x * drec.sw;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[base + c * drec.sc] = (TR)acc[c];
+}
+
+// ---- the rows in a DEVICE table of MAS_FACE_SLOTS slots (MAS_FACE_TABLE_INTS int32, include/mas_hip.h): arguments, grids and shapes do
+// not depend on the boxes.
+// A slot counts as empty unless its flag is set AND its fields could have passed check_rows (the host's check is the contract; this
+// one keeps a table that was never written, or written for other images, from indexing outside them).
+constexpr int SLOTS = MAS_FACE_SLOTS;
+constexpr int PAIRS = SLOTS / 2;
+struct FaceSlots { MasFaceRow row[SLOTS]; int32_t valid[SLOTS]; int32_t n_pairs; int32_t pad_; };       // the table's ints, named
+static_assert(sizeof(MasFaceRow) == 10 * sizeof(int32_t) && sizeof(FaceSlots) == MAS_FACE_TABLE_INTS * sizeof(int32_t), "the table's layout");
+
+__device__ __forceinline__ bool slot_ok(const MasFaceRow& r, int valid, int n_images) {
+    return valid != 0 && (unsigned)r.src <= 1u && (unsigned)r.b < (unsigned)n_images && r.h > 0 && r.w > 0 && r.rh >= FS && r.rw >= FS &&
+           r.ct >= 0 && r.cl >= 0 && r.ct <= r.rh - FS && r.cl <= r.rw - FS;
+}
+
+// bit q: pair q = (slot q, slot PAIRS + q) is valid.  The table's address and the indices are uniform: scalar loads, once per wave.
+// (The L1 passes read feature rows only, never the images: any b >= 0 is in range for them.)
+__device__ __forceinline__ unsigned pair_mask(const FaceSlots* __restrict__ t) {
+    const int np = min(max(t->n_pairs, 0), PAIRS);
+    unsigned m = 0u;
+#pragma unroll
+    for (int q = 0; q < PAIRS; ++q)
+        if (q < np && slot_ok(t->row[q], t->valid[q], 0x7fffffff) && slot_ok(t->row[PAIRS + q], t->valid[PAIRS + q], 0x7fffffff)) m |= 1u << q;
+    return m;
+}
+__device__ __forceinline__ int row_of(long long e, long long chw) { return (e >= chw) + (e >= 2 * chw); }     // e < PAIRS * chw
+static_assert(PAIRS == 3, "row_of counts two row boundaries");
+
+// crop_fwd_kernel with the row read from the table (blockIdx.y = slot); an empty slot's row is zeros
+template <typename TO>
+__global__ __launch_bounds__(NT) void crop_fwd_dev_kernel(MasFaceImage img, MasFaceImage rec, const FaceSlots* __restrict__ table,
+                                                          TO* __restrict__ out) {
+    const int r = blockIdx.y;
+    const int p = blockIdx.x * NT + threadIdx.x;
+    if (p >= FS * FS) return;
+    const MasFaceRow row = table->row[r];
+    const MasFaceImage& im = row.src ? rec : img;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (slot_ok(row, table->valid[r], im.N)) {
+        const int oy = p / FS, ox = p % FS;
+        const float sy = (float)row.h / (float)row.rh, sx = (float)row.w / (float)row.rw;
+        const Taps ty = make_taps(oy + row.ct, row.h, sy), tx = make_taps(ox + row.cl, row.w, sx);
+        for (int j = ty.lo; j < ty.hi; ++j) {
+            const float wy = tap_weight(ty, j);
+            const int iy = row.top + j;
+            float h[3] = {0.0f, 0.0f, 0.0f};
+            if (iy >= 0 && iy < im.H) {
+                for (int i = tx.lo; i < tx.hi; ++i) {
+                    const int ix = row.left + i;
+                    if (ix < 0 || ix >= im.W) continue;
+                    const float wx = tap_weight(tx, i);
+                    const long long base = (long long)row.b * im.sn + (long long)iy * im.sh + (long long)ix * im.sw;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) h[c] += wx * ld_any(im.data, im.dtype, base + c * im.sc);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] += wy * h[c];
+        }
+    }
+    TO* o = out + ((size_t)r * FS * FS + p) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (TO)acc[c];
+}
+
+// crop_bwd_kernel over slots PAIRS .. SLOTS - 1 in that order (dfaces [PAIRS][FS][FS][3]): the slots that hold a rec row
+template <typename TR>
+__global__ __launch_bounds__(NT) void crop_bwd_dev_kernel(const float* __restrict__ dfaces, const FaceSlots* __restrict__ table,
+                                                          MasFaceImage drec) {
+    const long long p = (long long)blockIdx.x * NT + threadIdx.x;
+    const long long hw = (long long)drec.H * drec.W;
+    if (p >= (long long)drec.N * hw) return;
+    const int b = (int)(p / hw);
+    const int y = (int)((p % hw) / drec.W), x = (int)(p % drec.W);
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    for (int r = 0; r < PAIRS; ++r) {
+        const MasFaceRow row = table->row[PAIRS + r];
+        if (!slot_ok(row, table->valid[PAIRS + r], drec.N) || row.src != 1) continue;
+        const int cy = y - row.top, cx = x - row.left;
+        if (row.b != b || cy < 0 || cy >= row.h || cx < 0 || cx >= row.w) continue;
+        const float sy = (float)row.h / (float)row.rh, sx = (float)row.w / (float)row.rw;
+        const float supy = sy >= 1.0f ? sy : 1.0f, supx = sx >= 1.0f ? sx : 1.0f;
         const int ylo = max((int)floorf(((float)cy + 0.5f - supy) / sy - 0.5f) - 1, row.ct);
         const int yhi = min((int)ceilf(((float)cy + 0.5f + supy) / sy - 0.5f) + 1, row.ct + FS - 1);
         const int xlo = max((int)floorf(((float)cx + 0.5f - supx) / sx - 0.5f) - 1, row.cl);
@@ -424,6 +533,57 @@ __global__ __launch_bounds__(NT) void l1_bwd_kernel(MasFaceFeats f, L1Blocks lb,
     Quad<T>::st(reinterpret_cast<T*>(seeds.p[fi]) + e, o);
 }
 
+// l1_partial_kernel over PAIRS pairs of capacity (f.half == PAIRS: p0 = rows 0 .. PAIRS - 1, p1 = rows PAIRS .. SLOTS - 1).  The valid pairs
+// are a prefix of the element range, and a block's elements are those of l1_partial_kernel's block of the same index for half = n_pairs:
+// with the masked lanes adding 0 as its out-of-range lanes do, partial[blk0[fi] + k] holds the same bits for every k it has, and 0 beyond.
+template <typename T>
+__global__ __launch_bounds__(NT) void l1_partial_dev_kernel(MasFaceFeats f, L1Blocks lb, const FaceSlots* __restrict__ table,
+                                                            float* __restrict__ partial) {
+    __shared__ float red[NT];
+    const int b = blockIdx.x;
+    int fi = 0;
+    while (fi < 4 && b >= lb.blk0[fi + 1]) ++fi;
+    const T* p = reinterpret_cast<const T*>(f.p[fi]);
+    const long long chw = f.chw[fi];
+    const long long n = (long long)PAIRS * chw;
+    const long long start = (long long)(b - lb.blk0[fi]) * L1_CHUNK;
+    const unsigned mask = pair_mask(table);
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < L1_QUADS; ++k) {
+        const long long e = start + 4 * ((long long)k * NT + threadIdx.x);
+        if (e < n && ((mask >> row_of(e, chw)) & 1u)) {             // (chw is a multiple of 4: a quad never straddles two rows)
+            const f32x4 a = Quad<T>::ld(p + e), c = Quad<T>::ld(p + n + e);
+            s += fabsf(a[0] - c[0]) + fabsf(a[1] - c[1]) + fabsf(a[2] - c[2]) + fabsf(a[3] - c[3]);
+        }
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) partial[b] = s;
+}
+
+// l1_bwd_kernel for slots PAIRS .. SLOTS - 1: every element of the seeds is written, zeros where the pair is invalid or the slot holds a gt row
+template <typename T>
+__global__ __launch_bounds__(NT) void l1_bwd_dev_kernel(MasFaceFeats f, L1Blocks lb, const FaceSlots* __restrict__ table,
+                                                        const float* __restrict__ dl6, SeedPtrs seeds) {
+    const int b = blockIdx.x;
+    int fi = 0;
+    while (fi < 4 && b >= lb.blk0[fi + 1]) ++fi;
+    const long long chw = f.chw[fi];
+    const long long n = (long long)PAIRS * chw;
+    const long long e = 4 * ((long long)(b - lb.blk0[fi]) * NT + threadIdx.x);
+    if (e >= n) return;
+    const int q = row_of(e, chw);
+    f32x4 o = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (((pair_mask(table) >> q) & 1u) && table->row[PAIRS + q].src == 1) {
+        const T* p = reinterpret_cast<const T*>(f.p[fi]);
+        const float coef = (dl6[fi] + dl6[5]) * f.alpha[fi] / (float)chw;
+        const f32x4 a = Quad<T>::ld(p + n + e), c = Quad<T>::ld(p + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = a[j] > c[j] ? coef : (a[j] < c[j] ? -coef : 0.0f);
+    }
+    Quad<T>::st(reinterpret_cast<T*>(seeds.p[fi]) + e, o);
+}
+
 int ew_grid(long long n4) {
     long long g = (n4 + NT - 1) / NT;
     const long long cap = 8LL * mas_num_cus();
@@ -671,5 +831,73 @@ extern "C" int mas_face_l1_bwd(const MasFaceFeats* f, int row0, int nb, const fl
     if (f->dtype == MAS_F32) hipLaunchKernelGGL(l1_bwd_kernel<float>, dim3(lb.blk0[5]), dim3(NT), 0, s, *f, lb, row0, nb, dl6, sp);
     else hipLaunchKernelGGL(l1_bwd_kernel<bf16_t>, dim3(lb.blk0[5]), dim3(NT), 0, s, *f, lb, row0, nb, dl6, sp);
     MAS_CHECK_LAUNCH("face_l1_bwd");
+    return MAS_OK;
+}
+
+// ---- the four passes on a device table of MAS_FACE_SLOTS slots (include/mas_hip.h): nothing below depends on the table's contents
+static const FaceSlots* slots_of(const int32_t* table_dev) { return reinterpret_cast<const FaceSlots*>(table_dev); }
+
+extern "C" int mas_face_crop_fwd_dev(const MasFaceImage* img, const MasFaceImage* rec, const int32_t* table_dev, void* out, int out_dtype,
+                                     void* stream) {
+    MAS_ENTER();
+    if (int rc = check_image(img, "face_crop_fwd_dev")) return rc;
+    if (int rc = check_image(rec, "face_crop_fwd_dev")) return rc;
+    if (!table_dev || !out) MAS_FAIL(MAS_EINVAL, "face_crop_fwd_dev: null table or output");
+    if (!dtype_ok(out_dtype)) MAS_FAIL(MAS_EINVAL, "face_crop_fwd_dev: dtype %d", out_dtype);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(mas_cdiv(FS * FS, NT), SLOTS);
+    if (out_dtype == MAS_F32) hipLaunchKernelGGL(crop_fwd_dev_kernel<float>, grid, dim3(NT), 0, s, *img, *rec, slots_of(table_dev), (float*)out);
+    else hipLaunchKernelGGL(crop_fwd_dev_kernel<bf16_t>, grid, dim3(NT), 0, s, *img, *rec, slots_of(table_dev), (bf16_t*)out);
+    MAS_CHECK_LAUNCH("face_crop_fwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_face_crop_bwd_dev(const float* dfaces, const int32_t* table_dev, const MasFaceImage* drec, void* stream) {
+    MAS_ENTER();
+    if (!dfaces || !table_dev) MAS_FAIL(MAS_EINVAL, "face_crop_bwd_dev: null gradient or table");
+    if (int rc = check_image(drec, "face_crop_bwd_dev")) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const long long px = (long long)drec->N * drec->H * drec->W;
+    const dim3 grid((unsigned)((px + NT - 1) / NT));
+    if (drec->dtype == MAS_F32) hipLaunchKernelGGL(crop_bwd_dev_kernel<float>, grid, dim3(NT), 0, s, dfaces, slots_of(table_dev), *drec);
+    else hipLaunchKernelGGL(crop_bwd_dev_kernel<bf16_t>, grid, dim3(NT), 0, s, dfaces, slots_of(table_dev), *drec);
+    MAS_CHECK_LAUNCH("face_crop_bwd_dev");
+    return MAS_OK;
+}
+
+static int check_feats_dev(const MasFaceFeats* f, const char* what) {
+    if (int rc = check_feats(f, what)) return rc;
+    if (f->half != PAIRS) MAS_FAIL(MAS_EINVAL, "%s: half = %d (the table's capacity is %d pairs)", what, f->half, PAIRS);
+    return MAS_OK;
+}
+
+extern "C" int mas_face_l1_fwd_dev(const MasFaceFeats* f, const int32_t* table_dev, float* workspace, float* out6, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_feats_dev(f, "face_l1_fwd_dev")) return rc;
+    if (!table_dev || !workspace || !out6) MAS_FAIL(MAS_EINVAL, "face_l1_fwd_dev: null argument");
+    const L1Blocks lb = l1_blocks(f, PAIRS, L1_CHUNK);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (f->dtype == MAS_F32) hipLaunchKernelGGL(l1_partial_dev_kernel<float>, dim3(lb.blk0[5]), dim3(NT), 0, s, *f, lb, slots_of(table_dev), workspace);
+    else hipLaunchKernelGGL(l1_partial_dev_kernel<bf16_t>, dim3(lb.blk0[5]), dim3(NT), 0, s, *f, lb, slots_of(table_dev), workspace);
+    MAS_CHECK_LAUNCH("face_l1_partial_dev");
+    hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(NT), 0, s, *f, lb, (const float*)workspace, out6);
+    MAS_CHECK_LAUNCH("face_l1_final");
+    return MAS_OK;
+}
+
+extern "C" int mas_face_l1_bwd_dev(const MasFaceFeats* f, const int32_t* table_dev, const float* dl6, void* const* seeds, void* stream) {
+    MAS_ENTER();
+    if (int rc = check_feats_dev(f, "face_l1_bwd_dev")) return rc;
+    if (!table_dev || !dl6 || !seeds) MAS_FAIL(MAS_EINVAL, "face_l1_bwd_dev: null argument");
+    SeedPtrs sp;
+    for (int i = 0; i < 5; ++i) {
+        if (!seeds[i]) MAS_FAIL(MAS_EINVAL, "face_l1_bwd_dev: null seed %d", i);
+        sp.p[i] = seeds[i];
+    }
+    const L1Blocks lb = l1_blocks(f, PAIRS, 4 * NT);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (f->dtype == MAS_F32) hipLaunchKernelGGL(l1_bwd_dev_kernel<float>, dim3(lb.blk0[5]), dim3(NT), 0, s, *f, lb, slots_of(table_dev), dl6, sp);
+    else hipLaunchKernelGGL(l1_bwd_dev_kernel<bf16_t>, dim3(lb.blk0[5]), dim3(NT), 0, s, *f, lb, slots_of(table_dev), dl6, sp);
+    MAS_CHECK_LAUNCH("face_l1_bwd_dev");
     return MAS_OK;
 }

@@ -11,6 +11,9 @@ no ATen kernel on an activation map.  Its backward reaches ``rec`` only (the par
 The reference's row selection is reproduced exactly: ``cat([gt faces], [rec faces])[:6]``, pairs (q, half + q) -- with n = 4 faces
 the pairs are (gt0, gt3), (gt1, rec0), (gt2, rec1), and with n >= 6 no rec face takes part.
 
+``forward(img, rec, table)`` with a ``mas_hip.face.FaceTable`` instead of the box lists is the same term at fixed capacity (six rows,
+whatever the table holds): the node a captured graph replays (``mas_hip.graphs.GraphedGanStep``).  Evaluation mode only.
+
 ``train()`` (training-mode BatchNorm, outside the envelope): the reference's arithmetic on the torch modules, fed by the HIP crop.
 
 Weights: ``MAS_FACE_CKPT``, or the reference's path if that file exists; loaded with ``strict=False`` as the reference does (extra
@@ -139,6 +142,14 @@ class FaceLoss(nn.Module):
         """sum_i alpha_i * |f_i(p0) - f_i(p1)|.sum(0).mean() over the reference's row pairs; ``img.new_tensor(0)`` without faces.
         ``self.last_diffs``: the five weighted terms of the last evaluation-mode call (None without faces)."""
         from mas_hip import face as F
+        if isinstance(bbox, F.FaceTable):
+            # the boxes in a device table: the fixed-capacity node, which runs whatever the table holds and reads nothing on the host
+            if self.training:
+                raise RuntimeError("FaceLoss: a FaceTable belongs to the evaluation-mode HIP path (training-mode BatchNorm runs on the torch "
+                                   "modules, from host box lists)")
+            out = F.face_loss_static(self, img, rec, bbox)
+            self.last_diffs = out[:5]
+            return out[5]
         if self.training:
             return self._forward_train(img, rec, bbox)
         out = F.face_loss(self, img, rec, bbox)

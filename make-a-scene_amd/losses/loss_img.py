@@ -21,7 +21,9 @@ face_loss)``; 1 -> ``d_loss``).
 perceptual term, the generator and hinge terms over the logits, the norm / ratio / clamp of the adaptive weight, the gate and the sum --
 runs on csrc/gan_loss.hip as three autograd nodes (``mas_hip.gan_tail``), in fixed-order sums, and reads nothing on the host:
 ``global_step`` may then be a 0-dim int64 device tensor (the gate ``global_step >= disc_start`` is evaluated on the device), which is
-what lets ``mas_hip.graphs.GraphedGanStep`` capture the whole step.  The two ``autograd.grad`` calls stay as they are.  With the switch
+what lets ``mas_hip.graphs.GraphedGanStep`` capture the whole step.  The two ``autograd.grad`` calls stay as they are.  On this path
+``bbox_face`` may also be a ``mas_hip.face.FaceTable`` (a ``FaceLoss`` then runs its fixed-capacity node, which a capture can hold), and a
+``FaceLoss`` with ``bbox_face=None`` -- a batch without faces -- is left out of the sum.  With the switch
 off ``forward`` is the code below, unchanged, and a tensor ``global_step`` raises."""
 import os
 import warnings
@@ -31,6 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .discriminator import Discriminator, weights_init
+from .face_loss import FaceLoss
 
 
 _hip = {"on": os.environ.get("MAS_GAN_TAIL_HIP", "0") == "1"}      # read once
@@ -89,7 +92,7 @@ class VQLPIPSWithDiscriminator(nn.Module):
         if isinstance(face_loss, str):
             if face_loss != "reference":
                 raise ValueError("face_loss: a callable, None, or 'reference' (the default)")
-            from .face_loss import FaceLoss, ckpt_path
+            from .face_loss import ckpt_path
             if ckpt_path() is not None:
                 face_loss = FaceLoss()
             else:
@@ -178,7 +181,11 @@ class VQLPIPSWithDiscriminator(nn.Module):
             if self.perceptual_loss is not None:
                 p_loss = self.perceptual_loss(images.contiguous(), reconstructions.contiguous(), bbox_obj)
             nll_loss = T.nll(images, reconstructions, p_loss, self.perceptual_weight)
-            face_loss = self.face_loss(images, reconstructions, bbox_face) if self.face_loss is not None else None
+            # (a FaceLoss takes lists of boxes or a mas_hip.face.FaceTable; with bbox_face=None -- a batch without faces -- the term is
+            # absent, as it is with face_loss=None.  Any other callable is handed what the caller gave.)
+            face_loss = None
+            if self.face_loss is not None and not (bbox_face is None and isinstance(self.face_loss, FaceLoss)):
+                face_loss = self.face_loss(images, reconstructions, bbox_face)
             object_loss = None
             if self.object_loss is not None:
                 if bbox_obj is None:

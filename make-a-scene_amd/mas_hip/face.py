@@ -4,14 +4,19 @@ Host side of the face-aware VQ-IMG term: the face geometry (torchvision's crop /
 from the host boxes -- no device-to-host synchronisation), the reference's ``faces[:6]`` row selection, and the frozen ResNet-50 in
 evaluation mode, forward and data gradient.  Activations are NHWC in the compute dtype (bf16 by default, fp32 in parity mode).  The
 backward runs the network only for the rows that come from ``rec``: they are always the tail of the surviving rows (the row pairs
-are (q, half + q) and ``half = min(n, 3) <= n``), so it works on slices of the saved maps."""
+are (q, half + q) and ``half = min(n, 3) <= n``), so it works on slices of the saved maps.
+
+``FaceTable`` / ``_FaceLossStatic``: the same term at fixed capacity.  The rows sit in six fixed slots of a DEVICE table that the host
+rewrites before each call (planning and checks stay here, on the host boxes); the node always runs six rows forward and the slice [3:6]
+backward, so its launches and shapes do not depend on the boxes and a captured graph of it follows the table of each replay
+(``mas_hip.graphs.GraphedGanStep``)."""
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
 
-from . import ACT_NONE, FACE_SIZE, FaceBnItem, FaceFeats, FaceRow, _DT, _image, _ptr as _p, _require_cuda, _stream, check, lib
+from . import ACT_NONE, FACE_SIZE, FACE_SLOTS, FACE_TABLE_INTS, FaceBnItem, FaceFeats, FaceRow, _DT, _image, _ptr as _p, _require_cuda, _stream, check, lib
 from . import ops
 
 FACE = FACE_SIZE      # CenterCrop(254): MAS_FACE_SIZE of include/mas_hip.h
@@ -72,6 +77,100 @@ def plan(bboxes, n_images: int):
         g = geo[i]
         rows.append(FaceRow(src, faces[i][0], g["top"], g["left"], g["h"], g["w"], g["rh"], g["rw"], g["ct"], g["cl"]))
     return len(faces), rows
+
+
+# --------------------------------------------------------------------------- #
+# the rows as six fixed slots of a device table (what a captured graph reads)
+# --------------------------------------------------------------------------- #
+SLOTS = FACE_SLOTS    # MAS_FACE_SLOTS of include/mas_hip.h
+PAIRS = SLOTS // 2
+
+
+class FaceSlots(C.Structure):
+    """The table's MAS_FACE_TABLE_INTS int32 (include/mas_hip.h), named: six rows, six flags, the pair count, a zero."""
+    _fields_ = [("row", FaceRow * SLOTS), ("valid", C.c_int32 * SLOTS), ("n_pairs", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(FaceRow) == 40 and C.sizeof(FaceSlots) == 4 * FACE_TABLE_INTS
+
+
+def slots(bboxes, n_images: int):
+    """-> (n faces, [6 x MasFaceRow or None]): surviving row q < half in slot q, row half + q in slot 3 + q (half = rows // 2 <= 3), so
+    pair q is always (slot q, slot 3 + q) and every rec row sits in slots 3..5:  n = 1: gt0 | rec0;  n = 4: gt0 gt1 gt2 | gt3 rec0 rec1;
+    n >= 6: gt only.  The pairing is ``plan``'s (the reference's), a box without area raises as there."""
+    n, rows = plan(bboxes, n_images)
+    half = len(rows) // 2
+    out = [None] * SLOTS
+    for q in range(half):
+        out[q], out[PAIRS + q] = rows[q], rows[half + q]
+    return n, out
+
+
+def check_slots(records, n_images: int):
+    """the library's ``check_rows`` conditions on every filled slot, and 0 <= b < n_images; raises ValueError"""
+    if len(records) != SLOTS:
+        raise ValueError(f"FaceLoss: a face table has {SLOTS} slots, got {len(records)} records")
+    for s, r in enumerate(records):
+        if r is None:
+            continue
+        if (r.h <= 0 or r.w <= 0 or r.rh < FACE or r.rw < FACE or r.ct < 0 or r.cl < 0 or r.ct + FACE > r.rh or r.cl + FACE > r.rw
+                or r.src not in (0, 1)):
+            raise ValueError(f"FaceLoss: slot {s} has an invalid geometry")
+        if not 0 <= r.b < n_images:
+            raise ValueError(f"FaceLoss: slot {s} names image {r.b} of a batch of {n_images}")
+    if any((records[q] is None) != (records[PAIRS + q] is None) for q in range(PAIRS)) or \
+            any(records[q] is None and records[q + 1] is not None for q in range(PAIRS - 1)):
+        raise ValueError("FaceLoss: the filled slots must be the pairs (q, 3 + q) for q < n_pairs")
+
+
+def pack_slots(records, n_images: int) -> FaceSlots:
+    """the table (``FaceSlots``) of six slot records (checked first); an empty slot is all zeros"""
+    check_slots(records, n_images)
+    t = FaceSlots()
+    for s, r in enumerate(records):
+        if r is not None:
+            t.row[s], t.valid[s] = r, 1
+    t.n_pairs = sum(r is not None for r in records[:PAIRS])
+    return t
+
+
+class FaceTable:
+    """One table of six face slots (``FaceSlots``: MAS_FACE_TABLE_INTS int32) on ``device`` that the host rewrites before every call of the static node (``_FaceLossStatic``) -- the only
+    thing about a batch's faces that reaches the device, so a captured graph that reads the table follows the boxes of each replay.
+
+    ``write`` fills a pinned host buffer and issues one asynchronous copy on the current stream; it reads nothing back.  TWO pinned
+    buffers alternate, each with an event recorded behind its copy: a buffer is rewritten only after the copy issued from it two
+    writes ago has completed (``event.synchronize()``: a wait on that one small copy, which has almost always finished long before).
+    On a CPU ``device`` the table is a plain buffer (the packing can be looked at without a GPU)."""
+    NBYTES = C.sizeof(FaceSlots)
+
+    def __init__(self, device):
+        self.dev = torch.zeros(self.NBYTES, dtype=torch.uint8, device=device)                 # all slots empty
+        self.device = self.dev.device
+        self._host = [torch.zeros(self.NBYTES, dtype=torch.uint8, pin_memory=self.device.type == "cuda") for _ in range(2)]
+        self._events = [None, None]                         # behind the last copy issued from each pinned buffer
+        self._turn = 0
+        self.n_faces, self.n_images = 0, 0
+
+    def write(self, bboxes, n_images: int) -> int:
+        """plans and checks the boxes on the host (a ValueError leaves the table as it was), then overwrites the device table; -> n faces"""
+        n, records = slots(bboxes if bboxes is not None else [], n_images)
+        raw = bytes(pack_slots(records, n_images))
+        k = self._turn
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        self._host[k].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+        self.dev.copy_(self._host[k], non_blocking=True)
+        if self.device.type == "cuda":
+            if self._events[k] is None:
+                self._events[k] = torch.cuda.Event()
+            self._events[k].record()
+        self._turn = 1 - k
+        self.n_faces, self.n_images = n, int(n_images)
+        return n
+
+    def data_ptr(self):
+        return self.dev.data_ptr()
 
 
 def _rows_array(rows):
@@ -287,6 +386,27 @@ def l1_forward(feats, half):
     return out
 
 
+def _network_backward(mod, ss, offs, feats, saved, idx, w0, seeds, row0, nb):
+    """the data gradient of the network for rows [row0, row0 + nb) of the saved maps, from the five seeds of those rows: the Bottlenecks
+    in reverse, pool, stem -> d faces [nb, 254, 254, 3] fp32"""
+    blocks = blocks_of(mod)
+    d = None
+    for k in range(len(blocks) - 1, -1, -1):
+        li, blk = blocks[k]
+        shape_in, a1, a2, out = saved[k]
+        last = blk is getattr(mod, f"layer{li}")[-1]
+        d = _block_bwd(blk, shape_in, d, seeds[li] if last else None, out[row0:row0 + nb], a1[row0:row0 + nb], a2[row0:row0 + nb], ss, offs)
+    y0 = feats[0][row0:row0 + nb]
+    dy0 = torch.empty_like(y0)
+    idx = idx[row0 * 63 * 63 * 64:]
+    dt = _DT[y0.dtype]
+    check(lib().mas_face_pool_bwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(d), _p(idx), _p(seeds[0]), _p(dy0), dt, nb, 127, 127, 64, _stream()),
+          "face_pool_bwd")
+    dfaces = torch.empty((nb, FACE, FACE, 3), dtype=torch.float32, device=y0.device)
+    check(lib().mas_face_stem_dgrad(_p(dy0), _p(w0), _p(dfaces), dt, nb, _stream()), "face_stem_dgrad")
+    return dfaces
+
+
 class _FaceLoss(torch.autograd.Function):
     """img, rec -> [d_0 .. d_4, loss]: crop, stem, bn1 + ReLU + pool, 16 Bottlenecks, L1 -- ~105 launches.  Backward: the seeds of
     the five L1 terms for the rec rows, the Bottlenecks in reverse (join, conv3^T, ReLU-BN, conv2^T, ReLU-BN, [downsample^T],
@@ -320,23 +440,68 @@ class _FaceLoss(torch.autograd.Function):
         f = _feats_table(feats, ctx.half)
         sp = (C.c_void_p * 5)(*[s.data_ptr() for s in seeds])
         check(lib().mas_face_l1_bwd(C.byref(f), row0, nb, _p(dl6), sp, _stream()), "face_l1_bwd")
-        blocks = blocks_of(mod)
-        d = None
-        for k in range(len(blocks) - 1, -1, -1):
-            li, blk = blocks[k]
-            shape_in, a1, a2, out = ctx.saved[k]
-            last = blk is getattr(mod, f"layer{li}")[-1]
-            d = _block_bwd(blk, shape_in, d, seeds[li] if last else None, out[row0:], a1[row0:], a2[row0:], ss, offs)
-        y0 = feats[0][row0:]
-        dy0 = torch.empty_like(y0)
-        idx = ctx.idx[row0 * 63 * 63 * 64:]
-        dt = _DT[y0.dtype]
-        check(lib().mas_face_pool_bwd(_p(y0), _ssp(ss, offs, mod.bn1), _p(d), _p(idx), _p(seeds[0]), _p(dy0), dt, nb, 127, 127, 64, _stream()),
-              "face_pool_bwd")
-        dfaces = torch.empty((nb, FACE, FACE, 3), dtype=torch.float32, device=y0.device)
-        check(lib().mas_face_stem_dgrad(_p(dy0), _p(ctx.w0), _p(dfaces), dt, nb, _stream()), "face_stem_dgrad")
+        dfaces = _network_backward(mod, ss, offs, feats, ctx.saved, ctx.idx, ctx.w0, seeds, row0, nb)
         drec = crop_faces_bwd(dfaces, ctx.rows[row0:], rec)
         return None, drec, None, None, None, None
+
+
+class _FaceLossStatic(torch.autograd.Function):
+    """``_FaceLoss`` at fixed capacity: the rows come from a ``FaceTable``, the network always runs on six rows and its backward on
+    the slice [3:6] (every rec row sits there), so the launches, their arguments and every shape are the same whatever the table holds
+    -- nothing is read on the host, and a captured graph of this node follows the table of each replay.  Empty slots are zero crops;
+    the L1 sums add exactly 0 for them and their seeds are zeros, so their rows carry zeros through the backward and the crop adjoint
+    skips them.  A table without faces gives a loss of exactly 0 and d rec of exact zeros."""
+
+    @staticmethod
+    def forward(ctx, img, rec, mod, table, dtype):
+        tp = C.c_void_p(table.data_ptr())
+        faces = torch.empty((SLOTS, 3, FACE, FACE), dtype=dtype, device=img.device, memory_format=torch.channels_last)
+        gi, gr = _image(img, "FaceLoss"), _image(rec, "FaceLoss")
+        check(lib().mas_face_crop_fwd_dev(C.byref(gi), C.byref(gr), tp, C.c_void_p(faces.data_ptr()), _DT[dtype], _stream()), "face_crop_fwd_dev")
+        ss, offs = fold_bn(mod)
+        feats, (w0, idx, saved) = network_forward(mod, faces, ss, offs)
+        f = _feats_table(feats, PAIRS)
+        nws = lib().mas_face_l1_workspace(C.byref(f))
+        if nws < 0:
+            check(nws, "face_l1_workspace")
+        ws = torch.empty(max(nws, 1), dtype=torch.float32, device=img.device)
+        out = torch.empty(6, dtype=torch.float32, device=img.device)
+        check(lib().mas_face_l1_fwd_dev(C.byref(f), tp, _p(ws), _p(out), _stream()), "face_l1_fwd_dev")
+        ctx.mod, ctx.table = mod, table
+        ctx.idx, ctx.ss, ctx.offs, ctx.w0, ctx.feats, ctx.saved = idx, ss, offs, w0, feats, saved
+        ctx.save_for_backward(rec)
+        return out
+
+    @staticmethod
+    def backward(ctx, dl6):
+        (rec,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        mod, ss, offs, feats = ctx.mod, ctx.ss, ctx.offs, ctx.feats
+        tp = C.c_void_p(ctx.table.data_ptr())
+        row0, nb = PAIRS, PAIRS
+        dl6 = dl6.float().contiguous()
+        seeds = [torch.empty((nb,) + tuple(f.shape[1:]), dtype=f.dtype, device=f.device, memory_format=torch.channels_last) for f in feats]
+        f = _feats_table(feats, PAIRS)
+        sp = (C.c_void_p * 5)(*[s.data_ptr() for s in seeds])
+        check(lib().mas_face_l1_bwd_dev(C.byref(f), tp, _p(dl6), sp, _stream()), "face_l1_bwd_dev")
+        dfaces = _network_backward(mod, ss, offs, feats, ctx.saved, ctx.idx, ctx.w0, seeds, row0, nb)
+        drec = torch.empty_like(rec)
+        g = _image(drec, "FaceLoss")
+        check(lib().mas_face_crop_bwd_dev(C.c_void_p(dfaces.data_ptr()), tp, C.byref(g), _stream()), "face_crop_bwd_dev")
+        return None, drec, None, None, None
+
+
+def face_loss_static(mod, img, rec, table, dtype=None):
+    """The evaluation-mode FaceLoss on a ``FaceTable``: -> [6] fp32 as ``face_loss``, ALWAYS (the node runs whatever the table holds;
+    whether a batch has faces at all is the caller's to decide from ``table.write``'s return value)."""
+    _require_cuda(img, "FaceLoss")
+    _require_cuda(rec, "FaceLoss")
+    if table.device != img.device:
+        raise RuntimeError(f"FaceLoss: the face table is on {table.device}, the images on {img.device}")
+    if table.n_images > min(img.shape[0], rec.shape[0]):
+        raise ValueError(f"FaceLoss: the face table was written for {table.n_images} images, the batch has {min(img.shape[0], rec.shape[0])}")
+    return _FaceLossStatic.apply(img, rec, mod, table, dtype or ops.compute_dtype())
 
 
 def face_loss(mod, img, rec, bbox, dtype=None):

@@ -246,6 +246,17 @@ class GraphedTrainStep:
                 cb.tick()
         return self.calls % self.accumulate == 0            # a closing call: the optimizer steps
 
+    def _keys(self):
+        """the graphs of one phase, in capture order (what ``_step`` is handed): the closing step alone, or the micro-step and the closing step"""
+        return (True,) if self.accumulate == 1 else (False, True)
+
+    def _key(self, closing):
+        """the graph this call replays"""
+        return closing
+
+    def _settle_for_capture(self):
+        """eager work that a capture needs done first (on the side stream, just before the graphs are taken); changes no value"""
+
     def _step(self, closing):
         """one call: with accumulate == 1 the step of ``_train_step``; else forward and backward ADDING into the gradients that are there,
         and on a closing call ``optimizer.step()`` and the gradients zeroed in place (they stay where the captured kernels write)"""
@@ -274,7 +285,7 @@ class GraphedTrainStep:
             for _ in range(warmup):
                 closing = self._tick()
                 with self._autocast():
-                    self._step(closing)
+                    self._step(self._key(closing))
         main.wait_stream(self._side)
 
     def _capture_phase(self):
@@ -291,8 +302,9 @@ class GraphedTrainStep:
             if k == 1:
                 for opt in opts:
                     opt.zero_grad(set_to_none=True)
-            pool = None                                     # the closing step's graph shares the micro-step's memory pool
-            for closing in ((True,) if k == 1 else (False, True)):
+            self._settle_for_capture()
+            pool = None                                     # the phase's graphs share the first one's memory pool
+            for key in self._keys():
                 for attempt in range(2):
                     for opt in opts:
                         opt.init_state()
@@ -300,7 +312,7 @@ class GraphedTrainStep:
                     without = [p for p in params if p.requires_grad and p.grad is None] if k > 1 else []
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph, pool=pool, stream=self._side), self._autocast():
-                        loss = self._step(closing)
+                        loss = self._step(key)
                     self._cb_rows = [cb._dev.get("last_n", 0) if cb.training and cb.phase() >= 1 else 0 for cb in self.codebooks]
                     for cb, c in zip(self.codebooks, rows):  # the capture's forward counted rows that no kernel collected
                         cb._dev["c"] = c
@@ -315,7 +327,7 @@ class GraphedTrainStep:
                     del graph, loss
                     for p in fresh:
                         p.grad = torch.zeros_like(p)
-                self._graphs[closing] = (graph, self._detached(loss))
+                self._graphs[key] = (graph, self._detached(loss))
                 pool = graph.pool()
                 self.captures += 1
         main.wait_stream(self._side)
@@ -335,7 +347,7 @@ class GraphedTrainStep:
         for s, x in zip(self._static, inputs):
             if x is not s:
                 s.copy_(x, non_blocking=True)
-        graph, loss = self._graphs[closing]
+        graph, loss = self._graphs[self._key(closing)]
         graph.replay()
         for cb, n in zip(self.codebooks, self._cb_rows):
             if n:
@@ -391,12 +403,18 @@ class GraphedGanStep(GraphedTrainStep):
       ``step.set_global_step(n)`` writes it (a resumed run).  Calls made at construction (``warmup``) count.
     * the signature holds both optimizers' ``state_generation``, hyperparameters and clip / EMA / guard settings, ``training`` of every
       module of ``model`` and ``loss``, and the codebook phase; ``sync_hyperparameters()`` of both runs before each replay.
-    * refused at construction: an optimizer without ``device_step``, a codebook without its device reservoir, a ``reducer``, and a
-      ``face_loss`` / ``object_loss`` on the loss (their crops are cut from host box lists).  The perceptual term may be LPIPS with its
-      HIP path on or off, any capturable callable, or ``None``."""
+    * the face term: a ``loss.face_loss`` that is a ``losses.face_loss.FaceLoss`` in evaluation mode is captured.  ``step(images,
+      bbox_face)`` takes one list of boxes per image (``None``: no faces), plans them on the host and writes them into the step's
+      ``mas_hip.face.FaceTable`` (``step.face_table``: ~300 bytes, one asynchronous copy, nothing read back), which the captured
+      fixed-capacity node reads.  Every phase then has its graphs TWICE, keyed ``(closing, faces)``: without the term (a call without
+      faces replays exactly what a step with ``face_loss=None`` replays) and with it; both are captured together and share the phase's
+      pool, so batches with and without faces alternate without a capture.  ``example_bbox_face``: the boxes of the warm-up calls.
+    * refused at construction: an optimizer without ``device_step``, a codebook without its device reservoir, a ``reducer``, an
+      ``object_loss`` on the loss, and any other ``face_loss`` (a callable, a ``FaceLoss`` in ``train()`` mode): their crops are cut
+      from host box lists.  The perceptual term may be LPIPS with its HIP path on or off, any capturable callable, or ``None``."""
 
     def __init__(self, model, loss, gen_optimizer, disc_optimizer, example_images, *, amp_dtype=None, accumulate=1, global_step=0, warmup=1,
-                 reducer=None):
+                 reducer=None, example_bbox_face=None):
         if isinstance(accumulate, bool) or not isinstance(accumulate, int):
             raise TypeError(f"GraphedGanStep: accumulate must be an integer (calls per optimizer step), got {accumulate!r}")
         if accumulate < 1:
@@ -410,7 +428,7 @@ class GraphedGanStep(GraphedTrainStep):
                                 f"count, bias corrections and learning rate live on the device), got {type(opt).__name__}"
                                 + ("" if not isinstance(opt, optim.Adam) else " with device_step=False"))
         for name in ("face_loss", "object_loss"):
-            if getattr(loss, name, None) is not None:
+            if getattr(loss, name, None) is not None and not (name == "face_loss" and self._capturable_face(loss.face_loss)):
                 raise NotImplementedError(f"GraphedGanStep: the loss has a {name}, whose crops are cut from host box lists that a capture "
                                           f"cannot hold; build the loss with {name}=None, or train eagerly")
         if not hasattr(loss, "hip_tail") or not hasattr(loss, "discriminator"):
@@ -436,7 +454,43 @@ class GraphedGanStep(GraphedTrainStep):
         self._side = torch.cuda.Stream(device=example_images.device)
         self._static = [example_images.detach().clone()]
         self.global_step = torch.full((), int(global_step), dtype=torch.int64, device=example_images.device)
+        self.face_table, self._faces = None, False
+        if getattr(loss, "face_loss", None) is not None:
+            from . import face
+            self.face_table = face.FaceTable(example_images.device)
+        self._write_faces(example_bbox_face, example_images.shape[0])
         self._warm_up(int(warmup))
+
+    @staticmethod
+    def _capturable_face(term):
+        """a ``losses.face_loss.FaceLoss`` in evaluation mode: the one face term whose rows a device table can carry"""
+        try:                                                  # (the loss stack imports this package, not the other way round)
+            from losses.face_loss import FaceLoss
+        except ImportError:
+            return False
+        return isinstance(term, FaceLoss) and not term.training
+
+    def _write_faces(self, bbox_face, n_images):
+        """the call's boxes into the table (host planning and checks, one asynchronous copy); sets which variant the call takes.
+        Without a face term the boxes are ignored, as the loss ignores them."""
+        self._faces = self.face_table is not None and self.face_table.write(bbox_face, n_images) > 0
+
+    def _keys(self):
+        variants = (False, True) if self.face_table is not None else (False,)
+        return tuple((closing, faces) for closing in super()._keys() for faces in variants)
+
+    def _key(self, closing):
+        return (closing, self._faces)
+
+    def _settle_for_capture(self):
+        """the face term alone, once, eagerly, on whatever the table holds: its weights' packed images, the BatchNorm address table and
+        the convolutions' choices exist before a capture meets them (the term is frozen: no value moves)"""
+        if self.face_table is None:
+            return
+        x = self._static[0]
+        rec = x.detach().clone().requires_grad_(True)
+        with self._autocast():
+            self.loss_module.face_loss(x, rec, self.face_table).backward()
 
     def set_global_step(self, n):
         """writes the device counter (a resume); no capture depends on its value"""
@@ -446,7 +500,8 @@ class GraphedGanStep(GraphedTrainStep):
     def _detached(out):
         return GanStepOut(*(t.detach() for t in out))
 
-    def _step(self, closing):
+    def _step(self, key):
+        closing, faces = key
         model, crit, images = self.model, self.loss_module, self._static[0]
         if self.accumulate == 1:
             for opt in self._opts:
@@ -461,7 +516,8 @@ class GraphedGanStep(GraphedTrainStep):
                 for p in disc:
                     p.requires_grad_(False)
                 crit.advance_global_step = True
-                loss, (nll_loss, _, _) = crit(0, self.global_step, images, rec, q_loss, last_layer=model.decoder.model[-1])
+                loss, (nll_loss, _, _) = crit(0, self.global_step, images, rec, q_loss, bbox_face=self.face_table if faces else None,
+                                              last_layer=model.decoder.model[-1])
                 loss.backward()
             finally:
                 crit.advance_global_step = advance
@@ -477,6 +533,7 @@ class GraphedGanStep(GraphedTrainStep):
                     torch._foreach_zero_(grads)
         return GanStepOut(loss, d_loss, nll_loss, terms["g_loss"], terms["d_weight"])
 
-    def __call__(self, images):
+    def __call__(self, images, bbox_face=None):
         self._check_inputs((images,))
+        self._write_faces(bbox_face, images.shape[0])         # (before the tick: a box that is refused leaves the counters alone)
         return self._call_phased((images,))

@@ -15,8 +15,19 @@ call: the device activities torch.profiler records for one closing call (kernels
 
 Then the tail alone, switch off against on, in the same process: the loss's two halves (discriminator passes included, no perceptual
 term) on a reconstruction that is one 128 -> 3 convolution of a fixed map, forward and backward; device time (the sum of the profiler's
-device activities) and their count per call, and the difference of the two columns, which is the tail's."""
-import argparse, os, sys, time
+device activities) and their count per call, and the difference of the two columns, which is the tail's.
+
+``--faces`` measures the face term inside the step INSTEAD: a synthetic-weight ``FaceLoss`` (tests/helpers/face_ref.py) on the loss, k faces
+per call with k = 0, 1, 2 alternating as a data set would, in four columns that alternate block by block in one process:
+
+  eager, lists             the step as it runs without this class: ATen tail, host-step Adams, the boxes as lists
+  graphed, table           GraphedGanStep(images, bbox_face): the boxes through the step's FaceTable, the two variants per phase
+  graphed, no faces        the same step called without boxes: the variant without the term, every call
+  graphed, face_loss=None  the step as it was before the face term could be captured
+
+then the face node alone, forward + backward at the batch's images: the list node against the fixed-capacity node at n = 1 and n = 3 faces
+(2n rows forward and n backward against 6 and 3)."""
+import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "make-a-scene_amd"))
 os.environ.setdefault("MAS_LPIPS_STRICT", "0")          # LPIPS keeps its initialisation: timing does not depend on the weights' values
@@ -30,6 +41,7 @@ from models.modules import Conv2d
 ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=2.0, help="wall time one timed block should fill")
 ap.add_argument("--configs", default="2:8,32:1", help="batch:accumulate pairs")
+ap.add_argument("--faces", action="store_true", help="measure the face term inside the step (see above) instead of the three forms")
 a = ap.parse_args()
 
 IMG_CFG = dict(ddconfig=dict(z_channels=256, in_channels=3, out_channels=3, channels=[128, 128, 128, 256, 512, 512], num_res_blocks=2,
@@ -53,7 +65,7 @@ def device_activities(fn):
         return None
 
 
-def gan_call(model, crit, gopt, dopt, x, step, closing, last_layer=None, rec_fn=None):
+def gan_call(model, crit, gopt, dopt, x, step, closing, last_layer=None, rec_fn=None, bbox_face=None):
     rec, q = model(x) if rec_fn is None else rec_fn()
     d_loss = crit(1, step, x, rec)
     d_loss.backward()
@@ -61,7 +73,7 @@ def gan_call(model, crit, gopt, dopt, x, step, closing, last_layer=None, rec_fn=
     for p in disc:
         p.requires_grad_(False)
     try:
-        loss, _ = crit(0, step, x, rec, q, last_layer=last_layer if last_layer is not None else model.decoder.model[-1])
+        loss, _ = crit(0, step, x, rec, q, bbox_face=bbox_face, last_layer=last_layer if last_layer is not None else model.decoder.model[-1])
         loss.backward()
     finally:
         for p in disc:
@@ -86,8 +98,104 @@ def block(fn, n, guarded=False):
     return (time.perf_counter() - t0) / n, loss
 
 
-with hip_path(True):
+def face_boxes(batch, k):
+    """k faces (0, 1 or 2) on the first images of a 256 x 256 batch: a portrait box and a landscape one"""
+    boxes = [[] for _ in range(batch)]
+    for i, box in enumerate(([40, 30, 168, 190], [96, 120, 240, 216])[:k]):
+        boxes[i % batch].append(box)
+    return boxes
+
+
+def bench_faces():
+    """--faces: the four step columns and the node alone, per configuration"""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import face_ref
+    from losses.face_loss import FaceLoss
+    from mas_hip import face as FH
+    ck = os.path.join(tempfile.mkdtemp(), "face_synth.pt")
+    torch.save(face_ref.synth_face_state_dict(0), ck)
+    os.environ["MAS_FACE_CKPT"] = ck
+    names = ("eager, lists", "graphed, table", "graphed, no faces", "graphed, face_loss=None")
     for cfg in a.configs.split(","):
+        batch, acc = (int(v) for v in cfg.split(":"))
+        x = torch.rand(batch, 3, 256, 256, generator=torch.Generator().manual_seed(0)).to(dev)
+        cycle = [face_boxes(batch, k) for k in (0, 1, 2)]
+        cols = {}
+        for name in names:
+            torch.manual_seed(1)
+            model = VQBASE(**IMG_CFG)
+            with torch.no_grad():
+                model.quantize.embedding.weight.normal_(0.0, 1.0)
+            model = model.to(dev).train()
+            model.quantize.q_counter = model.quantize.q_re_end
+            crit = VQLPIPSWithDiscriminator(disc_start=0, perceptual_loss="lpips", face_loss=None if name.endswith("None") else FaceLoss()).to(dev)
+            on = name != "eager, lists"
+            if on:
+                model.quantize.enable_device_reservoir(seed=7)
+            gopt = optim.Adam(model.parameters(), lr=5e-6 / acc, betas=(0.5, 0.9), device_step=on)
+            dopt = optim.Adam(crit.discriminator.parameters(), lr=5e-6 / acc, betas=(0.5, 0.9), device_step=on)
+            if on:
+                step = graphs.GraphedGanStep(model, crit, gopt, dopt, x, accumulate=acc, warmup=acc, global_step=0)
+                boxed = name == "graphed, table"
+
+                def call(step=step, boxed=boxed, n=[0]):
+                    n[0] += 1
+                    return step(x, cycle[n[0] % 3] if boxed else None).loss
+                for _ in range(3 * acc):
+                    call()
+                print(f"B={batch} accumulate={acc} {name}: {step.captures} capture(s)", flush=True)
+            else:
+                def call(model=model, crit=crit, gopt=gopt, dopt=dopt, n=[0]):
+                    n[0] += 1
+                    with hip_tail(False):
+                        return gan_call(model, crit, gopt, dopt, x, n[0], n[0] % acc == 0, bbox_face=cycle[n[0] % 3])
+                for _ in range(3 * acc):
+                    call()
+            cols[name] = call
+        unit = 3 * acc                                            # a block holds whole cycles of the boxes and whole optimizer steps
+        n_calls = {k: max(1, int(a.seconds / block(fn, unit, k != names[0])[0]) // unit) * unit for k, fn in cols.items()}
+        times = {k: [] for k in cols}
+        for _ in range(2):
+            for k, fn in cols.items():
+                dt, loss = block(fn, n_calls[k], k != names[0])
+                assert bool(torch.isfinite(loss)), (k, float(loss))
+                times[k].append(dt)
+        for k in cols:
+            print(f"VQ-IMG 256x256 B={batch} accumulate={acc} training call, faces 0/1/2 alternating, {k}: "
+                  + " / ".join(f"{t * 1e3:.2f}" for t in times[k]) + f" ms/call ({n_calls[k]} calls per block)", flush=True)
+        del cols, model, gopt, dopt, step, crit
+        torch.cuda.empty_cache()
+
+        # ---- the node alone: lists (2n rows forward, n backward) against the table (6 and 3) ---------------------------------------------------
+        mod = FaceLoss().to(dev)
+        rec = (x + 0.1 * torch.randn_like(x)).clamp(0, 1)
+        table = FH.FaceTable(dev)
+        three = [[[40, 30, 168, 190], [96, 120, 240, 216], [10, 10, 120, 130]]] + [[] for _ in range(batch - 1)]
+        for n, boxes in ((1, face_boxes(batch, 1)), (3, three)):
+            assert table.write(boxes, batch) == n
+            res = {}
+            for _ in range(2):
+                for k, bb in (("lists", boxes), ("table", table)):
+                    def node(bb=bb):
+                        r = rec.clone().requires_grad_(True)
+                        loss = mod(x, r, bb)
+                        loss.backward()
+                        return loss
+                    for _ in range(3):
+                        node()
+                    res.setdefault(k, []).append((device_activities(node), block(node, 30)[0]))
+            for k in ("lists", "table"):
+                print(f"face node alone B={batch} n={n}, {k}: " + " / ".join(
+                    (f"{c[0]} device activities, {c[1] / 1e3:.3f} ms on the device" if c else "device activities not measured") + f", {t * 1e3:.3f} ms wall"
+                    for c, t in res[k]), flush=True)
+        del mod, rec, table
+        torch.cuda.empty_cache()
+
+
+with hip_path(True):
+    if a.faces:
+        bench_faces()
+    for cfg in ([] if a.faces else a.configs.split(",")):
         batch, acc = (int(v) for v in cfg.split(":"))
         x = torch.rand(batch, 3, 256, 256, generator=torch.Generator().manual_seed(0)).to(dev)
         cols, counts = {}, {}

@@ -1,6 +1,6 @@
-"""``GraphedTrainStep``: a whole training step -- zero_grad, the refresh of stale weight images and bf16 shadows, forward, backward,
-``optimizer.step()`` -- captured once into ONE graph and replayed, so that a step costs the host one graph launch instead of the
-~1200 kernel launches of a stage-2 step.  Opt-in; nothing else in the package changes behaviour.
+"""``GraphedTrainStep``: a whole training call -- zero_grad, the refresh of stale weight images and bf16 shadows, forward, backward,
+``optimizer.step()`` -- captured into a graph and replayed, so that a call costs the host one graph launch instead of the ~1200 kernel
+launches of a stage-2 step.  Opt-in; nothing else in the package changes behaviour.
 
     opt  = mas_hip.optim.AdamW(model.parameters(), lr=4.5e-4, device_step=True)
     step = mas_hip.graphs.GraphedTrainStep(lambda t, s, i: model.token_loss(t, s, i), opt, (text, seg, img),
@@ -8,49 +8,42 @@
     for text, seg, img in loader:
         loss = step(text, seg, img)          # copies the inputs into the static ones, replays; the static 0-dim loss, no host read
 
-What it needs and what it does:
+One mechanism serves every step (``GraphedGanStep`` below is the VQ-IMG call on the same machinery):
 
-* the optimizer is ``mas_hip.optim.Adam`` / ``AdamW`` with ``device_step=True`` (its step count, bias corrections, learning rate and
-  EMA counter live on the device; anything else raises here).
-* CONSTRUCTION TRAINS: it runs ``warmup >= 1`` real training steps on ``example_inputs`` on a side stream (they settle the GEMM choices,
-  every workspace and the optimizer state), then captures the step there.  The capture itself executes nothing.
-* warm-up and capture run under ``torch.autocast("cuda", amp_dtype, cache_enabled=False)`` when ``amp_dtype`` is given (autocast off
-  otherwise), and with the convolution weight-gradient side stream off (``ops.wgrad_stream_off``): the graph is one stream without branches.
-* the stamps of the weight caches are made stale just before the capture, so the refresh launches are part of the graph even when the
-  caches happen to be fresh; every replay recomputes them from the weights of that moment.  The graph keeps the cached images it reads
-  alive, and after every replay the caches are told that the weights moved (what the optimizer's post-step hook does), so an eager
-  forward, ``generate()``, ``swap_ema()`` or a checkpoint between replays sees the current weights.
-* before every replay, on the host: ``optimizer.sync_hyperparameters()`` (a changed learning rate reaches the device without a new
-  capture), and a comparison of what the capture baked in -- ``optimizer.state_generation``, ``betas`` / ``eps`` / ``weight_decay``, the
-  clip / EMA / guard settings, the inputs' shapes and dtypes, the compute dtype, ``training`` of every module under ``modules=`` --
-  with what is there now.  When one differs the step is RECAPTURED lazily (no warm-up step runs then: a recapture changes no value);
-  ``step.captures`` counts captures.
-* dropout needs nothing: its ``{seed, offset}`` is drawn by ``torch.randint`` on the device, and a replay advances the generator.
-* the returned loss is the graph's static tensor: the next call overwrites it.
+* CONSTRUCTION TRAINS: ``warmup >= 1`` real training calls on ``example_inputs``, eager, on a side stream.  They settle the GEMM choices,
+  every workspace and the optimizer state, tick the codebooks and count towards ``accumulate`` (``step.calls``).
+* a CALL, on the host: the tick (``step.calls``, and ``Codebook.tick`` of every training codebook: its counter, and its
+  re-initialisation when due -- eager, BEFORE the replay; the captured forward does not tick); a comparison of the SIGNATURE -- what a
+  capture bakes in that the host can still change: every optimizer's ``state_generation``, ``betas`` / ``eps`` / ``weight_decay`` and
+  clip / EMA / guard settings, the inputs' shapes and dtypes, the compute dtype, ``training`` of every module under ``modules=``, each
+  codebook's phase -- with the one captured, and a lazy capture when they differ; ``sync_hyperparameters()`` (a changed learning rate
+  needs no capture); the copy of the inputs into the static ones; the replay.  Afterwards the codebooks are told the rows the replay
+  collected, and on a closing call the weight caches are told that the weights moved (what the optimizer's post-step hook does), so an
+  eager forward, ``generate()``, ``swap_ema()`` or a checkpoint between replays sees the current weights.
+* a CAPTURE executes nothing and runs no warm-up call (it changes no value); ``step.captures`` counts graphs.  It runs on the side
+  stream under ``torch.autocast("cuda", amp_dtype, cache_enabled=False)`` (autocast off without ``amp_dtype``) with the convolution
+  weight-gradient side stream off: one stream without branches.  The weight caches are made stale just before it, so their refresh is
+  part of the graph and every replay recomputes the images from the weights of that moment; the step keeps the images alive.
+* a PHASE is what a codebook's training forward does at its call counter: no collect and unquantised, collect and unquantised,
+  collect + lookup.  A capture holds the graphs of the phase of that moment; a phase change is a signature change: three captures over
+  a run.  ``codebooks=`` defaults to every ``Codebook`` under ``modules=``; each needs ``enable_device_reservoir()``, else this raises.
+* ``accumulate=k`` > 1: the optimizer steps on calls k, 2k, ... on the sum of the k calls' gradients (unaveraged, as the reference's
+  loop; the reference itself steps on calls 1, k+1, ...).  A phase then has two graphs that share the static inputs and one memory
+  pool: a micro-step (forward, backward ADDING into the gradients that are there) and a closing step (the same, ``optimizer.step()``,
+  the gradients zeroed in place).  The gradients are the tensors the warm-up calls left; a parameter without one keeps
+  ``.grad = None`` (AdamW does not decay it) until a capture shows that it receives one -- the embedding when the lookup begins -- and
+  then gets a persistent zero tensor, and the capture is taken again.
+* nothing is captured before the first call (``step.captures == 0``) -- except for a step that has one phase and one graph for life
+  (no codebook, ``accumulate == 1``): its capture is taken at the end of construction.
+* the optimizer is ``mas_hip.optim.Adam`` / ``AdamW`` with ``device_step=True`` (step count, bias corrections, learning rate and EMA
+  counter on the device); dropout needs nothing (its ``{seed, offset}`` is drawn on the device, a replay advances the generator); the
+  returned loss is the replayed graph's static tensor, overwritten by the next call of that graph.
 * ``nn.Embedding`` lookups of more than a few thousand indices must go through ``graphs.embedding(module, idx)`` (``MakeAScene`` does):
   ATen's backward for them reads a count on the host and faults when replayed.  Under a capture the helper sums ATen's dense backward
-  over slices of the indices, so a replayed step differs from an eager one in the order of those additions -- and not at all inside
-  ``graphs.embedding_grad_in_chunks()``.
+  over slices of the indices: the eager result up to the order of those additions, and exactly it inside ``embedding_grad_in_chunks()``.
 
-The VQ-SEG step needs two more things, both opt-in; without a codebook and with ``accumulate=1`` the code above runs as is:
-
-* ``codebooks=`` (default: every ``Codebook`` found under ``modules=``): each must have its device reservoir on
-  (``Codebook.enable_device_reservoir()``), else this raises.  A codebook's training forward has three shapes -- no collect and
-  unquantised, collect and unquantised, collect + lookup -- chosen by its call counter.  The host's half of a call (``Codebook.tick``:
-  the counter, and the re-initialisation when it is due) runs eagerly BEFORE the replay; the captured forward does not tick.  The phase
-  the call is in is part of the signature, so a phase change recaptures lazily: three captures over a run.
-* ``accumulate=k`` > 1: the optimizer steps on calls k, 2k, ... on the sum of the k calls' gradients (unaveraged, as the reference's
-  loop; the reference itself steps on calls 1, k+1, ...).  Two graphs per phase share the static inputs and one memory pool: a micro-step
-  (forward, backward ADDING into the gradients that are there) and a closing step (the same, ``optimizer.step()``, the gradients
-  zeroed in place).  The gradients are the tensors the warm-up calls left, at stable addresses; a parameter that had no gradient
-  then keeps ``.grad = None`` (AdamW does not decay it) until a capture shows that it receives one -- the embedding when the lookup
-  begins -- at which point it gets a persistent zero tensor and the capture is taken again.  The returned loss is the call's own.
-* in this mode CONSTRUCTION TRAINS TOO -- the ``warmup`` calls are real training calls, they tick the codebooks' counters and count
-  towards ``accumulate`` (``step.calls``) -- but nothing is captured before the first call (``step.captures == 0`` until then).
-
-Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collectives run on other streams; ``reducer=`` raises), steps
-with more than one optimizer or backward pass (the VQ-IMG step has its own class below, ``GraphedGanStep``), inputs that are not
-tensors, and a ``loss_fn`` that reads anything on the host."""
+Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collectives run on other streams; ``reducer=`` raises), inputs
+that are not tensors, and a ``loss_fn`` that reads anything on the host."""
 import collections
 import contextlib
 
@@ -112,23 +105,25 @@ def embedding_grad_in_chunks():
 class GraphedTrainStep:
     def __init__(self, loss_fn, optimizer, example_inputs, *, amp_dtype=None, warmup=1, modules=(), reducer=None, codebooks=None,
                  accumulate=1):
+        name = type(self).__name__
         if isinstance(accumulate, bool) or not isinstance(accumulate, int):
-            raise TypeError(f"GraphedTrainStep: accumulate must be an integer (calls per optimizer step), got {accumulate!r}")
+            raise TypeError(f"{name}: accumulate must be an integer (calls per optimizer step), got {accumulate!r}")
         if accumulate < 1:
-            raise ValueError(f"GraphedTrainStep: accumulate must be at least 1, got {accumulate}")
+            raise ValueError(f"{name}: accumulate must be at least 1, got {accumulate}")
         if reducer is not None:
-            raise NotImplementedError("GraphedTrainStep: a gradient reducer runs collectives on other streams, which one captured stream "
-                                      "cannot hold; train data-parallel runs eagerly")
-        if not isinstance(optimizer, optim.Adam) or not optimizer.device_step:
-            raise TypeError("GraphedTrainStep: the optimizer must be mas_hip.optim.Adam / AdamW with device_step=True (a step whose count, "
-                            f"bias corrections and learning rate live on the device), got {type(optimizer).__name__}"
-                            + ("" if not isinstance(optimizer, optim.Adam) else " with device_step=False"))
+            raise NotImplementedError(f"{name}: a gradient reducer runs collectives on other streams, which one captured stream cannot "
+                                      "hold; train data-parallel runs eagerly")
+        self.loss_fn, self.optimizer, self.amp_dtype = loss_fn, optimizer, amp_dtype
+        for role, opt in self._roles().items():
+            if not isinstance(opt, optim.Adam) or not opt.device_step:
+                raise TypeError(f"{name}: {role} must be mas_hip.optim.Adam / AdamW with device_step=True (a step whose count, bias "
+                                f"corrections and learning rate live on the device), got {type(opt).__name__}"
+                                + ("" if not isinstance(opt, optim.Adam) else " with device_step=False"))
         if int(warmup) < 1:
-            raise ValueError("GraphedTrainStep: warmup must be at least 1 (the capture needs every buffer and GEMM choice settled)")
+            raise ValueError(f"{name}: warmup must be at least 1 (the capture needs every buffer and GEMM choice settled)")
         if isinstance(example_inputs, torch.Tensor):
             example_inputs = (example_inputs,)
-        self.loss_fn, self.optimizer, self.amp_dtype = loss_fn, optimizer, amp_dtype
-        self._opts = [optimizer]
+        self._opts = list(self._roles().values())
         self.modules = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
         self.captures = 0
         self.graph = self.loss = self._sig = self._keep = None
@@ -140,17 +135,22 @@ class GraphedTrainStep:
         self.codebooks = [codebooks] if isinstance(codebooks, torch.nn.Module) else list(codebooks)
         for cb in self.codebooks:
             if not getattr(cb, "device_reservoir", False):
-                raise RuntimeError("GraphedTrainStep: a Codebook without its device reservoir cannot be captured (its reservoir is kept by CPU "
+                raise RuntimeError(f"{name}: a Codebook without its device reservoir cannot be captured (its reservoir is kept by CPU "
                                    "permutations and a growing tensor): call codebook.enable_device_reservoir() first")
         self.accumulate, self.calls = accumulate, 0
         self._graphs, self._cb_rows = {}, []
         self._check_inputs(example_inputs)
         self._side = torch.cuda.Stream(device=example_inputs[0].device)
         self._static = [x.detach().clone() for x in example_inputs]
-        if not self.codebooks and accumulate == 1:
-            self._capture(int(warmup))
-        else:
-            self._warm_up(int(warmup))
+        self._warm_up(int(warmup))
+        if self._captures_at_construction and not self.codebooks and accumulate == 1:
+            self._capture()                                   # one phase, one graph: taken now
+
+    _captures_at_construction = True
+
+    def _roles(self):
+        """the optimizers in the order they step, by what a message calls each"""
+        return {"the optimizer": self.optimizer}
 
     @staticmethod
     def _check_inputs(inputs):
@@ -171,37 +171,6 @@ class GraphedTrainStep:
                 tuple(m.training for mod in self.modules for m in mod.modules()),
                 tuple((cb.training, cb.phase()) for cb in self.codebooks))
 
-    def _train_step(self):
-        self.optimizer.zero_grad(set_to_none=True)
-        loss = self.loss_fn(*self._static)
-        loss.backward()
-        self.optimizer.step()
-        return loss
-
-    def _capture(self, warmup):
-        opt = self.optimizer
-        self.graph = self.loss = None                       # (a recapture: the old graph's memory goes first)
-        main = torch.cuda.current_stream(self._side.device)
-        opt.init_state()
-        self._side.wait_stream(main)
-        with contextlib.ExitStack() as stack:
-            stack.enter_context(torch.cuda.stream(self._side))
-            stack.enter_context(ops.wgrad_stream_off())
-            with self._autocast():
-                for _ in range(warmup):
-                    self._train_step()
-            opt.zero_grad(set_to_none=True)
-            opt.init_state()
-            self._stale_for_capture()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=self._side), self._autocast():
-                loss = self._train_step()
-        main.wait_stream(self._side)
-        self._settle_caches()
-        self.graph, self.loss = graph, loss.detach()
-        self._sig = self._signature(self._static)
-        self.captures += 1
-
     def _stale_for_capture(self):
         """Every derived copy of a parameter is made stale, so that its refresh gets captured.  The refresh of the packed convolution
         weights reads an item table that is uploaded from pageable memory when the set of stale images is new, which a capture cannot
@@ -210,34 +179,17 @@ class GraphedTrainStep:
         for _ in range(2):
             for opt in self._opts:
                 ops._note_optimizer_step(opt)
-            ops._pack_cache._refresh_stale(self._side.device)
+            ops.refresh_stale_weight_images(self._side.device)
         for opt in self._opts:
             ops._note_optimizer_step(opt)
 
-    def _settle_caches(self):
-        # the images the graph reads: kept alive here (invalidate_weight_cache() / swap_ema() drop the caches' own references)
-        self._keep = [e[2] for e in ops._bf16_shadows.params.values()] + [e[2] for e in ops._pack_cache.store.values()] + \
-                     [e[2] for e in ops._pack_cache.derived.values()] + [t[1] for t in ops._pack_cache._tables.values()]
-        # nothing ran, but the caches stamped as fresh whatever they "refreshed" inside the capture (this model's images and any other stale
-        # one in the process): none of those stamps describes a refresh that happened
-        for e in ops._bf16_shadows.params.values():
-            e[1] = None
-        for e in ops._pack_cache.store.values():
-            e[1] = None
-        ops._pack_cache.derived.clear()
-
-    # ---- codebook phases and gradient accumulation (codebooks under modules=, or accumulate > 1) -----------------------------------------
     @contextlib.contextmanager
-    def _ticked(self):
-        """inside, the codebooks' forward leaves the host-side tick (call counter, re-initialisation) to ``_tick``"""
-        old = [cb._ticked_outside for cb in self.codebooks]
-        for cb in self.codebooks:
-            cb._ticked_outside = True
-        try:
+    def _codebooks_in(self, mode):
+        """every codebook inside its context ``mode``: ``ticked_by_caller`` (the forward leaves the tick to ``_tick``), ``dry_forward``"""
+        with contextlib.ExitStack() as stack:
+            for cb in self.codebooks:
+                stack.enter_context(getattr(cb, mode)())
             yield
-        finally:
-            for cb, o in zip(self.codebooks, old):
-                cb._ticked_outside = o
 
     def _tick(self):
         self.calls += 1
@@ -257,18 +209,23 @@ class GraphedTrainStep:
     def _settle_for_capture(self):
         """eager work that a capture needs done first (on the side stream, just before the graphs are taken); changes no value"""
 
+    def _zero_grads_in_place(self):
+        """after a closing step under accumulate > 1: the gradients stay where the captured kernels add into them"""
+        grads = [p.grad for opt in self._opts for g in opt.param_groups for p in g["params"] if p.grad is not None]
+        if grads:
+            torch._foreach_zero_(grads)
+
     def _step(self, closing):
-        """one call: with accumulate == 1 the step of ``_train_step``; else forward and backward ADDING into the gradients that are there,
-        and on a closing call ``optimizer.step()`` and the gradients zeroed in place (they stay where the captured kernels write)"""
+        """one call.  accumulate == 1: zero_grad, forward, backward, ``optimizer.step()``; else forward and backward ADDING into the
+        gradients that are there, and on a closing call ``optimizer.step()`` and the gradients zeroed in place"""
         if self.accumulate == 1:
-            return self._train_step()
+            self.optimizer.zero_grad(set_to_none=True)
         loss = self.loss_fn(*self._static)
         loss.backward()
         if closing:
             self.optimizer.step()
-            grads = [p.grad for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
-            if grads:
-                torch._foreach_zero_(grads)
+            if self.accumulate > 1:
+                self._zero_grads_in_place()
         return loss
 
     @staticmethod
@@ -276,19 +233,19 @@ class GraphedTrainStep:
         return loss.detach()
 
     def _warm_up(self, warmup):
-        """``warmup`` real training calls, eager, under the conditions of the capture; nothing is captured before the first call"""
+        """``warmup`` real training calls, eager, under the conditions of the capture"""
         main = torch.cuda.current_stream(self._side.device)
         for opt in self._opts:
             opt.init_state()
         self._side.wait_stream(main)
-        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._ticked():
+        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._codebooks_in("ticked_by_caller"):
             for _ in range(warmup):
                 closing = self._tick()
                 with self._autocast():
                     self._step(self._key(closing))
         main.wait_stream(self._side)
 
-    def _capture_phase(self):
+    def _capture(self):
         """the graphs of the phase the codebooks are in now: one step when accumulate == 1, else a micro-step and a closing step that share
         the static inputs and one memory pool.  Executes nothing."""
         opts, k = self._opts, self.accumulate
@@ -296,9 +253,8 @@ class GraphedTrainStep:
         self._graphs = {}                                   # (the old phase's graphs and their memory go first)
         main = torch.cuda.current_stream(self._side.device)
         params = [p for opt in opts for g in opt.param_groups for p in g["params"]]
-        rows = [cb._dev["c"] for cb in self.codebooks]
         self._side.wait_stream(main)
-        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._ticked():
+        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._codebooks_in("ticked_by_caller"):
             if k == 1:
                 for opt in opts:
                     opt.zero_grad(set_to_none=True)
@@ -311,70 +267,55 @@ class GraphedTrainStep:
                     self._stale_for_capture()
                     without = [p for p in params if p.requires_grad and p.grad is None] if k > 1 else []
                     graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, pool=pool, stream=self._side), self._autocast():
+                    with self._codebooks_in("dry_forward"), torch.cuda.graph(graph, pool=pool, stream=self._side), self._autocast():
                         loss = self._step(key)
-                    self._cb_rows = [cb._dev.get("last_n", 0) if cb.training and cb.phase() >= 1 else 0 for cb in self.codebooks]
-                    for cb, c in zip(self.codebooks, rows):  # the capture's forward counted rows that no kernel collected
-                        cb._dev["c"] = c
-                        cb.reservoir = cb._dev["buf"][:c]
+                    self._cb_rows = [cb.rows_per_call() for cb in self.codebooks]
                     fresh = [p for p in without if p.grad is not None]
                     if not fresh:
                         break
                     # autograd installed a tensor of the graph's pool as these gradients (the embedding at the start of the lookup phase):
                     # they become persistent zeros that the capture, taken again, adds into
                     if attempt:
-                        raise RuntimeError("GraphedTrainStep: gradients appeared at the second capture that the first one did not produce")
+                        raise RuntimeError(f"{type(self).__name__}: gradients appeared at the second capture that the first one did not produce")
                     del graph, loss
                     for p in fresh:
                         p.grad = torch.zeros_like(p)
-                self._graphs[key] = (graph, self._detached(loss))
+                self.graph, self.loss = self._graphs[key] = (graph, self._detached(loss))
                 pool = graph.pool()
                 self.captures += 1
         main.wait_stream(self._side)
-        self._settle_caches()
+        # the images the graphs read are kept alive here (invalidate_weight_cache() / swap_ema() drop the caches' own references); and
+        # nothing ran, so none of the stamps the caches wrote inside the capture describes a refresh that happened
+        self._keep = ops.weight_cache_tensors()
+        ops.forget_capture_stamps()
         self._sig = self._signature(self._static)
 
-    def _call_phased(self, inputs):
+    def _replay(self, inputs):
         closing = self._tick()                              # eager, before the replay: the counter, and a due re-initialisation
         if self._signature(inputs) != self._sig:
             if len(inputs) != len(self._static) or any(x.shape != s.shape or x.dtype != s.dtype or x.device != s.device
                                                        for x, s in zip(inputs, self._static)):
                 self._graphs = {}
                 self._static = [x.detach().clone() for x in inputs]
-            self._capture_phase()
+            self._capture()
         for opt in self._opts:
             opt.sync_hyperparameters()
         for s, x in zip(self._static, inputs):
             if x is not s:
                 s.copy_(x, non_blocking=True)
-        graph, loss = self._graphs[self._key(closing)]
-        graph.replay()
+        self.graph, self.loss = self._graphs[self._key(closing)]
+        self.graph.replay()
         for cb, n in zip(self.codebooks, self._cb_rows):
             if n:
-                cb._note_collected(n)
+                cb.replay_collected(n)
         if closing:
             for opt in self._opts:
                 ops._note_optimizer_step(opt)
-        self.loss = loss
-        return loss
+        return self.loss
 
     def __call__(self, *inputs):
         self._check_inputs(inputs)
-        if self.codebooks or self.accumulate > 1:
-            return self._call_phased(inputs)
-        if self._signature(inputs) != self._sig:
-            if len(inputs) != len(self._static) or any(x.shape != s.shape or x.dtype != s.dtype or x.device != s.device
-                                                       for x, s in zip(inputs, self._static)):
-                self.graph = self.loss = None
-                self._static = [x.detach().clone() for x in inputs]
-            self._capture(0)
-        self.optimizer.sync_hyperparameters()
-        for s, x in zip(self._static, inputs):
-            if x is not s:
-                s.copy_(x, non_blocking=True)
-        self.graph.replay()
-        ops._note_optimizer_step(self.optimizer)
-        return self.loss
+        return self._replay(inputs)
 
 
 class GanStepOut(collections.namedtuple("GanStepOut", "loss d_loss nll_loss g_loss d_weight")):
@@ -415,51 +356,30 @@ class GraphedGanStep(GraphedTrainStep):
 
     def __init__(self, model, loss, gen_optimizer, disc_optimizer, example_images, *, amp_dtype=None, accumulate=1, global_step=0, warmup=1,
                  reducer=None, example_bbox_face=None):
-        if isinstance(accumulate, bool) or not isinstance(accumulate, int):
-            raise TypeError(f"GraphedGanStep: accumulate must be an integer (calls per optimizer step), got {accumulate!r}")
-        if accumulate < 1:
-            raise ValueError(f"GraphedGanStep: accumulate must be at least 1, got {accumulate}")
-        if reducer is not None:
-            raise NotImplementedError("GraphedGanStep: a gradient reducer runs collectives on other streams, which one captured stream cannot "
-                                      "hold; train data-parallel runs eagerly")
-        for name, opt in (("generator", gen_optimizer), ("discriminator", disc_optimizer)):
-            if not isinstance(opt, optim.Adam) or not opt.device_step:
-                raise TypeError(f"GraphedGanStep: the {name}'s optimizer must be mas_hip.optim.Adam / AdamW with device_step=True (a step whose "
-                                f"count, bias corrections and learning rate live on the device), got {type(opt).__name__}"
-                                + ("" if not isinstance(opt, optim.Adam) else " with device_step=False"))
-        for name in ("face_loss", "object_loss"):
-            if getattr(loss, name, None) is not None and not (name == "face_loss" and self._capturable_face(loss.face_loss)):
-                raise NotImplementedError(f"GraphedGanStep: the loss has a {name}, whose crops are cut from host box lists that a capture "
-                                          f"cannot hold; build the loss with {name}=None, or train eagerly")
+        name = type(self).__name__
+        for term in ("face_loss", "object_loss"):
+            if getattr(loss, term, None) is not None and not (term == "face_loss" and self._capturable_face(loss.face_loss)):
+                raise NotImplementedError(f"{name}: the loss has a {term}, whose crops are cut from host box lists that a capture "
+                                          f"cannot hold; build the loss with {term}=None, or train eagerly")
         if not hasattr(loss, "hip_tail") or not hasattr(loss, "discriminator"):
-            raise TypeError(f"GraphedGanStep: the loss must be a losses.loss_img.VQLPIPSWithDiscriminator, got {type(loss).__name__}")
-        if int(warmup) < 1:
-            raise ValueError("GraphedGanStep: warmup must be at least 1 (the capture needs every buffer and GEMM choice settled)")
+            raise TypeError(f"{name}: the loss must be a losses.loss_img.VQLPIPSWithDiscriminator, got {type(loss).__name__}")
         self._check_inputs((example_images,))
-        self.model, self.loss_module, self.amp_dtype = model, loss, amp_dtype
+        # what the warm-up calls at the end of the base constructor need: they are calls like any other
+        self.model, self.loss_module = model, loss
         self.gen_optimizer, self.disc_optimizer = gen_optimizer, disc_optimizer
-        self.optimizer, self._opts = gen_optimizer, [disc_optimizer, gen_optimizer]
-        self.modules = [model, loss]
-        self.captures = 0
-        self.graph = self.loss = self._sig = self._keep = None
-        self.codebooks = []
-        for mod in self.modules:
-            self.codebooks += [m for m in mod.modules() if hasattr(m, "enable_device_reservoir") and not any(m is s for s in self.codebooks)]
-        for cb in self.codebooks:
-            if not getattr(cb, "device_reservoir", False):
-                raise RuntimeError("GraphedGanStep: a Codebook without its device reservoir cannot be captured (its reservoir is kept by CPU "
-                                   "permutations and a growing tensor): call codebook.enable_device_reservoir() first")
-        self.accumulate, self.calls = accumulate, 0
-        self._graphs, self._cb_rows = {}, []
-        self._side = torch.cuda.Stream(device=example_images.device)
-        self._static = [example_images.detach().clone()]
         self.global_step = torch.full((), int(global_step), dtype=torch.int64, device=example_images.device)
         self.face_table, self._faces = None, False
         if getattr(loss, "face_loss", None) is not None:
             from . import face
             self.face_table = face.FaceTable(example_images.device)
         self._write_faces(example_bbox_face, example_images.shape[0])
-        self._warm_up(int(warmup))
+        super().__init__(None, gen_optimizer, (example_images,), amp_dtype=amp_dtype, warmup=warmup, modules=[model, loss], reducer=reducer,
+                         accumulate=accumulate)
+
+    _captures_at_construction = False                         # (a VQ-IMG model holds a codebook; without one the rule stays the same)
+
+    def _roles(self):
+        return {"the discriminator's optimizer": self.disc_optimizer, "the generator's optimizer": self.gen_optimizer}
 
     @staticmethod
     def _capturable_face(term):
@@ -528,12 +448,10 @@ class GraphedGanStep(GraphedTrainStep):
             self.disc_optimizer.step()
             self.gen_optimizer.step()
             if self.accumulate > 1:
-                grads = [p.grad for opt in self._opts for g in opt.param_groups for p in g["params"] if p.grad is not None]
-                if grads:
-                    torch._foreach_zero_(grads)
+                self._zero_grads_in_place()
         return GanStepOut(loss, d_loss, nll_loss, terms["g_loss"], terms["d_weight"])
 
     def __call__(self, images, bbox_face=None):
         self._check_inputs((images,))
         self._write_faces(bbox_face, images.shape[0])         # (before the tick: a box that is refused leaves the counters alone)
-        return self._call_phased((images,))
+        return self._replay((images,))

@@ -160,10 +160,20 @@ class _PackCache:
         if hit is None or hit[0]() is not w or hit[2].device != w.device:
             n = _packed_elems(w.shape[0], w.shape[1], w.shape[2], layout)
             self.store[key] = [weakref.ref(w, lambda _r, k=key: self.store.pop(k, None)), None, torch.empty(n, dtype=dtype, device=w.device)]
-        self._refresh_stale(w.device)
+        self.refresh_stale(w.device)
         return self.store[key][2]
 
-    def _refresh_stale(self, device):
+    def tensors(self):
+        """every device tensor a kernel launched now may read from this cache: packed images, derived images, item tables"""
+        return [e[2] for e in self.store.values()] + [e[2] for e in self.derived.values()] + [t[1] for t in self._tables.values()]
+
+    def forget_stamps(self):
+        """every image counts as stale again (the buffers stay, and are refreshed in place)"""
+        for e in self.store.values():
+            e[1] = None
+        self.derived.clear()
+
+    def refresh_stale(self, device):
         """Repacks EVERY stale entry on ``device``: after an optimizer step all of a model's images are stale at once.  The bf16 images
         of a parameter (forward / data-gradient operand, K64 / K32) are written together from ONE tiled read of it
         (``mas_pack_conv_weight_tiles``: one launch for the whole model); fp32 images (the parity mode) keep the gather kernel
@@ -246,6 +256,27 @@ def invalidate_weight_cache() -> None:
     (``drop_weight_cache_of``) from ``load_state_dict`` and on every train()/eval() switch."""
     _pack_cache.clear()
     _bf16_shadows.clear()
+
+
+# what a graph capture of a training step needs of the two caches (mas_hip.graphs); the optimizer's half is ``_note_optimizer_step``
+def refresh_stale_weight_images(device) -> None:
+    """Repacks, now, every packed convolution-weight image on ``device`` whose parameter has moved since it was packed (one or two
+    launches; nothing when none is stale).  A capture runs it first: the refresh uploads an item table whenever the set of stale
+    images is new, which a capture cannot hold -- afterwards the captured refresh of the same set finds its table on the device."""
+    _pack_cache.refresh_stale(device)
+
+
+def weight_cache_tensors() -> list:
+    """The tensors a capture taken now reads from the caches -- bf16 shadows, packed images, derived images, item tables -- for the
+    graph's owner to keep alive: ``invalidate_weight_cache()`` and ``swap_ema()`` drop the caches' own references."""
+    return _bf16_shadows.tensors() + _pack_cache.tensors()
+
+
+def forget_capture_stamps() -> None:
+    """After a capture: the caches stamped as fresh whatever they "refreshed" inside it (the captured model's images and any other
+    stale one in the process), but nothing ran.  Every shadow, stored image and derived image counts as stale again; the buffers stay."""
+    _bf16_shadows.forget_stamps()
+    _pack_cache.forget_stamps()
 
 
 def _packed_elems(cout: int, cin: int, ks: int, layout: int) -> int:
@@ -2147,6 +2178,15 @@ class _Bf16Shadows:
         k = id(p)
         if k not in self.params:
             self.params[k] = [weakref.ref(p, lambda _r, k=k: self.params.pop(k, None)), None, None]
+
+    def tensors(self):
+        """every bf16 copy a kernel launched now may read"""
+        return [e[2] for e in self.params.values() if e[2] is not None]
+
+    def forget_stamps(self):
+        """every copy counts as stale again (the buffers stay, and are recast in place)"""
+        for e in self.params.values():
+            e[1] = None
 
     def get(self, p: torch.nn.Parameter) -> torch.Tensor:
         self.register(p)

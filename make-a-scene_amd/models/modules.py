@@ -19,6 +19,7 @@ Parameters stay plain fp32 OIHW ``nn.Parameter``s (``change_requires_grad`` in t
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -337,7 +338,7 @@ class Codebook(nn.Module):
         self.reservoir_size = int(reservoir_size)
         self.reservoir = None
         self._dev = None                  # the device reservoir (enable_device_reservoir): buffer, counters, seed, the host's mirror of c
-        self._ticked_outside = False      # mas_hip.graphs.GraphedTrainStep ticks before a replay: forward must not tick again
+        self._ticked_outside = False      # inside ticked_by_caller() (a graphed step ticks before a replay): forward must not tick again
 
     # ---- device reservoir (opt-in) ------------------------------------------------------------------------------------
     def enable_device_reservoir(self, seed=None, device_kmeans=None):
@@ -396,13 +397,38 @@ class Codebook(nn.Module):
         if plan is None:
             plan = dev["plans"][batch_size] = torch.empty(ops.reservoir_plan_elems(batch_size), dtype=torch.int32, device=z.device)
         ops.reservoir_collect(z, dev["buf"], dev["state"], dev["seed"], plan)
-        self._note_collected(10 * batch_size)
+        self.replay_collected(10 * batch_size)
 
-    def _note_collected(self, n):
-        """the host's mirror of the rows held: min(R, c + n) after a collecting call, no read-back"""
+    def replay_collected(self, n):
+        """a collecting call -- this forward's, or a graph replay of it -- took ``n`` rows: the host's mirror of the rows held becomes
+        min(R, c + n), no read-back"""
         dev = self._dev
         dev["c"], dev["last_n"] = min(self.reservoir_size, dev["c"] + n), n
         self.reservoir = dev["buf"][:dev["c"]]
+
+    # ---- what a graphed step (mas_hip.graphs) does to a codebook: it ticks before each replay, captures the forward, counts after it ----
+    @contextlib.contextmanager
+    def ticked_by_caller(self):
+        """inside, the training forward leaves the tick to the caller, who calls ``tick()`` before it (or before a replay of it)"""
+        old, self._ticked_outside = self._ticked_outside, True
+        try:
+            yield
+        finally:
+            self._ticked_outside = old
+
+    @contextlib.contextmanager
+    def dry_forward(self):
+        """around a training forward that launches nothing (a graph capture): the host's mirror of the rows held is put back on exit,
+        since no kernel collected what the forward counted"""
+        c = self._dev["c"]
+        try:
+            yield
+        finally:
+            self._dev["c"], self.reservoir = c, self._dev["buf"][:c]
+
+    def rows_per_call(self):
+        """rows one training forward collects in the phase the codebook is in now, as the last collecting forward counted them"""
+        return self._dev.get("last_n", 0) if self.training and self.phase() >= 1 else 0
 
     @staticmethod
     def _randperm(n, device, keep=None):
@@ -446,27 +472,24 @@ class Codebook(nn.Module):
             pool = self.reservoir
         if self._dev is not None and self._dev["device_kmeans"]:
             # initial rows from the reservoir's seed at draw = q_counter: a resumed run draws what the uninterrupted one would
-            cent = kmeans_fit(pool, self.codebook_size, on_device=True, seed=self._dev["seed"], draw=self.q_counter).detach().contiguous()
-            if world_size > 1:
-                dist.broadcast(cent, 0)
-            self.embedding.weight.data.copy_(cent)        # in place: a captured step keeps reading the same storage
-            return
-        if self._dev is not None:
+            cent = kmeans_fit(pool, self.codebook_size, on_device=True, seed=self._dev["seed"], draw=self.q_counter)
+        elif self._dev is not None:
             # the cluster sums are index_add_: atomics in whatever order the device takes them unless torch is told otherwise
             det, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
             torch.use_deterministic_algorithms(True, warn_only=True)
             try:
-                cent = kmeans_fit(pool, self.codebook_size).detach().contiguous()
+                cent = kmeans_fit(pool, self.codebook_size)
             finally:
                 torch.use_deterministic_algorithms(det, warn_only=warn)
-            if world_size > 1:
-                dist.broadcast(cent, 0)
-            self.embedding.weight.data.copy_(cent)        # in place: a captured step keeps reading the same storage
-            return
-        cent = kmeans_fit(pool, self.codebook_size).detach().contiguous()
+        else:
+            cent = kmeans_fit(pool, self.codebook_size)
+        cent = cent.detach().contiguous()
         if world_size > 1:
             dist.broadcast(cent, 0)
-        self.embedding.weight.data = cent
+        if self._dev is not None:
+            self.embedding.weight.data.copy_(cent)        # in place: a captured step keeps reading the same storage
+        else:
+            self.embedding.weight.data = cent
 
     def _forward_device(self, z):
         """training forward with the device reservoir: tick (unless GraphedTrainStep did), collect, lookup"""
@@ -487,14 +510,14 @@ class Codebook(nn.Module):
         if self.training and self._dev is not None:
             return self._forward_device(z)
         if self.training:
-            self.q_counter += 1
-            if self.q_counter > self.q_start_collect:
+            self.q_counter += 1                           # (the reference's order: the re-initialisation AFTER the call's own collect)
+            phase = self.phase()
+            if phase >= 1:
                 self._collect(z.permute(0, 2, 3, 1).reshape(-1, self.codebook_dim), batch_size)
-            if self.q_counter < self.q_init:
+            if phase < 2:
                 return z, z.new_tensor(0), None           # warm-up: unquantised, loss 0, indices None
-            if self.q_init <= self.q_counter < self.q_re_end:
-                if (self.q_counter - self.q_init) % self.q_re_step == 0 or self.q_counter == self.q_init + self.q_re_end - 1:
-                    self._reinit_from_reservoir()
+            if self._reinit_due():
+                self._reinit_from_reservoir()
         z_q, loss, min_encoding_indices = ops.vq_lookup(z, self.embedding.weight, self.beta)
         return z_q, loss, min_encoding_indices
 

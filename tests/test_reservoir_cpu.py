@@ -145,3 +145,27 @@ def test_argument_checks_without_a_device():
     for bad, err in ((0, ValueError), (-2, ValueError), (2.0, TypeError), ("3", TypeError), (True, TypeError), (None, TypeError)):
         with pytest.raises(err, match="accumulate"):
             graphs.GraphedTrainStep(lambda x: x.sum(), None, torch.zeros(1), accumulate=bad)
+
+
+def test_host_reservoir_schedule_call_by_call(monkeypatch):
+    """the host-reservoir training forward over 70 calls (init_steps = 2: past q_re_end = 60): per call, whether the reservoir grew,
+    whether the call returned unquantised, whether the re-initialisation ran -- against the schedule written out from the four
+    constants.  The lookup kernel has no CPU path: it is stubbed (the schedule is decided before it is reached)."""
+    from mas_hip import ops
+    from models.modules import Codebook
+    cb = Codebook(64, 32, beta=0.25, init_steps=2, reservoir_size=64).train()
+    assert (cb.q_start_collect, cb.q_init, cb.q_re_end, cb.q_re_step) == (2, 6, 60, 1)
+    fired = []
+    monkeypatch.setattr(cb, "_reinit_from_reservoir", lambda: fired.append(cb.q_counter))
+    monkeypatch.setattr(ops, "vq_lookup", lambda z, w, beta: (z, z.new_tensor(0), torch.zeros(z.numel() // z.shape[1], dtype=torch.long)))
+    gen = torch.Generator().manual_seed(9)
+    for q in range(1, 71):
+        before, n_fired = cb.reservoir, len(fired)
+        _, _, idx = cb(torch.randn(2, 32, 4, 4, generator=gen))
+        assert cb.q_counter == q
+        # a collecting call takes 20 rows into a reservoir of 64: 20, 40, 60, then full -- and a new tensor every time, full or not
+        assert (cb.reservoir is not before) == (q > cb.q_start_collect) == (q > 2), q
+        assert (0 if cb.reservoir is None else cb.reservoir.shape[0]) == min(64, 20 * max(q - 2, 0)), q
+        assert (idx is None) == (q < 6), q
+        assert (len(fired) > n_fired) == (6 <= q < 60 and (q - 6) % 1 == 0), q
+    assert fired == list(range(6, 60))

@@ -452,6 +452,42 @@ int mas_attn_decode_split_dev(const void* q, const void* k_new, const void* v_ne
                               int ld_c, long long c_bs, int capacity, void* o, long long o_bs, int dtype, int B, int H, int hd,
                               const int32_t* past, float scale, int nsplit, float* workspace, size_t workspace_floats, void* stream);
 
+/* ---- decode attention for candidates that share a prompt (generate(num_samples=n): make-a-scene_amd/csrc/attn_decode_shared.hip).
+ * rows = groups * group cache rows, one new query row each (nq = 1); the `group` consecutive rows r with r / group == g are candidates
+ * for one prompt.  The keys live in two places:
+ *   prompt_k / prompt_v  [groups, prompt_len, H*hd]: read-only, block g shared by the rows of group g; ld_p elements between tokens, p_bs
+ *                        between blocks (views into a larger buffer are fine).
+ *   k_cache / v_cache    [rows, capacity, H*hd]: each row's image positions only; ld_c between tokens, c_bs between rows.
+ * Query r attends to the prompt_len keys of block r / group and to its own keys 0 .. past - prompt_len.  `past` keeps the meaning it has
+ * in every decode entry -- the number of positions before the new row, prompt included -- so a step counter serves both layouts.
+ * Two launches on `stream`, no parallel branch: "partial" -- groups*H*ceil(group / QT)*nsplit_prompt work-groups that walk one range of
+ * the prompt's keys for QT = MAS_ATTN_DECODE_SHARED_QT rows of a group at once (every 16-byte unit of a key row loaded once for the
+ * QT queries; ranges: chunks of ceil(prompt_len / nsplit_prompt) rounded up to 32 keys) and rows*H*nsplit_own work-groups that walk a row's own L_own = past -
+ * prompt_len + 1 keys (chunks of ceil(L_own / nsplit_own) rounded up to 32, as mas_attn_decode_split) -- and "combine", which merges the
+ * nsplit_prompt + nsplit_own states {o[hd], m, l} of workspace[(r*H + h)][s] in a fixed order: prompt ranges, then own ranges.
+ * The same inputs give the same bits; a row's bits depend on its query, its prompt block and its own cache alone (not on its place in
+ * the group, nor on other groups); they are not the bits of mas_attn_decode / _split on a concatenated cache (another summation order,
+ * the same tolerance).
+ * workspace: device fp32, at least rows*H*(nsplit_prompt + nsplit_own)*(hd + 2) floats (MAS_EWORKSPACE), the caller's, reusable by the
+ *   next call on the stream.  Each split count in [1, MAS_ATTN_DECODE_MAX_SPLITS]; group >= 1, rows % group == 0, prompt_len >= 1
+ *   (MAS_EINVAL); hd in {16,32,64,128}; dtype bf16 or fp32; rows 16-byte aligned (MAS_EUNSUPPORTED).  Nothing is launched on an error.
+ * mas_attn_decode_shared: host `past` in [prompt_len, prompt_len + capacity) (MAS_EINVAL otherwise); own rows 0 .. past - prompt_len
+ *   valid: the caller appends the new row BEFORE the call.  q: row r at q + r*q_bs.
+ * mas_attn_decode_shared_dev: *past on the device; the new k / v row (row r at k_new + r*new_bs, q likewise) is appended to own cache
+ *   row *past - prompt_len by the one work-group of each (r, h) whose range holds it, before that work-group loads any key.  *past <
+ *   prompt_len or *past - prompt_len >= capacity: every work-group returns at once; caches, workspace and o untouched.  Bit for bit the
+ *   output of mas_attn_decode_shared on a cache where the row was appended beforehand (the same two kernels).                        */
+#define MAS_ATTN_DECODE_SHARED_QT 4
+int mas_attn_decode_shared(const void* q, long long q_bs, const void* prompt_k, const void* prompt_v, int ld_p, long long p_bs,
+                           int prompt_len, const void* k_cache, const void* v_cache, int ld_c, long long c_bs, int capacity, void* o,
+                           long long o_bs, int dtype, int rows, int group, int H, int hd, int past, float scale, int nsplit_prompt,
+                           int nsplit_own, float* workspace, size_t workspace_floats, void* stream);
+int mas_attn_decode_shared_dev(const void* q, const void* k_new, const void* v_new, long long new_bs, const void* prompt_k,
+                               const void* prompt_v, int ld_p, long long p_bs, int prompt_len, void* k_cache, void* v_cache, int ld_c,
+                               long long c_bs, int capacity, void* o, long long o_bs, int dtype, int rows, int group, int H, int hd,
+                               const int32_t* past, float scale, int nsplit_prompt, int nsplit_own, float* workspace,
+                               size_t workspace_floats, void* stream);
+
 /* ---- small NHWC helpers on the path -------------------------------------------------
  * nearest x2 upsample (F.interpolate, modules.py:56) and its adjoint (2x2 sum);
  * zero-stuffing used by the stride-2 data gradient (adjoint of modules.py:76-78).      */

@@ -7,11 +7,15 @@ from typing import Optional
 
 import torch
 
-from . import ATTN_DECODE_MAX_SPLITS, _DT, _ptr, _require_cuda, _stream, check, lib
-from .ops import _ATTN_HEAD_DIMS
+from . import ATTN_DECODE_MAX_SPLITS, ATTN_DECODE_SHARED_QT, _DT, _ptr, _require_cuda, _stream, check, lib
+from .ops import _ATTN_HEAD_DIMS, _shared_layout, _shared_workspace
 
 GREEDY, SAMPLE, FORCED = 0, 1, 2
 AUTO_MAX_SPLITS = 8   # resolve_kv_splits("auto") never goes beyond: more splits measured slower
+AUTO_MAX_PROMPT_SPLITS = 4   # resolve_prompt_splits("auto") likewise (shared prompt)
+# Measurement only: an integer here replaces "auto" as the prompt split count of generate(num_samples=n, share_prompt=True), which has
+# no argument for it (tools/sample_bench.py --prompt-splits sets it around a call and puts None back).  It is part of the graph key.
+PROMPT_SPLITS_OVERRIDE = None
 
 
 def resolve_kv_splits(kv_splits, rows: int, n_heads: int, n_cus: int) -> int:
@@ -41,6 +45,68 @@ def resolve_kv_splits(kv_splits, rows: int, n_heads: int, n_cus: int) -> int:
 def split_workspace_floats(rows: int, n_heads: int, head_dim: int, n_split: int) -> int:
     """fp32 elements of the split decode attention's workspace: one {o[hd], m, l} state per (row, head, split)"""
     return rows * n_heads * n_split * (head_dim + 2)
+
+
+def shared_workspace_floats(rows: int, heads: int, hd: int, prompt_splits: int, own_splits: int) -> int:
+    """fp32 elements of the shared-prompt decode attention's workspace: one {o[hd], m, l} state per (row, head) and per key range, the
+    ``prompt_splits`` ranges of the prompt block first, then the ``own_splits`` ranges of the row's own cache"""
+    return rows * heads * (prompt_splits + own_splits) * (hd + 2)
+
+
+def resolve_prompt_splits(value, groups: int, group: int, heads: int, n_cus: int) -> int:
+    """The number of key ranges the prompt block of ``attention_decode_shared`` is split into: an integer in
+    [1, ATTN_DECODE_MAX_SPLITS] (itself) or ``"auto"``: the largest power of two n <= AUTO_MAX_PROMPT_SPLITS = 4 with
+    groups * ceil(group / QT) * heads * n <= n_cus -- ``resolve_kv_splits``'s rule applied to the prompt work-groups of the partial
+    launch (QT = ATTN_DECODE_SHARED_QT rows of a group per work-group), with the bound and the clamp the measurement of DESIGN 2.6
+    gives: at the four measured points (one prompt of 512 positions, 8 and 32 candidates, plain and guided: 32 / 64 / 128 / 256 prompt
+    work-groups on 256 compute units) it picks 4 / 4 / 2 / 1 ranges, the best measured column at each.  The rule first written down
+    (2 * n_cus, clamp 8: 8 / 8 / 4 / 2) lost 0.005 - 0.044 ms per token to it.  Beyond those points (other prompt lengths, more than 256
+    prompt work-groups) it is unmeasured.  Anything else raises ValueError."""
+    if isinstance(value, str):
+        if value != "auto":
+            raise ValueError(f"prompt_splits: {value!r} is neither an integer nor 'auto'")
+        if groups < 1 or group < 1 or heads < 1 or n_cus < 1:
+            raise ValueError(f"prompt_splits='auto': groups={groups}, group={group}, heads={heads}, n_cus={n_cus} must be positive")
+        blocks = groups * (-(-group // ATTN_DECODE_SHARED_QT)) * heads
+        n = 1
+        while 2 * n <= AUTO_MAX_PROMPT_SPLITS and blocks * 2 * n <= n_cus:
+            n *= 2
+        return n
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"prompt_splits: {value!r} is neither an integer nor 'auto'")
+    if not 1 <= value <= ATTN_DECODE_MAX_SPLITS:
+        raise ValueError(f"prompt_splits: {value} outside [1, {ATTN_DECODE_MAX_SPLITS}]")
+    return value
+
+
+def attention_decode_shared_dev(qkv: torch.Tensor, prompt_k: torch.Tensor, prompt_v: torch.Tensor, k_cache: torch.Tensor,
+                                v_cache: torch.Tensor, past: torch.Tensor, n_heads: int, *, group: int, prompt_splits: int = 1,
+                                kv_splits: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``attention_decode_dev`` for candidates that share a prompt (``mas_attn_decode_shared_dev``): qkv [rows, 1, 3D], prompt blocks
+    [rows / group, prompt_len, D] (read-only, block g serves rows g * group .. (g + 1) * group - 1), own caches [rows, cap, D] that hold
+    the image positions only, ``past`` a device int32 that counts the prompt too.  Appends k / v of the new row at own cache row
+    ``past - prompt_len`` and returns the context [rows, 1, D] of the query over its prompt block and its own rows 0 .. past -
+    prompt_len.  ``prompt_splits`` / ``kv_splits``: key ranges of the prompt block / of the own cache (None: 1); ``workspace``: fp32, at
+    least ``shared_workspace_floats(rows, n_heads, hd, prompt_splits, kv_splits)`` elements (allocated here when None)."""
+    who = "attention_decode_shared_dev"
+    _require_cuda(qkv, who)
+    if qkv.dim() != 3 or qkv.shape[2] % 3:
+        raise RuntimeError(f"{who}: qkv [rows, 1, 3D]")
+    d = qkv.shape[2] // 3
+    q = qkv[..., :d]
+    rows, d, hd, nsp, nso = _shared_layout(who, q, prompt_k, prompt_v, k_cache, v_cache, n_heads, group, prompt_splits, kv_splits)
+    if past.dtype != torch.int32 or past.device != qkv.device:
+        raise RuntimeError(f"{who}: past is a device int32")
+    workspace = _shared_workspace(who, workspace, shared_workspace_floats(rows, n_heads, hd, nsp, nso), qkv.device)
+    if out is None:
+        out = torch.empty((rows, 1, d), dtype=qkv.dtype, device=qkv.device)
+    check(lib().mas_attn_decode_shared_dev(_ptr(q), _ptr(qkv[..., d:2 * d]), _ptr(qkv[..., 2 * d:]), qkv.stride(0), _ptr(prompt_k),
+                                           _ptr(prompt_v), prompt_k.stride(1), prompt_k.stride(0), prompt_k.shape[1], _ptr(k_cache),
+                                           _ptr(v_cache), k_cache.stride(1), k_cache.stride(0), k_cache.shape[1], _ptr(out),
+                                           out.stride(0), _DT[qkv.dtype], rows, group, n_heads, hd, _ptr(past), float(hd) ** -0.5, nsp,
+                                           nso, _ptr(workspace), workspace.numel(), _stream()), "attn_decode_shared_dev")
+    return out
 
 
 def attention_decode_dev(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, past: torch.Tensor, n_heads: int,

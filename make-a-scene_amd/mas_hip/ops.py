@@ -1853,6 +1853,67 @@ def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return o
 
 
+def _shared_layout(who: str, q: torch.Tensor, prompt_k: torch.Tensor, prompt_v: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                   n_heads: int, group: int, prompt_splits, kv_splits):
+    """the checks ``attention_decode_shared`` and ``decode.attention_decode_shared_dev`` share; q [rows, 1, D] (any row stride).  Returns
+    (rows, d, hd, prompt split count, own split count)"""
+    rows, nq, d = q.shape
+    hd = d // n_heads
+    nsp = 1 if prompt_splits is None else prompt_splits
+    nso = 1 if kv_splits is None else kv_splits
+    for name, n in (("prompt_splits", nsp), ("kv_splits", nso)):
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= ATTN_DECODE_MAX_SPLITS:
+            raise RuntimeError(f"{who}: {name} {n!r} is not an integer in [1, {ATTN_DECODE_MAX_SPLITS}]")
+    others = (prompt_k, prompt_v, k_cache, v_cache)
+    if nq != 1 or q.dtype not in _DT or any(t.dtype != q.dtype for t in others):
+        raise RuntimeError(f"{who}: one new row; q, the prompt blocks and the caches share a dtype in {{float32, bfloat16}}")
+    if any(t.device != q.device for t in others):
+        raise RuntimeError(f"{who}: the prompt blocks and the caches live on q's device ({q.device})")
+    if hd * n_heads != d or hd not in _ATTN_HEAD_DIMS:
+        raise RuntimeError(f"{who}: head width {d}/{n_heads} not in {_ATTN_HEAD_DIMS}")
+    if not isinstance(group, int) or isinstance(group, bool) or group < 1 or rows % group:
+        raise RuntimeError(f"{who}: group {group!r} must be a positive integer that divides the {rows} rows")
+    if k_cache.shape != v_cache.shape or k_cache.dim() != 3 or k_cache.shape[0] != rows or k_cache.shape[2] != d \
+            or not k_cache.is_contiguous() or not v_cache.is_contiguous():
+        raise RuntimeError(f"{who}: caches {tuple(k_cache.shape)} must be contiguous [{rows}, cap, {d}]")
+    if prompt_k.dim() != 3 or prompt_k.shape != prompt_v.shape or prompt_k.shape[0] != rows // group or prompt_k.shape[1] < 1 \
+            or prompt_k.shape[2] != d or prompt_k.stride() != prompt_v.stride() or prompt_k.stride(2) != 1 or q.stride(2) != 1:
+        raise RuntimeError(f"{who}: prompt blocks {tuple(prompt_k.shape)} must be [{rows // group}, prompt_len, {d}] with contiguous rows "
+                           "and equal strides")
+    return rows, d, hd, nsp, nso
+
+
+def _shared_workspace(who: str, workspace, need: int, device):
+    if workspace is None:
+        return torch.empty(need, dtype=torch.float32, device=device)
+    if workspace.dtype != torch.float32 or workspace.device != device or not workspace.is_contiguous() or workspace.numel() < need:
+        raise RuntimeError(f"{who}: the workspace is a contiguous device fp32 tensor of at least {need} elements")
+    return workspace
+
+
+def attention_decode_shared(q: torch.Tensor, prompt_k: torch.Tensor, prompt_v: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                            past: int, n_heads: int, *, group: int, prompt_splits: int = 1, kv_splits: Optional[int] = None) -> torch.Tensor:
+    """Cached attention of one new row per cache row when ``group`` consecutive rows are candidates for one prompt
+    (``mas_attn_decode_shared``): q [rows, 1, H*hd] (a strided view of a fused qkv row is fine), prompt blocks [rows / group,
+    prompt_len, H*hd] -- stored once, block g read for the rows g * group .. (g + 1) * group - 1 together --, own caches
+    [rows, cap, H*hd] with the image positions only, rows 0 .. past - prompt_len valid (the new row already appended).  ``past`` counts
+    the prompt, as in ``attention_decode``.  Returns the context [rows, 1, H*hd] of every query over its prompt block and its own rows.
+    ``prompt_splits`` / ``kv_splits``: how many key ranges the prompt block / the own cache is walked in (None: 1)."""
+    who = "attention_decode_shared"
+    _require_cuda(q, who)
+    rows, d, hd, nsp, nso = _shared_layout(who, q, prompt_k, prompt_v, k_cache, v_cache, n_heads, group, prompt_splits, kv_splits)
+    plen, cap = prompt_k.shape[1], k_cache.shape[1]
+    if not plen <= past < plen + cap:
+        raise RuntimeError(f"{who}: past={past} outside [prompt_len, prompt_len + capacity) = [{plen}, {plen + cap})")
+    ws = _shared_workspace(who, None, rows * n_heads * (nsp + nso) * (hd + 2), q.device)
+    o = torch.empty((rows, 1, d), dtype=q.dtype, device=q.device)
+    check(lib().mas_attn_decode_shared(_ptr(q), q.stride(0), _ptr(prompt_k), _ptr(prompt_v), prompt_k.stride(1), prompt_k.stride(0), plen,
+                                       _ptr(k_cache), _ptr(v_cache), k_cache.stride(1), k_cache.stride(0), cap, _ptr(o), o.stride(0),
+                                       _DT[q.dtype], rows, group, n_heads, hd, int(past), float(hd) ** -0.5, nsp, nso, _ptr(ws),
+                                       ws.numel(), _stream()), "attn_decode_shared")
+    return o
+
+
 # --------------------------------------------------------------------------- #
 # transformer row operators: tanh-GELU, LayerNorm (+ fused residual)
 # --------------------------------------------------------------------------- #

@@ -22,6 +22,10 @@ mask and the kept tokens from the entry's static buffers (``keep`` uint8 [B, L],
 common prefix m never recapture.  With m > 0 the prefill has already run the m leading kept tokens: the caches are copied over plen + m
 rows, the counters start at step m, and the host replays L - 1 - m times.
 
+``generate(num_samples=n, share_prompt=True)`` is a configuration of its own (its key is longer: n and the prompt split count stand in
+front of the split count): the entry keeps the prompt's keys / values once per group of n candidates (``pk`` / ``pv`` [groups, plen, D]),
+caches of ``image_length`` rows, and the step calls ``mas_attn_decode_shared_dev`` (see ``generate_graph``).
+
 Tokens are drawn by Gumbel-max from Philox4x32-10 (include/mas_hip.h, "Sampling"): reproducible under ``torch.manual_seed`` or a seeded
 ``generator``, but not the tokens ``torch.multinomial`` would draw (the eager path's)."""
 import warnings
@@ -74,18 +78,28 @@ def _pointer_signature(model, bf16_autocast):
 class _Entry:
     """static buffers and the captured graph of one key"""
 
-    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1, top_p=False, prompted=False):
+    def __init__(self, model, b, rows, guided, mode, top_k, return_logits, kv_dtype, sig, kv_splits=1, top_p=False, prompted=False,
+                 num_samples=0, prompt_splits=1):
         dev = model.device
         d = model.transformer.layers[0].attn.hidden_dim
         heads = model.transformer.layers[0].attn.num_attn_heads
         # split decode attention (kv_splits > 1): one workspace for every layer -- they run one after the other on the graph's stream
         self.kv_splits = kv_splits
         self.split_ws = torch.empty(decode.split_workspace_floats(rows, heads, d // heads, kv_splits), dtype=torch.float32,
-                                    device=dev) if kv_splits > 1 else None
+                                    device=dev) if kv_splits > 1 and not num_samples else None
         s, length = model.total_length, model.image_length
         v = model.to_logits[1].out_features
         self.b, self.rows, self.guided, self.mode, self.top_k = b, rows, guided, mode, top_k
         self.plen = model.text_length + model.seg_length
+        # generate(num_samples=n): b = B * n token rows, `rows` cache rows in groups of n that share a prompt.  The prompt's keys / values
+        # are stored once per group (pk / pv), the caches hold the image positions only, and the step calls the shared-prompt attention
+        self.group, self.prompt_splits = num_samples, prompt_splits
+        if num_samples:
+            self.pk = [torch.empty((rows // num_samples, self.plen, d), dtype=kv_dtype, device=dev) for _ in model.transformer.layers]
+            self.pv = [torch.empty_like(t) for t in self.pk]
+            self.shared_ws = torch.empty(decode.shared_workspace_floats(rows, heads, d // heads, prompt_splits, kv_splits),
+                                         dtype=torch.float32, device=dev)
+            s = length
         self.kc = [torch.empty((rows, s, d), dtype=kv_dtype, device=dev) for _ in model.transformer.layers]
         self.vc = [torch.empty_like(t) for t in self.kc]
         self.x = torch.empty((rows, 1, d), dtype=torch.float32, device=dev)
@@ -119,8 +133,14 @@ def _step(model, e):
     for li, layer in enumerate(model.transformer.layers):
         attn = layer.attn
         qkv = attn.qkv(layer.ln_in(x))
-        a = attn.out_drop(attn.out_proj(decode.attention_decode_dev(qkv, e.kc[li], e.vc[li], e.ctr[1:2], attn.num_attn_heads,
-                                                                    kv_splits=e.kv_splits, workspace=e.split_ws)))
+        if e.group:
+            ctx = decode.attention_decode_shared_dev(qkv, e.pk[li], e.pv[li], e.kc[li], e.vc[li], e.ctr[1:2], attn.num_attn_heads,
+                                                     group=e.group, prompt_splits=e.prompt_splits, kv_splits=e.kv_splits,
+                                                     workspace=e.shared_ws)
+        else:
+            ctx = decode.attention_decode_dev(qkv, e.kc[li], e.vc[li], e.ctr[1:2], attn.num_attn_heads, kv_splits=e.kv_splits,
+                                              workspace=e.split_ws)
+        a = attn.out_drop(attn.out_proj(ctx))
         h = layer.first_ln_sandwich(a, residual=x) if layer.cogview_sandwich_layernorm else x + a
         m = layer.mlp(layer.ln_out(h))
         x = layer.second_ln_sandwich(m, residual=h) if layer.cogview_sandwich_layernorm else h + m
@@ -167,12 +187,18 @@ def _draw_seed(generator, device):
 
 
 def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits, kv_splits=1,
-                   top_p=None, keep=None, prefix=0):
+                   top_p=None, keep=None, prefix=0, num_samples=None):
     """``MakeAScene.generate(..., graph=True)``; returns None outside the envelope (the caller then runs the eager path).  ``kv_splits``:
     the resolved split count of the decode attention (1: ``mas_attn_decode_dev``; n > 1: ``mas_attn_decode_split_dev``), part of the key.
     ``top_p``: None (off: ``mas_sample_tokens``) or the validated nucleus mass in (0, 1); only "on" is part of the key.
     ``keep`` / ``prefix``: the validated image-prompt mask (None: none) and the number m of leading kept positions the prefill takes;
-    only "prompted" is part of the key"""
+    only "prompted" is part of the key.
+    ``num_samples`` n (validated; ``prefix`` is 0 with it): n candidates per prompt that share its keys / values.  The B prompts (2B under
+    guidance: conditional ones first, then the text-free ones) are prefilled once, their K / V go to per-layer prompt blocks
+    [groups, plen, D], the caches [groups * n, image_length, D] hold image positions only, the prefill's last logits row is repeated n
+    times per group (the sampler's Philox counter holds the row: the candidates differ from position 0 on) and the step calls
+    ``mas_attn_decode_shared_dev``.  Row b * n + j of the result is candidate j of prompt b.  n and the prompt split count
+    (``decode.resolve_prompt_splits("auto", ...)``) join the key in front of the split count"""
     reason = _envelope_reason(model)
     if reason is not None:
         warned = model.__dict__.setdefault("_decode_graph_warned", set())
@@ -180,9 +206,11 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
             warned.add(reason)
             warnings.warn(f"MakeAScene.generate(graph=True): {reason}; sampling eagerly instead", RuntimeWarning, stacklevel=3)
         return None
-    b = text_tokens.shape[0]
     guided = cond_scale is not None
-    rows = 2 * b if guided else b
+    n = int(num_samples) if num_samples is not None else 0
+    groups = text_tokens.shape[0] * (2 if guided else 1)     # prompts that are prefilled
+    b = text_tokens.shape[0] * max(n, 1)                     # token rows
+    rows = 2 * b if guided else b                            # cache rows
     prompted = keep is not None
     mode = decode.FORCED if (img_tokens is not None and not prompted) else (decode.GREEDY if temperature == 0 else decode.SAMPLE)
     m = int(prefix) if prompted else 0
@@ -193,6 +221,12 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     dev = model.device
     # the split count stays the key's last element: "prompted" goes in front of it
     key = (b, guided, mode, top_k, p_on, prompted, bool(return_logits), ops.compute_dtype(), autocast, ac_dtype, str(dev), int(kv_splits))
+    p_splits = 1
+    if n:                                               # a longer key: a call without num_samples never meets these entries
+        attn0 = model.transformer.layers[0].attn
+        p_splits = decode.resolve_prompt_splits(decode.PROMPT_SPLITS_OVERRIDE or "auto", groups, n, attn0.num_attn_heads,
+                                                torch.cuda.get_device_properties(dev).multi_processor_count)
+        key = key[:-1] + (n, p_splits, int(kv_splits))
     sig = _pointer_signature(model, autocast and ac_dtype == torch.bfloat16)
     graphs = model.__dict__.setdefault("_decode_graphs", {})
     params = _param_pointers(model)
@@ -210,7 +244,7 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     prompt = model._prompt_embeddings(text_tokens, seg_tokens)
     bb, plen, d = prompt.shape
     for layer in model.transformer.layers:
-        layer.attn.cache_capacity = model.total_length
+        layer.attn.cache_capacity = plen if n else model.total_length      # shared prompt: the prefill's cache holds the prompt alone
     if m:
         prompt = torch.cat([prompt, model._prefix_embeddings(img_tokens, m, guided)], dim=1)
     hidden, cache = model.transformer(prompt, None, cache={}, use_cache=True)
@@ -218,7 +252,7 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     prefix_logits = model._prefix_logits(hidden, plen, m, b, cond_scale) if m and return_logits else None
     kv = [(cache[i][0], cache[i][1]) for i in range(len(model.transformer.layers))]
     if e is None:
-        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits), p_on, prompted)
+        e = _Entry(model, b, rows, guided, mode, top_k, return_logits, kv[0][0].dtype, sig, int(kv_splits), p_on, prompted, n, p_splits)
         graphs[key] = e
 
     # ---- per-call device state, then the static caches ----
@@ -239,8 +273,11 @@ def generate_graph(model, text_tokens, seg_tokens, temperature, top_k, cond_scal
     rows_filled = plen + m
     from .transformer import _kv_backing
     for li, (k, v) in enumerate(kv):
-        e.kc[li][:, :rows_filled].copy_(_kv_backing(k, bb, d)[:, :rows_filled])
-        e.vc[li][:, :rows_filled].copy_(_kv_backing(v, bb, d)[:, :rows_filled])
+        kdst, vdst = (e.pk[li], e.pv[li]) if n else (e.kc[li], e.vc[li])
+        kdst[:, :rows_filled].copy_(_kv_backing(k, bb, d)[:, :rows_filled])
+        vdst[:, :rows_filled].copy_(_kv_backing(v, bb, d)[:, :rows_filled])
+    if n:
+        logits0 = logits0.repeat_interleave(n, dim=0)   # every candidate of a group draws position 0 from its prompt's row
     del cache, kv, hidden, prefix_logits
 
     # ---- token m (0 without a prefix) from the prefill (eager, the same sampler kernel), tokens m+1 .. L-1 by replay ----

@@ -396,7 +396,8 @@ class MakeAScene(nn.Module):
 
     @torch.no_grad()
     def generate(self, text_tokens, seg_tokens, temperature=1.0, top_k=None, cond_scale=None, generator=None, img_tokens=None,
-                 return_logits=False, *, graph=False, kv_splits=None, top_p=None, keep=None, prefill_prefix=True):
+                 return_logits=False, *, graph=False, kv_splits=None, top_p=None, keep=None, prefill_prefix=True, num_samples=None,
+                 share_prompt=False):
         """Autoregressive sampling of the ``image_length`` image tokens given text + segmentation tokens, KV-cached: one prefill
         over the prompt (the training attention kernel), then one ``mas_attn_decode`` pass per layer and token.
         ``temperature`` 0 -> greedy; ``top_k`` keeps the k most likely tokens; ``cond_scale`` s -> classifier-free guidance
@@ -438,32 +439,64 @@ class MakeAScene(nn.Module):
         logits; the token loop starts at position m, so keeping the top half of the image halves the call.  Finding m reads the mask on
         the host: one synchronisation before the loop when ``keep`` lives on the GPU, none when it is a CPU tensor; the replay loop of
         ``graph=True`` stays free of host calls.  False: every position takes a decode step -- the bits of the step-by-step path (the
-        prefill kernel sums in another order, so with True the logits move within the cached-against-uncached tolerance)."""
+        prefill kernel sums in another order, so with True the logits move within the cached-against-uncached tolerance).
+        ``num_samples`` n (an int >= 1, not a bool; anything else raises ValueError before the device is touched): n candidates for
+        every prompt in one call -- what ``log_likelihood``'s reranking recipe draws.  Returns [B * n, image_length]; row b * n + j is
+        candidate j of prompt b, the row order of ``text_tokens.repeat_interleave(n, 0)``, and ``img_tokens``, ``keep`` and the returned
+        logits have that many rows (another row count raises ValueError).  None: the code path and the bits of a call without it.
+        With ``graph=False`` or ``share_prompt=False`` the prompts are expanded with ``repeat_interleave`` and take the path above: n
+        prefills of the same prompt, n copies of its keys and values, each read once per candidate at every token; that is what the
+        result means.  With ``graph=True`` and ``share_prompt=True`` the B prompts (2B under guidance) are prefilled once, their keys /
+        values are stored once per layer and read once per ``ATTN_DECODE_SHARED_QT`` candidates (``mas_attn_decode_shared_dev``), and
+        the caches hold ``image_length`` rows per candidate instead of ``total_length``.  The candidates differ because the sampler's
+        random stream carries the row.  The summation order differs from the expanded path's, so logits agree within the kernels'
+        tolerance, not bit for bit.  ``keep`` works as above; ``prefill_prefix`` is ignored on this path: every position takes a decode
+        step.  ``kv_splits`` splits each candidate's own keys and "auto" counts the B * n (2 B * n) rows; the prompt's split count is
+        ``decode.resolve_prompt_splits("auto", ...)``.  Outside the graph envelope the call warns and runs the expanded prompts eagerly.
+        ``share_prompt`` defaults to False because sharing does not win everywhere it was measured (one prompt at config-4
+        width on an MI355X -- 32 candidates 3.17 -> 2.38 ms per token, 5.15 -> 2.82 with guidance, a third of the memory; 8 candidates
+        with guidance 2.06 -> 2.02; 8 candidates without 1.94 -> 1.97, a loss): pass True from about 16 cache rows per prompt on, or
+        whenever the n copies of the prompt's keys and values do not fit."""
         if top_p is not None:
             top_p = float(top_p)
             if not 0.0 < top_p <= 1.0:                                  # NaN fails both comparisons
                 raise ValueError(f"generate: top_p {top_p} outside (0, 1]")
             if top_p == 1.0:
                 top_p = None
+        n_rows = text_tokens.shape[0]
+        if num_samples is not None:
+            if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+                raise ValueError(f"generate: num_samples {num_samples!r} is not an integer >= 1")
+            n_rows *= num_samples
+            if isinstance(img_tokens, torch.Tensor) and img_tokens.shape[0] != n_rows:
+                raise ValueError(f"generate: num_samples={num_samples} takes img_tokens of {n_rows} rows (row b * n + j: candidate j of "
+                                 f"prompt b), not {img_tokens.shape[0]}")
+        shared = num_samples is not None and graph and share_prompt
+        if num_samples is not None and not shared:                      # the semantics: n unrelated copies of every prompt
+            text_tokens = text_tokens.repeat_interleave(num_samples, dim=0)
+            seg_tokens = seg_tokens.repeat_interleave(num_samples, dim=0)
         m = 0
         if keep is not None:
-            want = (text_tokens.shape[0], self.image_length)
+            want = (n_rows, self.image_length)
             if img_tokens is None:
                 raise ValueError("generate: keep says which of img_tokens stay; it needs img_tokens")
             if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or tuple(keep.shape) != want:
                 raise ValueError(f"generate: keep must be a bool tensor of shape {want}")
             if not isinstance(img_tokens, torch.Tensor) or tuple(img_tokens.shape) != want:
                 raise ValueError(f"generate: with keep, img_tokens must be a tensor of shape {want}")
-            if prefill_prefix:
+            if prefill_prefix and not shared:
                 from .image_prompt import common_prefix
                 m = common_prefix(keep)
-        n_split = self._resolve_kv_splits(kv_splits, text_tokens.shape[0] * (2 if cond_scale is not None else 1))
+        n_split = self._resolve_kv_splits(kv_splits, n_rows * (2 if cond_scale is not None else 1))
         if graph:
             from .decode_graph import generate_graph
             out = generate_graph(self, text_tokens, seg_tokens, temperature, top_k, cond_scale, generator, img_tokens, return_logits,
-                                 kv_splits=n_split, top_p=top_p, keep=keep, prefix=m)
+                                 kv_splits=n_split, top_p=top_p, keep=keep, prefix=m, num_samples=num_samples if shared else None)
             if out is not None:
                 return out
+            if shared:                                                  # outside the graph envelope: the expanded prompts, eagerly
+                text_tokens = text_tokens.repeat_interleave(num_samples, dim=0)
+                seg_tokens = seg_tokens.repeat_interleave(num_samples, dim=0)
         attns = [layer.attn for layer in self.transformer.layers]
         saved = [a.__dict__.get("decode_kv_splits") for a in attns]
         for a in attns:

@@ -26,6 +26,14 @@ entry on the unprompted amount of work.  The mask is a CPU tensor (no synchronis
 call time / 1024 whatever is kept, so the columns compare as call times.  With ``--profile`` every call is followed by its prompted
 twins (``prefill_prefix`` off: 1023 more ``sample_kernel`` launches with the mask).
 
+``--num-samples N ...``: a section of its own (the others are skipped): ``generate(num_samples=N, graph=True)`` for B = 1 prompt, plain
+and guided, ``--kv-splits`` as given (the first one; default "auto").  Columns ``expanded`` (``share_prompt=False``: the prompts
+repeated, the path a call on ``text.expand(N, -1)`` takes) and ``shared`` (``share_prompt=True``: one prefill, the prompt's K / V stored
+once, ``mas_attn_decode_shared_dev``), timed in one process, twice each (more with ``--runs``), alternating; ms per token (call time /
+1024: one token of all N candidates) and ``torch.cuda.max_memory_allocated`` of a call of each column alone.  ``--prompt-splits P ...``
+adds ``shared_p<P>`` columns with the prompt block in P key ranges instead of ``decode.resolve_prompt_splits("auto", ...)``.  With
+``--profile``: one guided call per column after a warm one, for rocprofv3 --kernel-trace --stats.
+
 ms per token = wall time of a whole call (prefill, first token and the 1023 replays, synchronised) / 1024; capture = first graph call
 minus a steady one (warm-up step, capture, graph instantiation)."""
 import argparse
@@ -67,6 +75,63 @@ def timed(fn):
     return time.perf_counter() - t, out
 
 
+def num_samples_section(a, m, dev, L, kw):
+    """--num-samples: B = 1 prompt, n candidates, plain and guided; columns ``share_prompt=False`` (the prompts expanded: the path of a
+    call on ``text.expand(n, -1)``), ``True`` and, with --prompt-splits, ``True`` with a fixed prompt split count"""
+    from mas_hip import decode
+    text, seg = prompt(1, dev)
+    kvs = a.kv_splits[0] if a.kv_splits else "auto"
+    auto_rule = decode.resolve_prompt_splits
+    cols = [("expanded", False, None), ("shared", True, None)] + [(f"shared_p{p}", True, p) for p in a.prompt_splits]
+
+    def call(n, cs, share, psplit):
+        decode.PROMPT_SPLITS_OVERRIDE = psplit              # None: "auto" (generate() has no argument for the prompt split count)
+        try:
+            return m.generate(text, seg, cond_scale=cs, graph=True, kv_splits=kvs, num_samples=n, share_prompt=share, **kw)
+        finally:
+            decode.PROMPT_SPLITS_OVERRIDE = None
+
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    if a.profile:
+        res = {"B": 1, "cond_scale": 3.0, "kv_splits": kvs}
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            for n in a.num_samples:
+                for tag, share, psplit in cols:
+                    call(n, 3.0, share, psplit)
+                    res[f"profile_call_s_n{n}_{tag}"] = round(timed(lambda: call(n, 3.0, share, psplit))[0], 4)
+        print(json.dumps(res))
+        return
+    rows = []
+    for n in a.num_samples:
+        for cs in (None, 3.0):
+            groups = 2 if cs is not None else 1
+            r = {"B": 1, "num_samples": n, "cond_scale": cs, "kv_splits": kvs, "kv_resolves_to": m._resolve_kv_splits(kvs, groups * n),
+                 "prompt_splits_auto": auto_rule("auto", groups, n, CFG["num_attn_heads"], cus)}
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+                for tag, share, psplit in cols:                     # memory: each column alone, entries and cached blocks released first
+                    m.release_decode_graphs()
+                    torch.cuda.empty_cache()
+                    torch.cuda.reset_peak_memory_stats()
+                    call(n, cs, share, psplit)
+                    torch.cuda.synchronize()
+                    r[f"max_memory_allocated_MiB_{tag}"] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+                m.release_decode_graphs()
+                for tag, share, psplit in cols:                     # capture
+                    call(n, cs, share, psplit)
+                times = {c[0]: [] for c in cols}
+                for _ in range(max(2, a.runs)):                     # every column twice, alternating: the spread is the noise to beat
+                    for tag, share, psplit in cols:
+                        times[tag].append(timed(lambda: call(n, cs, share, psplit))[0])
+            for tag, _, _ in cols:
+                r[f"ms_per_token_{tag}"] = round(1e3 * min(times[tag]) / L, 4)
+                r[f"spread_ms_per_token_{tag}"] = round(1e3 * (max(times[tag]) - min(times[tag])) / L, 4)
+            rows.append(r)
+            print(json.dumps(r), file=sys.stderr, flush=True)
+            m.release_decode_graphs()
+    print(json.dumps({"metric": "MakeAScene.generate(num_samples=n), config-4 width, bf16 autocast", "tokens_per_image": L,
+                      "top_k": kw["top_k"], "device": torch.cuda.get_device_name(0), "rows": rows}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
@@ -78,6 +143,10 @@ def main():
     ap.add_argument("--top-p", type=float, default=None, help="also time every graph-path column with generate(top_p=P)")
     ap.add_argument("--keep-rows", type=int, nargs="+", default=[],
                     help="also time every graph-path column with the top N token rows of a random image kept, prefill_prefix on and off")
+    ap.add_argument("--num-samples", type=int, nargs="+", default=[],
+                    help="time generate(num_samples=N, graph=True) for one prompt: share_prompt False against True (this section only)")
+    ap.add_argument("--prompt-splits", type=int, nargs="+", default=[],
+                    help="with --num-samples: also the shared column with the prompt block in this many key ranges instead of 'auto'")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     m = build(dev)
@@ -95,6 +164,9 @@ def main():
         img = torch.randint(0, CFG["image_vocab_size"], (b, L), generator=torch.Generator().manual_seed(100 + b)).to(dev)
         return dict(img_tokens=img, keep=border_keep_mask(n_dim, up=pk[0])[None].repeat(b, 1), prefill_prefix=pk[1])
 
+    if a.num_samples:
+        num_samples_section(a, m, dev, L, kw)
+        return
     prompts = [None] + [(n, on) for n in a.keep_rows for on in (True, False)]
     ptag = lambda pk: "" if pk is None else f"_keep{pk[0]}" + ("" if pk[1] else "_steps")
     if a.profile:

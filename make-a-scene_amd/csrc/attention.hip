@@ -696,7 +696,7 @@ int launch_fwd_fast(const AttnParams& p, hipStream_t s) {
         mas_attr_done(attr_mask, attr_bit);
     }
     hipLaunchKernelGGL(kern, dim3(mas_cdiv(p.S, QT), p.B * p.H), dim3(NT), G::LDS_BYTES, s, p);
-    MAS_CHECK_LAUNCH("attn_causal_fwd");
+    MAS_CHECK_LAUNCH("attn_causal_fwd_fast");
     return MAS_OK;
 }
 
@@ -1413,7 +1413,7 @@ int launch_bwd_fast64(const AttnBwdDropParams& pd, hipStream_t s) {
     constexpr size_t lds_dkv = 2 * (2 * FaTile::BYTES + 2 * 64 * sizeof(float)), lds_dq = 2 * (2 * FaTile::BYTES);
     hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<DROP>, grid, dim3(NT), lds_dkv, s, q);
     hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<DROP>, grid, dim3(NT), lds_dq, s, q);
-    MAS_CHECK_LAUNCH("attn_causal_bwd");
+    MAS_CHECK_LAUNCH("attn_causal_bwd_fast64");
     return MAS_OK;
 }
 
@@ -1426,7 +1426,7 @@ int launch_bwd(const AttnBwdDropParams& pd, hipStream_t s) {
     const dim3 grid(mas_cdiv(p.S, QT), p.B * p.H);
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD, DROP>), grid, dim3(NT), 0, s, a);
     hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD, DROP>), grid, dim3(NT), 0, s, a);
-    MAS_CHECK_LAUNCH("attn_causal_bwd");
+    MAS_CHECK_LAUNCH("attn_causal_bwd_generic");
     return MAS_OK;
 }
 
@@ -1452,7 +1452,7 @@ int launch_hd(const AttnDropParams& pd, int hd, hipStream_t s) {
         case 128: hipLaunchKernelGGL((attn_causal_fwd_kernel<T, 128, DROP>), grid, dim3(NT), 0, s, p); break;
         default: MAS_FAIL(MAS_EUNSUPPORTED, "attn_causal_fwd: head_dim %d not in {16,32,64,128}", hd);
     }
-    MAS_CHECK_LAUNCH("attn_causal_fwd");
+    MAS_CHECK_LAUNCH("attn_causal_fwd_generic");
     return MAS_OK;
 }
 

@@ -67,7 +67,8 @@ K_LSE = {("attn_causal_fwd_generic", "f32"): 32.0, ("attn_causal_fwd_generic", "
 FLOOR = 2.0 ** -100
 PLANT = 10
 GAP = 32.0
-DMIN = {16: 4, 32: 8, 64: 20, 128: 48}
+DMIN = {16: 4, 32: 8, 64: 20, 128: 48,
+        96: 24, 160: 48, 384: 140, 512: 200}    # the channel widths of tests/helpers/spatial_attn_check.py (code books of up to 769 keys)
 DROP_P, DROP_SEED = 0.25, (0x1234ABCD5678, 7)
 N_RULES = 11
 

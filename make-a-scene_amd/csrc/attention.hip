@@ -399,29 +399,10 @@ constexpr int F2_TILE = 64 * 128;                 // one 64-key x 64-dim bf16 ti
 constexpr int F2_STAGE = 2 * F2_TILE;             // K then V
 constexpr int F2_LDS = 2 * F2_STAGE;              // 32 KB
 
-// -DFA_TRACE (tools/build_file_variant.sh, never the shipped build): lane 0 of wave 3 of the heaviest work-group of (batch 0, head 0) sums
-// the 100 MHz wall clock over the phases of its key tiles (each phase closed by a read of its last result, so MFMA / LDS / VALU
-// latencies are inside the phase that caused them; every stamp is an s_memrealtime round trip of ~80 ns that lands in the phase it
-// closes); tools/kbench.py attn prints them.
-#ifdef FA_TRACE
-__device__ long long g_fa_trace[32];
-#define FA_T(i) do { if (fa_tr) { const long long now_ = wall_clock64(); fa_acc[i] += now_ - fa_last; fa_last = now_; } } while (0)
-#define FA_FORCE(x) do { if (fa_tr) asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(fa_sink) : "v"(x)); } while (0)
-#else
-#define FA_T(i) do { } while (0)
-#define FA_FORCE(x) do { } while (0)
-#endif
 // (DROP: the Philox work does not fit 128 VGPRs without scratch; 3 work-groups per CU, <= 168 VGPRs)
 template <bool DROP>
 __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kernel(FaFwdArgs<DROP> p) {
     using T = bf16_t;
-#ifdef FA_TRACE
-    const bool fa_tr = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 192;
-    long long fa_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const long long fa_t0 = wall_clock64();
-    long long fa_last = fa_t0;
-    int fa_sink = 0;
-#endif
     constexpr int HD = 64, KT2 = 64, NKK = 4, NMI = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char fa_smem[];
     const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) unsigned char*)fa_smem;
@@ -488,7 +469,6 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
     const int n_tiles = q_last / KT2 + 1;
     issue(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    FA_T(0);                                         // prologue: Q loads + the first tile's DMA
     // the Q fragments are USED here, before the loop: the compiler then places its own wait for their global loads here and not in
     // front of the first MFMA of every tile -- where a vmcnt(0) also waits for the DMA of the NEXT tile that was issued a few
     // instructions earlier (the counter cannot tell the two apart), i.e. exposes the whole prefetch latency once per tile
@@ -501,23 +481,11 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
         constexpr int ST = decltype(stage_c)::value;
         const int k0 = it * KT2;
         const bool more = it + 1 < n_tiles;
-#ifndef FA_ABL_NODMA
         if (more) issue(k0 + KT2, ST ^ 1);
-#else
-        (void)more;
-#endif
-        FA_T(1);                                     // DMA issue
         if (k0 <= qw + 31) {                         // wave-uniform: otherwise the tile is entirely above this wave's diagonal
             const unsigned char* kt = fa_smem + ST * F2_STAGE;
             const unsigned char* vt = kt + F2_TILE;
             f32x16 s[2];
-#ifdef FA_ABL_NOQK
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[sub][r] = (float)it;
-            (void)kt;
-#else
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
@@ -528,9 +496,6 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
                     mma16(s[sub], kf, qf[kk]);
                 }
             }
-#endif
-            FA_FORCE(s[1][15]);
-            FA_T(2);                                                // K fragment reads + score MFMAs
             if ((k0 + KT2 - 1 > qw) || (k0 + KT2 > p.S)) {          // tile touches the diagonal or the sequence end: mask
 #pragma unroll
                 for (int sub = 0; sub < 2; ++sub)
@@ -540,10 +505,6 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
                         if (!(key <= query && key < p.S)) s[sub][r] = -1e30f;
                     }
             }
-#ifdef FA_ABL_NOSOFTMAX                    // (ablation builds, tools/experiments/gpu_r5_12.sh: where the forward's time goes)
-            const float alpha = 1.0f;
-            l += s[0][0];
-#else
             float tmax = -1e30f;
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)
@@ -552,43 +513,23 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
             tmax = fmaxf(tmax, fa_other_half(tmax)) * c2;
             const float m_new = fmaxf(m, tmax);
             const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-#ifdef FA_ABL_NOEXP
-#define FA_EXP2(x) (x)
-#else
-#define FA_EXP2(x) __builtin_amdgcn_exp2f(x)
-#endif
-#ifdef FA_SCALAR_SOFTMAX   // one v_fma / v_exp / v_add per score (build with -fno-slp-vectorize): packed fp32 VALU beside MFMAs is priced as an
-            float rs0 = 0.0f, rs1 = 0.0f;                           // anti-lever in MI355X_MICROARCH.md (2 v_pk_add +26 cycles vs 2 v_fma per gap)
+            // one v_fma / v_exp / v_add per score (the file is built with -fno-slp-vectorize): packed fp32 VALU beside MFMAs is priced as
+            // an anti-lever in MI355X_MICROARCH.md (2 v_pk_add +26 cycles vs 2 v_fma per gap)
+            float rs0 = 0.0f, rs1 = 0.0f;
             const float nm = -m_new;
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {
-                    const float t0 = FA_EXP2(__builtin_fmaf(s[sub][r], c2, nm));
-                    const float t1 = FA_EXP2(__builtin_fmaf(s[sub][r + 1], c2, nm));
+                    const float t0 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[sub][r], c2, nm));
+                    const float t1 = __builtin_amdgcn_exp2f(__builtin_fmaf(s[sub][r + 1], c2, nm));
                     s[sub][r] = t0; s[sub][r + 1] = t1;
                     rs0 += t0; rs1 += t1;
                 }
             float rsum = rs0 + rs1;
-#else
-            fa_f32x2 rs2 = fa_f32x2{0.0f, 0.0f};
-            const fa_f32x2 c22 = fa_f32x2{c2, c2}, nm2 = fa_f32x2{-m_new, -m_new};
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    fa_f32x2 t2 = fa_f32x2{s[sub][r], s[sub][r + 1]} * c22 + nm2;
-                    t2[0] = __builtin_amdgcn_exp2f(t2[0]);
-                    t2[1] = __builtin_amdgcn_exp2f(t2[1]);
-                    s[sub][r] = t2[0]; s[sub][r + 1] = t2[1];
-                    rs2 += t2;
-                }
-            float rsum = rs2[0] + rs2[1];
-#endif
             rsum += fa_other_half(rsum);
             l = l * alpha + rsum;
             m = m_new;
-#endif
             if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
 #pragma unroll
                 for (int i = 0; i < NMI; ++i)
@@ -606,9 +547,6 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
                         for (int e = 0; e < 4; ++e) s[sub][4 * j + e] = ((km >> e) & 1) ? s[sub][4 * j + e] : 0.0f;
                     }
             }
-            FA_FORCE(l);
-            FA_FORCE(s[1][15]);
-            FA_T(3);                                                // mask + softmax (+ rescale)
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
@@ -616,26 +554,15 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
                     bf16x8 pf;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) pf[j] = (T)s[sub][8 * t + j];
-#ifdef FA_ABL_NOPV
-                    asm volatile("" ::"v"(pf));
-                    (void)vt;
-#else
 #pragma unroll
                     for (int i = 0; i < NMI; ++i) {
                         const unsigned char* a0 = vt + va[i] + (sub * 32 + 16 * t) * 128;
                         mma16(oacc[i], tr_frag(a0, a0 + 8 * 128), pf);
                     }
-#endif
                 }
         }
-        FA_FORCE(oacc[1][15]);
-        FA_T(4);                                                     // converts + V^T fragment reads + P V MFMAs
-#ifndef FA_ABL_NOBAR
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's pieces of the next tile have landed
-        FA_T(5);                                                     // wait for the next tile's DMA
         __syncthreads();
-        FA_T(6);                                                     // work-group barrier
-#endif
     };
     for (int it = 0; it < n_tiles; it += 2) {
         tile(it, std::integral_constant<int, 0>{});
@@ -657,23 +584,8 @@ __global__ __launch_bounds__(NT, DROP ? 3 : 4) void attn_causal_fwd_bf16_v2_kern
             }
         if (p.lse && g == 0) p.lse[((size_t)b * p.H + h) * p.S + query] = m * 0.6931471805599453f + __logf(l);
     }
-#ifdef FA_TRACE
-    FA_T(7);                                         // epilogue
-    if (fa_tr) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) g_fa_trace[i] = fa_acc[i];
-        g_fa_trace[8] = n_tiles; g_fa_trace[9] = fa_t0; g_fa_trace[10] = fa_last;
-    }
-    if (blockIdx.x == 0 && blockIdx.y == gridDim.y - 1 && threadIdx.x == 0) { g_fa_trace[11] = fa_t0; g_fa_trace[12] = wall_clock64(); }   // the lightest block of the same head
-    (void)fa_sink;
-#endif
 }
 
-#ifdef FA_TRACE
-}  // namespace
-extern "C" int mas_fa_trace(long long* out32) { return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_fa_trace), sizeof(long long) * 32); }
-namespace {
-#endif
 template <bool DROP>
 int launch_fwd_fast_v2(const AttnDropParams& p, hipStream_t s) {
     FaFwdArgs<DROP> q = p;
@@ -1056,9 +968,7 @@ __device__ __forceinline__ void fa_dma_tile(i32x4 rs, unsigned lds_tile, int row
     }
 }
 
-#ifndef FA_DKV_WGS
-#define FA_DKV_WGS 2
-#endif
+constexpr int FA_DKV_WGS = 2;
 template <bool DROP>
 __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwdArgs<DROP> p) {
     using T = bf16_t;
@@ -1132,9 +1042,7 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
     for (int it = 0; it < n_tiles; ++it) {
         const int q0 = q_start + it * QT2;
         const bool more = it + 1 < n_tiles;
-#ifndef FB_ABL_NODMA                                 // (ablation builds of the BACKWARD, round 6: profiles/r06_attn_bwd_ablation.txt; -DFB_ABL_* change results)
         if (more) issue(q0 + QT2, cur ^ 1);         // the other stage was last read before the barrier that ended the previous tile
-#endif
         const unsigned char* qt = fa_smem + cur * STAGE;
         const unsigned char* gt = qt + FaTile::BYTES;
         const float* lse_s = reinterpret_cast<const float*>(qt + 2 * FaTile::BYTES);
@@ -1154,12 +1062,8 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
                     for (int r = 0; r < 16; ++r) z[r] = 0.0f;
                     s = z; dp = z;
                 }
-#ifndef FB_ABL_NOSDP
                 mma16(s, qa, kf[kk]);
                 mma16(dp, ga, vf[kk]);
-#else
-                s[kk] += (float)qa[0]; dp[kk] += (float)ga[0];
-#endif
             }
             f32x4 l4[4], d4[4];                     // rows r = 4j..4j+3 are queries 8j + 4g + 0..3 of the block
 #pragma unroll
@@ -1170,13 +1074,8 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
             const bool needs_mask = (qs < kw + 31) || (qs + 32 > p.S) || (kw + 32 > p.S);
             // (the mask as ONE wave-uniform branch around 16 selects, not a branch per element: with the test inside the element loop the
             //  compiler cut this block into 33 basic blocks per 32 MFMAs and nothing could be scheduled across them)
-#ifndef FB_ABL_NOSOFTMAX
 #pragma unroll
-#ifndef FB_ABL_NOEXP
             for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, -l4[r >> 2][r & 3]));      // P[query][key]
-#else
-            for (int r = 0; r < 16; ++r) s[r] = __builtin_fmaf(s[r], c2, -l4[r >> 2][r & 3]);
-#endif
             if (needs_mask) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -1201,10 +1100,6 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
 #pragma unroll
             for (int r = 0; r < 16; ++r) dp[r] = s[r] * (dp[r] - d4[r >> 2][r & 3]) * p.scale;                            // dS[query][key]
             }
-#else
-            if (needs_mask && c2 == 12345.0f) s[0] = l4[0][0] + d4[0][0];
-#endif
-#ifndef FB_ABL_NOOUT
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 bf16x8 pf, sf;
@@ -1216,15 +1111,9 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
                     mma16(dk[i], fa_tr_tile_frag(qt, sub * 32 + 16 * t, i, g, G16, sl), sf);    // dK^T += Q^T dS
                 }
             }
-#else
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { dv[0][r] += s[r]; dk[0][r] += dp[r]; }
-#endif
         }
         if (more) commit(fa_smem + (cur ^ 1) * STAGE);
-#ifndef FB_ABL_NOWAIT                                // (timing only: is the DMA's LATENCY exposed, or only its issue?)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of the next tile have landed
-#endif
         __syncthreads();
         cur ^= 1;
     }
@@ -1250,9 +1139,7 @@ __global__ __launch_bounds__(NT, FA_DKV_WGS) void attn_bwd_dkv_bf16_kernel(FaBwd
     }
 }
 
-#ifndef FA_DQ_WGS
-#define FA_DQ_WGS 3
-#endif
+constexpr int FA_DQ_WGS = 3;
 template <bool DROP>
 __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdArgs<DROP> p) {       // (round 3: DMA staging -> <= 168 VGPRs, 3 waves per SIMD)
     using T = bf16_t;
@@ -1308,12 +1195,10 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdAr
     for (int it = 0; it < n_tiles; ++it) {
         const int k0 = it * KT2;
         const bool more = it + 1 < n_tiles;
-#ifndef FB_ABL_NODMA
         if (more) {                                 // the other stage was last read before the barrier that ended the previous tile
             fa_dma_tile(rs_k, lds0 + (cur ^ 1) * STAGE, k0 + KT2, p.S, p.ld, wave, lane, vo);
             fa_dma_tile(rs_v, lds0 + (cur ^ 1) * STAGE + FaTile::BYTES, k0 + KT2, p.S, p.ld, wave, lane, vo);
         }
-#endif
         const unsigned char* kt = fa_smem + cur * STAGE;
         const unsigned char* vt = kt + FaTile::BYTES;
 #pragma unroll
@@ -1331,21 +1216,12 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdAr
                     for (int r = 0; r < 16; ++r) z[r] = 0.0f;
                     s = z; dp = z;
                 }
-#ifndef FB_ABL_NOSDP
                 mma16(s, ka, qf[kk]);
                 mma16(dp, va, gf[kk]);
-#else
-                s[kk] += (float)ka[0]; dp[kk] += (float)va[0];
-#endif
             }
             const bool needs_mask = (ks + 31 > qw) || (ks + 32 > p.S);
-#ifndef FB_ABL_NOSOFTMAX
 #pragma unroll
-#ifndef FB_ABL_NOEXP
             for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c2, -my_lse2));
-#else
-            for (int r = 0; r < 16; ++r) s[r] = __builtin_fmaf(s[r], c2, -my_lse2);
-#endif
             if (needs_mask) {                                        // (one wave-uniform branch around 16 selects: see attn_bwd_dkv)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -1365,10 +1241,6 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdAr
 #pragma unroll
             for (int r = 0; r < 16; ++r) dp[r] = s[r] * (dp[r] - my_delta) * p.scale;                                     // dS^T[key][query]
             }
-#else
-            if (needs_mask && c2 == 12345.0f) s[0] = my_lse2 + my_delta;
-#endif
-#ifndef FB_ABL_NOOUT
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 bf16x8 sf;
@@ -1377,14 +1249,8 @@ __global__ __launch_bounds__(NT, FA_DQ_WGS) void attn_bwd_dq_bf16_kernel(FaBwdAr
 #pragma unroll
                 for (int i = 0; i < NMI; ++i) mma16(dq[i], fa_tr_tile_frag(kt, sub * 32 + 16 * t, i, g, G16, sl), sf);   // dQ^T += K^T dS^T
             }
-#else
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { dq[0][r] += s[r]; dq[1][r] += dp[r]; }
-#endif
         }
-#ifndef FB_ABL_NOWAIT
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of the next tile have landed
-#endif
         __syncthreads();
         cur ^= 1;
     }

@@ -29,11 +29,8 @@
 namespace {
 
 // queries per prompt tile: 4 builds at 124-126 VGPRs in bf16 (4 waves per SIMD), 8 at 203-206 (2 waves per SIMD); neither uses scratch
-// (profiles/shared_prompt_resources.txt has both builds).  -DDECODE_SHARED_QT=8 is that experiment's switch, nothing else sets it.
-#ifndef DECODE_SHARED_QT
-#define DECODE_SHARED_QT MAS_ATTN_DECODE_SHARED_QT
-#endif
-constexpr int QT = DECODE_SHARED_QT;
+// (profiles/shared_prompt_resources.txt has both builds)
+constexpr int QT = MAS_ATTN_DECODE_SHARED_QT;
 
 struct SharedParams {
     const void* q; const void* kn; const void* vn;   // kn / vn: the row to append (device-past form) or null

@@ -25,7 +25,7 @@
 namespace {
 
 struct StreamParams {
-    unsigned long long* dbg;                   // -DS_TIMELINE builds only (tools/timeline_stream.py): s_memtime stamps of one work-group
+    unsigned long long* dbg;                   // always null: nothing reads it (kept: the kernel argument layout is unchanged)
     const unsigned char* x; const float* ss; const unsigned char* w; const float* bias; const unsigned char* res; unsigned char* y;
     int N, H, W, Cin, Ho, Wo, Cout;
     int Hl, Wl, pad_top, pad_left, upsample, act;
@@ -49,29 +49,16 @@ template <int TH> struct SGeo {
 constexpr int S_WT = 128 * 128;                // one tap-step weight tile: 128 couts x 128 B
 constexpr int S_WSTAGE = 2 * S_WT;
 
-#ifndef S_ABL_NOBARRIER
-#define S_WAIT_BARRIER(N) WAIT_BARRIER(N)
-#else   // timing experiment only (races): what do the 9 work-group barriers per pair cost?
-#define S_WAIT_BARRIER(N) do { asm volatile("s_waitcnt vmcnt(" #N ") lgkmcnt(0)" ::: "memory"); asm volatile("" ::: "memory"); } while (0)
-#endif
-
-#ifdef S_TIMELINE      // stamps only where no ds_read is in flight (s_memtime returns through lgkmcnt)
-#define STS(id) do { if (lane == 0 && blockIdx.x == 100 && tl_iter >= 1 && tl_iter < 3 && p.dbg) \
-                         p.dbg[((tl_iter - 1) * 8 + wave) * 64 + (id)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STS(id) do {} while (0)
-#endif
-
 __device__ __forceinline__ void s_wait_barrier(int n) {   // n is compile-time after unrolling, or selected by a uniform branch
     switch (n) {
-        case 0: S_WAIT_BARRIER(0); break;
-        case 1: S_WAIT_BARRIER(1); break;
-        case 2: S_WAIT_BARRIER(2); break;
-        case 3: S_WAIT_BARRIER(3); break;
-        case 4: S_WAIT_BARRIER(4); break;
-        case 7: S_WAIT_BARRIER(7); break;
-        case 8: S_WAIT_BARRIER(8); break;
-        default: S_WAIT_BARRIER(0); break;
+        case 0: WAIT_BARRIER(0); break;
+        case 1: WAIT_BARRIER(1); break;
+        case 2: WAIT_BARRIER(2); break;
+        case 3: WAIT_BARRIER(3); break;
+        case 4: WAIT_BARRIER(4); break;
+        case 7: WAIT_BARRIER(7); break;
+        case 8: WAIT_BARRIER(8); break;
+        default: WAIT_BARRIER(0); break;
     }
 }
 
@@ -157,13 +144,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
         const int soff = t0 * wstride + c0 * 128 + wpiece;
         unsigned char* dst = wbuf + sel * S_WSTAGE + wave * 4096;
         // the instruction's immediate offset advances BOTH the memory address and the LDS address (LDS = M0 + imm + 16*lane)
-#ifndef S_ABL_NOW
 #define S_WDMA(K) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)dst, 16, wlane, soff, (K) * 1024, 0)
         S_WDMA(0); S_WDMA(1); S_WDMA(2); S_WDMA(3);
 #undef S_WDMA
-#else
-        if (p.N == -12345) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)dst, 16, wlane, soff, 0, 0);
-#endif
     };
 
     // ---- patch operations ---------------------------------------------------------------------------------------
@@ -173,9 +156,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
         for (int k = 0; k < G::NSLOT; ++k) {
             if (k < i0 || k >= i0 + cnt) continue;
             const int piece = (wave + 8 * k < G::NPIECE) ? wave + 8 * k : wave + 8 * (k - 1);
-#ifdef S_ABL_NOPATCH
-            if (p.N != -12345) continue;
-#endif
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(patch + buf * G::PATCH + piece * 1024),
                                                      16, vo[k], soff, 0, 0);
         }
@@ -243,9 +223,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
     auto store_one = [&](int k) {               // k = (j*2 + i)*2 + qp
         const int j = k >> 2, i = (k >> 1) & 1, qp = k & 1;
         const int off = ooff[j] + (i * 32 + qp * 16) * 2;
-#ifdef S_ABL_NOEPI
-        if (p.N != -12345) { asm volatile("" :: "v"(outp[k])); return; }
-#endif
         __builtin_amdgcn_raw_buffer_store_b128(outp[k], rs_y, off, 0, 0);
     };
 
@@ -267,31 +244,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
     p_dma(rs_cur, vo_cur, 0, 0, 0, G::NSLOT);
     if constexpr (ACT) {
         ss_load(cur.n, 0);
-        S_WAIT_BARRIER(0);                       // the raw patch of chunk 0 has landed for every wave
+        WAIT_BARRIER(0);                       // the raw patch of chunk 0 has landed for every wave
         p_activate(inb_cur, 0, 0, 3);
         p_activate(inb_cur, 0, 3, 3);
     }
     const int n_pairs = p.n_chunks >> 1;
-#ifdef S_PRIO_HALF   // MI355X_MICROARCH.md "Two waves per SIMD" item 4: static priority for the second-dispatched half
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
-#ifdef S_DEBUG_DUMP      // debug build: dump weight stage 0 (32 KiB) + patch buffer 0 (41 KiB) of work-group 0's first tile into y
-    S_WAIT_BARRIER(0);
-    if (blockIdx.x == 0) {
-        for (int i = tid; i < S_WSTAGE / 16; i += 512) reinterpret_cast<u32x4*>(p.y)[i] = *reinterpret_cast<const u32x4*>(wbuf + i * 16);
-        for (int i = tid; i < G::PATCH / 16; i += 512) reinterpret_cast<u32x4*>(p.y + S_WSTAGE)[i] = *reinterpret_cast<const u32x4*>(patch + i * 16);
-    }
-    return;
-#endif
 
-#ifdef S_TIMELINE
-    int tl_iter = 0;
-#endif
     for (;;) {
         const int next_tile = tile + step;
         const bool has_next = next_tile < tile_end;
         const Tile nxt = has_next ? decode(next_tile) : cur;
-        STS(0);
 
         f32x16 acc[2][G::NJ];
 #pragma unroll
@@ -314,7 +276,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
                 constexpr int s = decltype(s_c)::value;
                 // ---- barrier(s): stage s's weights, and every patch chunk it reads, are visible; stage s-1's buffers are free.
                 //      vmcnt allowance = the VMEM operations issued AFTER the weight DMA in stage s-1 (they may stay in flight)
-                if (pair == 0) STS(1 + 3 * s);
                 {
                     constexpr int sp = (s + 8) % 9;           // previous stage (of this or the previous pair)
                     constexpr int npatch = ACT ? ((sp == 0 || sp == 5) ? 7 : ((sp == 1 || sp == 6) ? 3 : 0))
@@ -323,14 +284,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
                     else if (s == 0 && imm_stores) { s_wait_barrier(G::NST); imm_stores = false; }   // younger than stage 0's weight DMA
                     else s_wait_barrier(npatch);
                 }
-                if (pair == 0) STS(2 + 3 * s);
-#ifdef S_DEBUG_DUMP_STAGE   // debug build: the weight stage + both patch buffers as stage S_DEBUG_DUMP_STAGE of work-group 0 sees them -> p.res
-                if (s == S_DEBUG_DUMP_STAGE && blockIdx.x == 0 && tile == 0 && pair == 0) {
-                    unsigned char* dd = const_cast<unsigned char*>(p.res);
-                    for (int i = tid; i < S_WSTAGE / 16; i += 512) reinterpret_cast<u32x4*>(dd)[i] = *reinterpret_cast<const u32x4*>(wbuf + wsel * S_WSTAGE + i * 16);
-                    for (int i = tid; i < 2 * G::PATCH / 16; i += 512) reinterpret_cast<u32x4*>(dd + S_WSTAGE)[i] = *reinterpret_cast<const u32x4*>(patch + i * 16);
-                }
-#endif
                 // ---- register path: commit what was loaded two stages ago (guaranteed landed by the wait above)
                 if constexpr (ACT) {
                     if (s == 2) p_activate(inb_cur, 1, 0, 3);
@@ -375,10 +328,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
                 }
                 asm volatile("" ::: "memory");
                 };
-#ifndef S_LATE_ISSUE
                 late_ops();
-#endif
-                if (pair == 0) STS(3 + 3 * s);
                 // ---- 2 tap-steps = 8 k-steps of 4 MFMAs; fragment reads software-pipelined one k-step ahead
                 {
                     const unsigned char* wb = wbuf + wsel * S_WSTAGE;
@@ -410,22 +360,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
                     }
                     __builtin_amdgcn_sched_group_barrier(0x008, 2 * G::NJ, 0);
                 }
-#ifdef S_LATE_ISSUE   // HBM-facing operations of this stage issued at its END, where the early half of the waves would wait at the barrier anyway
-                asm volatile("" ::: "memory");
-                late_ops();
-#endif
                 wsel ^= 1;
             });
         }
 
-        STS(40);
-#ifdef S_ABL_NOEPIALL   // timing experiment only: no epilogue at all (the accumulators are consumed by an impossible store)
-        if (p.N != -12345) {
-            float t = 0.0f;
-            for (int i = 0; i < 2; ++i) for (int j = 0; j < G::NJ; ++j) for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-            if (t == 123.456f) reinterpret_cast<float*>(p.y)[0] = t;
-        } else
-#endif
         // ---- epilogue: lanes l / l+32 exchange accumulator quads (fp32) so each lane owns 8 consecutive couts of its pixel;
         //      bias and residual arrive by UNCONDITIONAL buffer loads (a null pointer is a zero-length descriptor that returns
         //      zeros): no per-load branches, so hipcc batches the 24 loads instead of waiting for each one
@@ -478,10 +416,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_stream_kernel(StreamParams p) 
             pending_out = DEFER;
             imm_stores = !DEFER;
         }
-        STS(41);
-#ifdef S_TIMELINE
-        ++tl_iter;
-#endif
         if (!has_next) break;
         tile = next_tile; cur = nxt; rs_cur = rs_nxt; inb_cur = inb_nxt;
 #pragma unroll
@@ -531,9 +465,6 @@ int mas_conv3x3_stream_try(const MasConvDesc* d, const void* x, const float* sca
     if (img_bytes >= 0x7fffffffLL || out_bytes >= 0x7fffffffLL) return 0;
     StreamParams p;
     p.dbg = nullptr;
-#ifdef S_TIMELINE
-    if (const char* e = getenv("MAS_DBG_PTR")) p.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
-#endif
     p.x = (const unsigned char*)x; p.ss = scale_shift; p.w = (const unsigned char*)w_packed; p.bias = bias;
     p.res = (const unsigned char*)residual; p.y = (unsigned char*)y;
     p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;

@@ -27,7 +27,7 @@
 namespace {
 
 struct WideParams {
-    unsigned long long* dbg;                   // -DW_TIMELINE builds only
+    unsigned long long* dbg;                   // always null: nothing reads it (kept: the kernel argument layout is unchanged)
     const unsigned char* x; const float* ss; const unsigned char* w; const float* bias; const unsigned char* res; unsigned char* y;
     float* stats;                              // optional [N][tiles_h * tiles_w][Cout][2]: per-tile sum / sum of squares of the bf16 OUTPUT (the consumer's GroupNorm statistics)
     int N, H, W, Cin, Ho, Wo, Cout;
@@ -53,13 +53,6 @@ constexpr int W_SS = W_NEXT + 512 * 16;        // [2][Cin <= 512][2] fp32 GroupN
 constexpr int W_MAXCIN = 512;
 constexpr int W_LDS = W_SS + 2 * W_MAXCIN * 8;   // + {table row, cout offset} of the pending statistics flush
 constexpr int W_NSLOT = 5;                     // patch DMA pieces (and 16-byte activation slots) per wave (thread) per chunk
-
-#ifdef W_TIMELINE
-#define WTS(id) do { __builtin_amdgcn_sched_barrier(0); if (lane == 0 && blockIdx.x == 100 && tl_iter >= 1 && tl_iter < 3 && p.dbg) \
-                         p.dbg[((tl_iter - 1) * 8 + wave) * 64 + (id)] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define WTS(id) do {} while (0)
-#endif
 
 __device__ __forceinline__ void w_wait_barrier(int n) {   // n is a compile-time constant after unrolling, or selected by a uniform branch
     switch (n) {
@@ -152,9 +145,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
         for (int k = 0; k < W_NSLOT; ++k) {
             if (k < k0 || k >= k0 + cnt) continue;
             const int piece = (k < 4) ? wave + 8 * k : (wave < 7 ? 32 + wave : 38);
-#ifdef W_ABL_NOPATCH
-            if (p.N != -12345) continue;
-#endif
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(patch + buf * W_PATCH + piece * 1024),
                                                      16, vo[k], soff, 0, 0);
         }
@@ -208,9 +198,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
         //  operand with a waterfall loop around every DMA instruction)
         const int soff = __builtin_amdgcn_readfirstlane(t0 * wstride + c0 * 64 + wave * 1024);
         unsigned char* dst = wbuf + sel * W_WSTAGE + wave * 1024;
-#ifdef W_ABL_NOW
-        if (p.N != -12345) return;
-#endif
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)dst, 16, wlane, soff, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(dst + W_WT), 16, wlane, soff + wstride, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(dst + 2 * W_WT), 16, wlane, soff + 2 * wstride, 0, 0);
@@ -269,14 +256,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
     };
     bool stores_in_flight = false;               // the previous tile's 32 epilogue stores may still be in flight at the first wait
     const int n_pairs = p.n_chunks >> 1;
-#ifdef W_TIMELINE
-    int tl_iter = 0;
-#endif
 
     for (;;) {
         const int next_tile = tile + step;
         const bool has_next = next_tile < tile_end;
-        WTS(0);
 
         f32x16 acc[4][2];
 #pragma unroll
@@ -293,7 +276,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                 constexpr int s = decltype(s_c)::value;
                 constexpr int cb = s / 3, kh = s % 3;         // chunk A / B of the pair (= patch buffer), filter row
                 constexpr int wsel = s & 1;
-                if (pair < 2) WTS(1 + 3 * (pair * 6 + s));
                 // ---- barrier: this stage's weights, and the patch chunk it reads, are visible; the previous stage's buffers are free.
                 //      vmcnt allowance = VMEM operations issued AFTER the weight DMA in the previous stage
                 {
@@ -304,7 +286,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                         if constexpr (STATS) stats_flush();      // the finished tile's statistics: one store, older than this stage's weight DMA
                     } else w_wait_barrier(allow);      // one store, older than this stage's weight DMA
                 }
-                if (pair < 2) WTS(2 + 3 * (pair * 6 + s));
                 // ---- the next tile's plan, and GroupNorm(+SiLU) in place on the NEXT chunk's raw patch (all of it has landed: allowance 0 above)
                 auto plan_blk = [&]() {
                     if (s == 2 && last_pair && has_next) {        // the next tile's plan (used by the chunk-B stages 3, 4); without a next
@@ -352,7 +333,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                     }
                 }
                 asm volatile("" ::: "memory");
-                if (pair < 2) WTS(3 + 3 * (pair * 6 + s));
                 // ---- 3 taps x 2 k-steps of 8 MFMAs; fragment reads software-pipelined one k-step ahead
                 {
                     const unsigned char* wb = wbuf + wsel * W_WSTAGE;
@@ -363,16 +343,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
 #pragma unroll
                         for (int j = 0; j < 2; ++j)
                             bfr[b][j] = *reinterpret_cast<const bf16x8*>(pb + (b_addr(pj0 + (j + kh) * W_PWL + kw) ^ kx));
-#ifdef W_ABL_HALF_A   // timing experiment only (wrong results): 2 of the 4 weight fragments per k-step are not re-read -- 0.5 instead of 0.75
-#pragma unroll        // LDS reads per MFMA: what a 128 x 128 register tile would buy (tools/experiments/gpu_r3_41.sh)
-                        for (int i = 0; i < 2; ++i)
-                            afr[b][i] = *reinterpret_cast<const bf16x8*>(wb + kw * W_WT + i * 2048 + (a_off ^ kx));
-                        if (p.N == -12345) { afr[b][2] = afr[b][0]; afr[b][3] = afr[b][1]; }
-#else
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             afr[b][i] = *reinterpret_cast<const bf16x8*>(wb + kw * W_WT + i * 2048 + (a_off ^ kx));
-#endif
                     };
                     ld_k(0, 0);
 #pragma unroll
@@ -394,14 +367,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
             });
         }
 
-        WTS(60);
-#ifdef W_ABL_NOEPI     // timing experiment only
-        if (p.N != -12345) {
-            float t = 0.0f;
-            for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-            if (t == 123.456f) reinterpret_cast<float*>(p.y)[0] = t;
-        } else
-#endif
         // ---- epilogue.  The weight rows of a cout tile are stored PERMUTED (LDS row 32 i + l holds cout 4 l + i, see
         //      mas_pack_conv_weight_layout), so a lane owns 4 CONSECUTIVE couts (one of each of its 4 accumulator tiles) of the
         //      16 pixels of each register block: one 8-byte store per pixel and lane, and the 32 lanes of a half-wave write one
@@ -464,13 +429,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                 for (int i = 0; i < 4; ++i) ob[i] = (bf16_t)v[i];
                 return o;
             };
-#ifndef W_ST_AUX
-#define W_ST_AUX 0
-#endif
             auto store = [&](int j, int r, u32x2 o) {
                 const int pc = (r & 3) + 8 * (r >> 2);
                 const bool ok = (pc < ob_cur[2]) && (ob_cur[j] != OOB_VOFFSET);
-                __builtin_amdgcn_raw_buffer_store_b64(o, rs_y, ok ? ob_cur[j] : OOB_VOFFSET, pc * row_bytes, W_ST_AUX);
+                __builtin_amdgcn_raw_buffer_store_b64(o, rs_y, ok ? ob_cur[j] : OOB_VOFFSET, pc * row_bytes, 0);
             };
             if constexpr (RES) {
                 res_load(0);
@@ -502,10 +464,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wide_kernel(WideParams p) {
                 if (tid == 0) { int* meta = reinterpret_cast<int*>(smem + W_STAT + 8 * 128 * 2 * 4); meta[0] = ob_cur[3]; meta[1] = c0_cur; }
             }
         }
-        WTS(61);
-#ifdef W_TIMELINE
-        ++tl_iter;
-#endif
         if (!has_next) break;
         tile = next_tile; c0_cur = c0_nxt; n_cur = n_nxt; inb_cur = inb_nxt; ss_sel ^= 1;
         { const u32x4 nx = *reinterpret_cast<const u32x4*>(smem + W_NEXT + tid * 16); ob_cur[0] = (int)nx[0]; ob_cur[1] = (int)nx[1]; ob_cur[2] = (int)nx[2]; ob_cur[3] = (int)nx[3]; }
@@ -567,9 +525,6 @@ int mas_conv3x3_wide_launch(const MasConvDesc* d, const void* x, const float* sc
     WideParams p;
     p.dbg = nullptr;
     p.stats = stats;
-#ifdef W_TIMELINE
-    if (const char* e = getenv("MAS_DBG_PTR")) p.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
-#endif
     p.x = (const unsigned char*)x; p.ss = scale_shift; p.w = (const unsigned char*)w_packed; p.bias = bias;
     p.res = (const unsigned char*)residual; p.y = (unsigned char*)y;
     p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;

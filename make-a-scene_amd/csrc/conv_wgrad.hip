@@ -18,7 +18,7 @@
 namespace {
 
 struct WgradParams {
-    unsigned long long* dbg;
+    unsigned long long* dbg;   // always null: nothing reads it (kept: the kernel argument layout is unchanged)
     const void* x; const float* ss; const void* dy; float* dw; float* dbias;
     int N, H, W, Cin, Ho, Wo, Cout;
     int Hl, Wl, pad_top, pad_left, act, upsample;
@@ -27,19 +27,13 @@ struct WgradParams {
                            // sums into dw + s * Cout*KS*KS*Cin and dbias + s * Cout -- mas_wgrad_reduce adds the slabs in a fixed order
 };
 
-#ifndef MAS_WGRAD_BCI
-#define MAS_WGRAD_BCI 32
-#endif
 // work-group = 128 co x BCI ci x all taps; 4 waves per 32 ci, so BCI = 32 -> 256 threads and two independent
 // work-groups per CU (one stages while the other runs MFMAs), BCI = 64 -> 512 threads, one per CU
-constexpr int BCI = MAS_WGRAD_BCI, TWW = 16, BCO = 128;
+constexpr int BCI = 32, TWW = 16, BCO = 128;
 // 3x3: each 32x32 (co x ci) accumulator tile is shared by SPLIT = 2 waves that split the 9 taps 5 / 4, so a wave holds
 // 80 accumulator VGPRs instead of 144 (which left no registers to batch the staging loads and forced spills) and the
 // work-group is 16 waves = 4 per SIMD.  1x1: one wave per tile, 8 waves.
-#ifndef MAS_WGRAD_SPLIT
-#define MAS_WGRAD_SPLIT 2
-#endif
-template <int KS> struct WSplit { static constexpr int SPLIT = KS == 3 ? MAS_WGRAD_SPLIT : 1, NTW = 64 * 4 * (BCI / 32) * SPLIT; };
+template <int KS> struct WSplit { static constexpr int SPLIT = KS == 3 ? 2 : 1, NTW = 64 * 4 * (BCI / 32) * SPLIT; };
 
 template <typename T, int KS, int STRIDE, int THW>
 struct WGeo {
@@ -182,12 +176,6 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
     const T* a_frag_base = dyt + (wco + l31) * DS + skew_a + g * 8;
     const T* b_frag_base = at + (wci + l31) * CS + skew_b + g * 8;
 
-#ifdef MAS_TIMELINE
-    int tl_iter = 0;
-#define WTS(id) do { if (lane == 0 && blockIdx.x == 100 && tl_iter < 4 && p.dbg) p.dbg[(tl_iter * 8 + wave) * 8 + (id)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WTS(id) do {} while (0)
-#endif
     // ---- fast staging (16-byte aligned channel slots): the global loads of tile k+1 are issued into registers right
     // before the MFMA phase of tile k and converted / transposed into LDS after it, so HBM latency hides under the MFMAs
     const bool fast = vec_dy && vec_x;
@@ -282,7 +270,6 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
                 }
                 store_quad_bf16(reinterpret_cast<bf16_t*>(dyt), DS, dy_cu, pix0, o);
             }
-            WTS(2);
 #pragma unroll
             for (int qi = 0; qi < A_PER_T / 4; ++qi) {
                 const int grp = tid / A_UPP + qi * (NTW / A_UPP);
@@ -328,7 +315,6 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
 #pragma unroll
             for (int e = 0; e < EPU; ++e) dyt[(dy_cu * EPU + ((e + dy_cu) & (EPU - 1))) * DS + pix] = ov[e];
         }
-        WTS(2);
 #pragma unroll
         for (int i = 0; i < A_PER_T; ++i) {
             int ih, iw, off;
@@ -360,9 +346,7 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
         const int tw_i = t % p.tiles_w; t /= p.tiles_w;
         const int th_i = t % p.tiles_h; const int n = t / p.tiles_h;
         const int h0 = th_i * THW, w0 = tw_i * TWW;
-        WTS(0);
         __syncthreads();                         // previous tile's fragment reads are done
-        WTS(1);
         if (fast) {
             commit_tile(pt);
         } else {
@@ -440,9 +424,7 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
             }
         }
         }
-        WTS(3);
         __syncthreads();
-        WTS(4);
         if (fast) {                              // next tile's loads fly during this tile's MFMAs (a harmless re-read at the end)
             const int npt = (pt + p.nsplit < p.n_pt) ? pt + p.nsplit : pt;
             issue(npt);
@@ -482,10 +464,6 @@ __global__ __launch_bounds__(WSplit<KS>::NTW) void conv_wgrad_kernel(WgradParams
         };
         if (SPLIT == 1 || half == 0) mfma_phase(std::integral_constant<int, 0>{});
         else mfma_phase(std::integral_constant<int, SPLIT - 1>{});
-        WTS(5);
-#ifdef MAS_TIMELINE
-        ++tl_iter;
-#endif
     }
 
     // ---- commit: dW[co][kh][kw][ci], fp32 atomics or this split's slab --------------------------------
@@ -720,10 +698,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_tr_kernel(WgradParams p) {
     if (do_bias) commit_bias<NT, 8, 16>(smem, tid, dy_cu, bsum, p.dbias + (p.slabs ? (size_t)split * p.Cout : 0) + co0, p.Cout - co0, p.slabs);
 }
 
-#ifndef MAS_WGRAD_TR_BCI
-#define MAS_WGRAD_TR_BCI 64
-#endif
-template <int KS, int BCI_ = MAS_WGRAD_TR_BCI>
+template <int KS, int BCI_ = 64>
 int launch_tr(WgradParams p, hipStream_t s, int* splits_only) {
     using G = TrGeo<KS, BCI_>;
     auto kern = conv_wgrad_tr_kernel<KS, BCI_>;
@@ -841,9 +816,6 @@ extern "C" int mas_conv_wgrad(const MasConvDesc* d, const void* x, const float* 
         if (rc != 0) return rc < 0 ? rc : MAS_OK;
     }
     WgradParams p = general_params(d, x, scale_shift, dy, dw, dbias, 0);
-#ifdef MAS_TIMELINE          // s_memtime timeline builds only (tools/build_variant.sh tl -DMAS_TIMELINE)
-    if (const char* e = getenv("MAS_DBG_PTR")) p.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
-#endif
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (d->in_dtype == MAS_BF16) return launch_t<bf16_t>(p, d->ks, d->stride, s);
     if (d->in_dtype == MAS_F32) return launch_t<float>(p, d->ks, d->stride, s);

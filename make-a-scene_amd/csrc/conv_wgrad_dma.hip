@@ -31,7 +31,7 @@ struct DmaWgradParams {
     int N, H, W, Cin, Ho, Wo, Cout;
     int Hl, Wl, pad_top, pad_left, act, upsample;
     int tiles_h, tiles_w, n_pt, n_co_t, n_ci_t, nsplit;
-    unsigned long long* dbg;                       // -DD_TIMELINE builds only
+    unsigned long long* dbg;                       // always null: nothing reads it (kept: the kernel argument layout is unchanged)
     // KS = 2 (the sub-pixel form of Upsample + conv, see below): dy is the HIGH-resolution tensor walked as four phase images
     int dy_px, dy_row, dy_ph_px, dy_ph_row;        // bytes between low-resolution neighbours of a phase image; offset of phase column / row
     unsigned dy_img, dy_bytes;                     // bytes of one image of dy / of the whole tensor
@@ -42,13 +42,6 @@ constexpr int D_DY = 128 * 256;                // one dY tile: 128 pixels x 128 
 constexpr int D_XP = 23 * 1024;                // one patch: 180 pixels x 128 B -> 23 DMA pieces of 8 pixels
 constexpr int D_SS = 2 * 1024;                 // scale/shift rows of two tiles (64 channels x 2 floats = 512 B, in a 1 KiB DMA piece)
 constexpr int D_LDS = 2 * D_DY + 3 * D_XP + D_SS;     // 138240 B
-
-__device__ __forceinline__ bf16x8 d_tr_frag(const unsigned char* a0, const unsigned char* a1) {
-#ifdef D_ABL_NOREAD     // timing experiment only: fragments without LDS reads
-    { const unsigned k = (unsigned)(size_t)a0 | 0x3f803f80u; u32x4 q = {k, k, k, k}; return *reinterpret_cast<const bf16x8*>(&q); }
-#endif
-    return tr_frag(a0, a1);
-}
 
 #define D_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
@@ -172,9 +165,6 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
             const bool ok = (ho < p.Ho) && (wo < p.Wo);
             vo = ok ? (int)((((size_t)(c.n * p.Ho + ho) * p.Wo + wo) * p.Cout + co0 + blk * 32 + (lane & 3) * 8) * 2) : OOB_VOFFSET;
         }
-#ifdef D_ABL_NODMA
-        if (p.N != -12345) return;
-#endif
         dma16(rs_dy, __builtin_amdgcn_readfirstlane(lds0 + buf * D_DY + piece * 1024), vo);
     };
     // patch: wave w moves pieces w, w + NW, .. below 23 (8 pixels x 128 B each); lane -> patch pixel 8 piece + (lane >> 3), physical
@@ -187,9 +177,6 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
         if (wave + NW * k >= 23) return;
         int vo = xL[k] + c.ux;                      // (dead lanes: the marker stays out of range after the add)
         if (!c.fx) vo = x_inb(k, c) ? vo : OOB_VOFFSET;   // edge tile (uniform branch): halo pixels outside the image read as zeros
-#ifdef D_ABL_NODMA
-        if (p.N != -12345) return;
-#endif
         dma16(rs_x, __builtin_amdgcn_readfirstlane(lds0 + 2 * D_DY + buf * D_XP + (wave + NW * k) * 1024), vo);
     };
     // (scale, shift) of the 64 channels of a tile's image: 512 B, lanes 0..31 of one DMA piece, ONE copy per work-group (wave 0 moves
@@ -264,13 +251,6 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
     asm volatile("" ::: "memory");
     cA = cN;                                       // inside iteration j: cA = tile j+1 (fetched in steps 0..7), cN = tile j+2 (steps 7..9)
 
-#ifdef D_TIMELINE      // s_memtime stamps of iterations 40 and 41 of work-group 100: [0] arrive, [1] released, [2 + s] MFMAs of step s issued
-    unsigned long long tsv[12];
-#define DTS(k) asm volatile("s_memtime %0" : "=s"(tsv[k]) :: "memory")
-#else
-#define DTS(k)
-#endif
-
     // ---- schedule.  A tile is 10 steps (patch rows); the taps of this wave are [LO, HI).  SPLIT = 1 prefetches the patch fragments
     // of step s+1 during step s (double-buffered registers); SPLIT = 2 reads them at the start of their step (the SIMD's other three
     // waves cover the latency).  The ONE work-group barrier per tile sits between steps 7 and 8 -- not at the tile boundary -- so the
@@ -284,11 +264,7 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
     auto run = [&](auto HALF_T) {
         constexpr int HALF = decltype(HALF_T)::v;
         constexpr int LO = SPLIT == 1 ? 0 : (HALF ? 5 : 0), HI = SPLIT == 1 ? KS * KS : (HALF ? 9 : 5);
-#ifdef D_NO_ACT_PREFETCH   // A/B builds: round 2's rule (the prologue variant spent those 12 registers on address temporaries)
-        constexpr bool PREFETCH = SPLIT == 1 && !ACT;
-#else
         constexpr bool PREFETCH = SPLIT == 1;             // (round 3: the leaner address code freed the 12 registers for the prologue variant too)
-#endif
 #pragma unroll
         for (int t = 0; t < HI - LO; ++t)
 #pragma unroll
@@ -310,33 +286,11 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
         // swizzled offset; a read is then `base register + compile-time offset` (row * 2304, +512 for the second half) -- round 2
         // formed every address with two VALU adds (120 per tile).  The bases move to the next buffer of the ring once per tile.
         auto load_b = [&](int pr) {                               // -> bf[PREFETCH ? pr & 1 : 0], from the buffer bxo points at
-#ifdef D_KW_REUSE      // experiment builds only -- measured SLOWER (0.594 vs 0.584 ms at 128->128 @256^2; step 63.52 vs 63.28 ms, one box):
-            if constexpr (SPLIT == 1) {
-                // The three kw fragments of a patch row are windows of the SAME 10 pixels (8 g + kw .. 8 g + kw + 7): three transpose reads
-                // (pixels +0..3, +4..7, +8..11 of the lane's channel; a dword = two pixels) instead of six -- kw = 2 is the window shifted
-                // by one dword, kw = 1 by half a dword (four v_alignbit).  80 -> 50 LDS reads per tile, but +70 VALU: the odd-register
-                // window of kw = 2 is not a legal MFMA operand (tuples are even-aligned), so it is copied, and an issued VALU instruction
-                // costs this kernel as much as an issued LDS read (R2.2's cost model).  (SPLIT 1: a step needs all three kw or none.)
-                if (!kw_needed(pr, 0)) return;
-                const unsigned char* b0 = smem + bxo[0][pr & 1] + pr * (D_PW * 128);
-                const s16x4 r0 = lds_read_tr16(b0);
-                const s16x4 r1 = lds_read_tr16(b0 + 4 * 128);
-                const s16x4 r2 = lds_read_tr16(b0 + 8 * 128);
-                const u32x2 a = *reinterpret_cast<const u32x2*>(&r0), b = *reinterpret_cast<const u32x2*>(&r1), c = *reinterpret_cast<const u32x2*>(&r2);
-                const u32x4 f0 = {a[0], a[1], b[0], b[1]}, f2 = {a[1], b[0], b[1], c[0]};
-                const u32x4 f1 = {__builtin_amdgcn_alignbit(a[1], a[0], 16), __builtin_amdgcn_alignbit(b[0], a[1], 16),
-                                  __builtin_amdgcn_alignbit(b[1], b[0], 16), __builtin_amdgcn_alignbit(c[0], b[1], 16)};
-                bf[PREFETCH ? (pr & 1) : 0][0] = *reinterpret_cast<const bf16x8*>(&f0);
-                bf[PREFETCH ? (pr & 1) : 0][1] = *reinterpret_cast<const bf16x8*>(&f1);
-                bf[PREFETCH ? (pr & 1) : 0][2] = *reinterpret_cast<const bf16x8*>(&f2);
-                return;
-            }
-#endif
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 if (!kw_needed(pr, kw)) continue;
                 const unsigned char* b0 = smem + bxo[kw][pr & 1] + pr * (D_PW * 128);                  // patch pixels (pr, kw + 8g + j)
-                bf[PREFETCH ? (pr & 1) : 0][kw] = d_tr_frag(b0, b0 + 4 * 128);
+                bf[PREFETCH ? (pr & 1) : 0][kw] = tr_frag(b0, b0 + 4 * 128);
             }
         };
         auto advance_bases = [&]() {                              // ring of three patch buffers
@@ -347,7 +301,7 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
         };
         auto load_a = [&](const unsigned char* dys, int pr) {     // -> aw[pr % 3]
             const unsigned char* a0 = dys + pr * (16 * 256) + a_lane;                                 // dY pixels (pr, 8g + j)
-            aw[pr % 3] = d_tr_frag(a0, a0 + 4 * 256);
+            aw[pr % 3] = tr_frag(a0, a0 + 4 * 256);
         };
         auto mfma_kh = [&](int pr, int kh) {
             const int rr = pr - kh;
@@ -356,36 +310,21 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
             for (int kw = 0; kw < KS; ++kw) {
                 const int t = kh * KS + kw;
                 if (t < LO || t >= HI) continue;
-#ifdef D_ABL_NOMFMA     // timing experiment only
-                acc[t - LO][0] += (float)aw[rr % 3][0] + (float)bf[PREFETCH ? (pr & 1) : 0][kw][0];
-#else
                 mma16(acc[t - LO], aw[rr % 3], bf[PREFETCH ? (pr & 1) : 0][kw]);
-#endif
             }
         };
         if constexpr (PREFETCH) load_b(0);
         load_a(dyb, 0);
         for (int j = 0; j < n_mine; ++j) {
-#ifdef D_TIMELINE
-            if (j >= 41 && j < 43 && blockIdx.x == 100 && lane == 0 && p.dbg) {
-#pragma unroll
-                for (int k = 0; k < 12; ++k) p.dbg[((j - 41) * NW + wave) * 16 + k] = tsv[k];
-            }
-            asm volatile("" ::: "memory");
-#endif
             const unsigned char* dys = dyb + (j & 1) * D_DY;
             const unsigned char* xs = xb + (j % 3) * D_XP;
             const int xn = (j + 1) % 3, dn = (j + 1) & 1;         // buffers of tile j+1
 #pragma unroll
             for (int pr = 0; pr < D_PH; ++pr) {
                 if (pr == 8) {                                    // ---- the barrier: tile j+1 complete and visible, dY(j) dead
-                    DTS(0);
                     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#ifndef D_ABL_NOBAR
                     __builtin_amdgcn_s_barrier();
-#endif
                     asm volatile("" ::: "memory");
-                    DTS(1);
                 }
                 if constexpr (PREFETCH) {
                     if (pr + 1 < D_PH) load_b(pr + 1);
@@ -432,11 +371,6 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
                 else if (pr == D_PH - 1) load_a(dyb + dn * D_DY, 0);   // step 9: dY row 0 of the next tile (slot 0: row 6 is done)
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_kh(pr, 0);
-#ifdef D_TIMELINE
-                __builtin_amdgcn_sched_barrier(0);
-                DTS(2 + pr);
-                if (pr == D_PH - 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             cA = cN;
@@ -444,14 +378,6 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
         D_WAIT(0);                                                // the look-ahead DMA of tiles past the end must land before the LDS is reused / the block exits
 
         const int ci = ci0 + wci + l31;
-#ifdef D_ABL_NOATOM     // timing experiment only
-        if (p.N != -12345) {
-            float t = 0.0f;
-            for (int k = 0; k < HI - LO; ++k) for (int r = 0; r < 16; ++r) t += acc[k][r];
-            if (t == 123.456f) p.dw[0] = t;
-            return;
-        }
-#endif
         if (p.part) {
             // this work-group's own slab of the partial table: plain coalesced stores (a half-wave writes 128 consecutive bytes).  The
             // fp32 atomics they replace cost 45-60 us per launch on every shape but the largest (18.9 M read-modify-writes at the L2:
@@ -475,9 +401,6 @@ __global__ __launch_bounds__(512 * SPLIT) void conv_wgrad_dma_kernel(DmaWgradPar
         }
     };
     if (SPLIT == 1 || half == 0) run(d_ic<0>{}); else run(d_ic<1>{});
-#ifdef D_ABL_NOATOM
-    if (p.N != -12345) return;
-#endif
     if (do_bias) {                                 // thread (tid & 15) = channel unit, (tid >> 4) = pixel phase: fixed-order sum over the phases
         __syncthreads();
         float* red = reinterpret_cast<float*>(smem);               // [NT / 16][128]
@@ -549,14 +472,7 @@ static bool dma_setup(const MasConvDesc* d, DmaWgradParams& p) {
 }
 
 static int dma_launch(DmaWgradParams& p, hipStream_t s) {
-#ifdef D_TIMELINE
-    if (const char* e = getenv("MAS_DBG_PTR")) p.dbg = reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0));
-#endif
     const bool act = p.act != MAS_ACT_NONE;
-#ifdef D_SPLIT2         // experiment builds only: the 16-wave tap-split variant does not fit the 128-register cap (88 spilled registers)
-    static const int wsplit = mas_env_int("MAS_WGRAD_SPLIT", 2);
-    if (wsplit == 2) return act ? launch_dma<true, 2>(p, s) : launch_dma<false, 2>(p, s);
-#endif
     return act ? launch_dma<true, 1>(p, s) : launch_dma<false, 1>(p, s);
 }
 

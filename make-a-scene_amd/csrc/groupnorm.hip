@@ -16,18 +16,10 @@ constexpr int NT = 256;
 // fit the 256 MiB Infinity Cache, and written through the default policy they evict what the next pass could still have hit (x and
 // da, left there by gn_bwd_partial in the reverse block order).  Measured (profiles/r03_gn_streaming.txt): gn_bwd 128 ch @256^2
 // 0.543 -> 0.528 ms, with 4096 apply blocks 0.479; @128^2 0.125 -> 0.111.  Non-temporal LOADS are a wash: gn_bwd_partial alone gains
-// 19 % (207 -> 169 us = 6.35 TB/s) and gn_bwd_apply loses the same microseconds again (its operands were not left in the cache) --
-// -DGN_NT_LD keeps the experiment; -DGN_NO_NT_ST restores default-policy stores.
-#ifdef GN_NT_LD
-#define GN_LD(p) __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p))
-#else
+// 19 % (207 -> 169 us = 6.35 TB/s) and gn_bwd_apply loses the same microseconds again (its operands were not left in the cache), so loads
+// keep the default policy.
 #define GN_LD(p) (*reinterpret_cast<const u32x4*>(p))
-#endif
-#ifndef GN_NO_NT_ST
 #define GN_ST(p, v) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p))
-#else
-#define GN_ST(p, v) (*reinterpret_cast<u32x4*>(p) = (v))
-#endif
 constexpr int MAX_SPLIT = 64;
 
 // ---------------------------------------------------------------------------------------

@@ -17,22 +17,14 @@
 //                    dQ_blk = apply(dS, K)
 //   backward, dK/dV: the same with the roles of queries and keys swapped (block = 32 KEYS, columns = queries, lse / delta indexed
 //                    by column): dV_blk = apply(P^T, dO), dK_blk = apply(dS^T, Q).
-// With 256 work-groups of 4 waves the kernels are bound by exposed memory round trips (1.2 us each, measured with -DSP_TRACE), not
-// by MFMA (2 us per work-group) or bandwidth: round 4 keeps 16-32 KiB per wave in flight (prod: next 256-channel step prefetched,
+// With 256 work-groups of 4 waves the kernels are bound by exposed memory round trips (1.2 us each, measured with wall-clock stamps at
+// the phase boundaries), not by MFMA (2 us per work-group) or bandwidth: round 4 keeps 16-32 KiB per wave in flight (prod: next 256-channel step prefetched,
 // apply: M tiles four ahead and issued before the softmax) and does the softmax / dS arithmetic on the accumulators instead of
 // bouncing fp32 scores through LDS row by row: forward 58 -> 23 us, backward 72 + 95 -> 31 + 43 us (profiles/r04_spatial_attn.txt).
 // No atomics: every output element is written exactly once (deterministic).
 #include "mas_lds.h"
 #include <math.h>
 
-namespace {
-// -DSP_TRACE (tools/build_file_variant.sh, never the shipped build): wave 0 of one work-group stamps the 100 MHz wall clock at the phase
-// boundaries of the forward kernel; tools/kbench.py sp_attn prints the differences.
-#ifdef SP_TRACE
-__device__ long long g_sp_trace[32];
-#define SP_T(i) do { if (blockIdx.x == 9 && threadIdx.x == 0) g_sp_trace[i] = wall_clock64(); } while (0)
-#endif
-}  // namespace
 #include "spatial_attn_core.h"
 
 namespace {
@@ -69,13 +61,10 @@ __global__ __launch_bounds__(SNT) void spatial_attn_fwd_kernel(SpParams p) {
     const int rot = blk % nqb;
     int mt[TPW];
     sp_tiles(mt, wave, p.S, rot);
-    SP_T(0);
     f32x16 sc[TPW];
     sp_prod(sc, mt, rot, smem + L.o_x, L.RX, Q, ld, q0, K, ld, p.S, p.C, tid);
-    SP_T(1);
     u32x4 pf[4][UPT];
     sp_apply_issue(pf, V, ld, p.S, p.C, rot, tid);                 // four V tiles travel while the softmax runs
-    SP_T(2);
     // softmax over keys, in the accumulators: lane (g, l31) holds 32 of query l31's scores
     float mx = -1e30f;
 #pragma unroll
@@ -101,12 +90,9 @@ __global__ __launch_bounds__(SNT) void spatial_attn_fwd_kernel(SpParams p) {
         for (int r = 0; r < 16; ++r) sc[ti][r] *= inv;
     sp_put_rows(smem + L.o_p, L.SP, sc, p.S, mt, g, l31);
     if (wave == 0 && g == 0 && q0 + l31 < p.S && p.lse) p.lse[(size_t)n * p.S + q0 + l31] = mx + __logf(sum);
-    SP_T(3);
     f32x16 acc[CPW];
     sp_apply_run(acc, pf, smem + L.o_p, L.SP, smem + L.o_m0, smem + L.o_m1, L.RM, V, ld, p.S, p.C, rot, tid);
-    SP_T(4);
     sp_store(acc, p.out + (size_t)n * p.S * p.C, p.C, q0, p.S, p.C, tid);
-    SP_T(5);
 }
 
 // ---- backward, shared body.  KEYS = false: block = 32 queries -> dQ (and delta); KEYS = true: block = 32 keys -> dK, dV ---------
@@ -190,10 +176,6 @@ int sp_check(const char* what, const void* a, const void* b, int dtype, int N, i
 }
 
 }  // namespace
-
-#ifdef SP_TRACE
-extern "C" int mas_sp_trace(long long* out16) { return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_sp_trace), sizeof(long long) * 32); }
-#endif
 
 extern "C" int mas_spatial_attn_fwd(const void* qkv, void* out, float* lse, int dtype, int N, int S, int C, void* stream) {
     MAS_ENTER();

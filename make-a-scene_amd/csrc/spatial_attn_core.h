@@ -6,21 +6,14 @@
 #include "mas_lds.h"
 #include <math.h>
 
-#ifndef SP_T
-#define SP_T(i) do { } while (0)              // phase stamps: spatial_attn.hip defines them under -DSP_TRACE
-#endif
-
 namespace {
 
-#ifndef SP_NW
-#define SP_NW 8                                 // waves per work-group: 8 (two per SIMD; shipped) or 4 (-DSP_NW=4: the A/B of profiles/r04_spatial_attn.txt, section 8)
-#endif
-constexpr int NW = SP_NW, SNT = 64 * NW;
+constexpr int NW = 8;                           // waves per work-group: two per SIMD (the A/B against 4: profiles/r04_spatial_attn.txt, section 8)
+constexpr int SNT = 64 * NW;
 constexpr int S_MAX = 256, C_MAX = 512;
-constexpr int TPW = S_MAX / 32 / NW;            // 32-column score tiles per wave: 2 | 1
-constexpr int CPW = C_MAX / 32 / NW;            // 32-channel output tiles per wave: 4 | 2
-constexpr int UPT = 32 * (C_MAX / 8) / SNT;     // 16-byte units of a 32-row tile per thread: 8 | 4
-static_assert(NW == 4 || NW == 8, "4 or 8 waves");
+constexpr int TPW = S_MAX / 32 / NW;            // 32-column score tiles per wave
+constexpr int CPW = C_MAX / 32 / NW;            // 32-channel output tiles per wave
+constexpr int UPT = 32 * (C_MAX / 8) / SNT;     // 16-byte units of a 32-row tile per thread
 
 struct SpParams {
     const bf16_t* qkv; const bf16_t* o; const bf16_t* dout; bf16_t* out; bf16_t* dqkv; float* lse; float* delta;
@@ -91,7 +84,7 @@ __device__ __forceinline__ int sp_col(const int (&mt)[TPW], int ti, int r, int g
 
 // sc[ti][r] = sum_c X[r0 + n][c] * Y[m][c]: the 32 block rows are staged into xs (LDS) by this call, the rows of Y stream straight
 // from global memory as MFMA A fragments (lane = m), B operand (lane = n) from LDS; the result stays in the accumulators.
-// At one wave per SIMD nothing hides anything, so the loop is written for the two things that were found to cost (SP_TRACE + the ISA):
+// At one wave per SIMD nothing hides anything, so the loop is written for the two things that were found to cost (phase time stamps + the ISA):
 // * memory-level parallelism: a step is 128 channels of one column tile (8 fragments, 8 KiB per wave); a ring of four fragment
 //   buffers keeps THREE steps in flight behind the one being multiplied, and the first three are issued before the block rows are
 //   committed to LDS, so that round trip overlaps too;
@@ -123,14 +116,12 @@ __device__ __forceinline__ void sp_prod_t(f32x16 (&sc)[TPW], const int (&mt)[TPW
     };
 #pragma unroll
     for (int k = 0; k < RING - 1; ++k) fetch(a[k], k);
-    SP_T(16);
     if constexpr (STAGE) {
         __syncthreads();                          // whoever read xs before is done
         sp_rows_commit(xr_, xs, RX, r0, Sx, mp);
         sp_rows_zero_pad(xs, RX, C, tid);
         __syncthreads();
     }
-    SP_T(17);
 #pragma unroll
     for (int ti = 0; ti < TPW; ++ti)
 #pragma unroll
@@ -151,7 +142,6 @@ __device__ __forceinline__ void sp_prod_t(f32x16 (&sc)[TPW], const int (&mt)[TPW
                 for (int u = 0; u < UB; ++u) mma16(sc[k >> 2], a[k % RING][u0 + u], b[u]);
             }
         }
-        SP_T(18 + k);
     }
 }
 __device__ __forceinline__ void sp_prod(f32x16 (&sc)[TPW], const int (&mt)[TPW], int rot, unsigned char* xs, int RX, const bf16_t* X, int ldx,
@@ -249,7 +239,6 @@ __device__ __forceinline__ void sp_apply_run_t(f32x16 (&acc)[CPW], u32x4 (&pf)[D
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int i = 0; i < CPW; ++i) mma16(acc[i], aq[ks][i], bq[ks]);
-            SP_T(6 + t);
         }
     }
     __syncthreads();                              // the last tile's reads are done: the caller may reuse both buffers

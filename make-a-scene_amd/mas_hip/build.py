@@ -14,8 +14,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # VALU beside MFMAs is slower on gfx950 -- measured -2 ... -5 % on the forward kernel, profiles/r03_attn_v2.txt)
 # conv3x3_wide.hip: the same for the epilogue's bias / residual adds (-2 % on the launch, gpu_r3_17.sh; the stream kernel measured 5 % SLOWER
 # without packing and keeps it)
-PER_FILE_FLAGS = {"attention.hip": ["-DFA_SCALAR_SOFTMAX", "-fno-slp-vectorize"], "conv3x3_wide.hip": ["-fno-slp-vectorize"],
+PER_FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"], "conv3x3_wide.hip": ["-fno-slp-vectorize"],
                   "conv_up2.hip": ["-fno-slp-vectorize"]}
+
+
+def flags_for(basename):
+    """every compile flag of one csrc file (the variant build scripts ask for them: `python build.py --flags attention.hip`)"""
+    return FLAGS + PER_FILE_FLAGS.get(basename, [])
 
 
 def _hipcc():
@@ -54,7 +59,7 @@ def build(force=False, verbose=True):
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_t):
             continue
-        cmd = [hipcc] + FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
+        cmd = [hipcc] + flags_for(os.path.basename(src)) + ["-c", src, "-o", obj]
         if verbose:
             print("[mas_hip.build]", " ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
@@ -75,5 +80,8 @@ def build(force=False, verbose=True):
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
-    print(LIB)
+    if "--flags" in sys.argv:
+        print(" ".join(flags_for(sys.argv[sys.argv.index("--flags") + 1])))
+    else:
+        build(force="--force" in sys.argv)
+        print(LIB)

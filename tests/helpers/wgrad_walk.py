@@ -40,7 +40,7 @@ def general_thw(ks, stride):
 
 
 def general_bci(kernel, ks):
-    """input channels per work-group: launch_tr<4, 32>, launch_tr<2, 64>, launch_tr<1|3> MAS_WGRAD_TR_BCI = 64; launch MAS_WGRAD_BCI = 32"""
+    """input channels per work-group: launch_tr<4, 32>, launch_tr<2, 64>, launch_tr<1|3> (default BCI_) = 64; launch_t (BCI) = 32"""
     if kernel == "conv_wgrad_tr":
         return 32 if ks == 4 else 64
     return 32

@@ -1,12 +1,10 @@
 #!/usr/bin/env python3
 """Energy budget of the convolution kernels (VERDICT r4 "next" #1): shader clock and package power over the steady state of >= 4 s
 loops of (a) the matrix pipe alone, fed constant / random operands from registers / random operands through ds_read_b128 at the
-wide kernel's 0.75 reads per MFMA and at 0.5 (tools/probes/mfma_power.hip), (b) the wide convolution kernel and its ablation builds
-(-DW_ABL_NOPATCH: no activation DMA, -DW_ABL_NOW: no weight DMA, -DW_ABL_NOEPI: no epilogue, all three = MFMAs + fragment reads
-only, -DW_ABL_HALF_A: 0.5 fragment reads per MFMA), on random and on all-zero inputs, (c) the LDS-DMA weight gradient.
+wide kernel's 0.75 reads per MFMA and at 0.5 (tools/probes/mfma_power.hip), (b) the wide convolution kernel on random and on
+all-zero inputs, (c) the LDS-DMA weight gradient.
 Prints one row per load: ms per launch, TFLOP/s, clock, watts, JOULES PER LAUNCH (P x t) and pJ per FLOP.
-    python tools/probes/energy_budget.py [seconds per load, default 5]
-The ablation libraries are looked up under make-a-scene_amd/csrc/build/variants/ (tools/experiments/gpu_r5_1.sh builds them)."""
+    python tools/probes/energy_budget.py [seconds per load, default 5]"""
 import os
 import re
 import subprocess
@@ -77,17 +75,9 @@ def main():
         measure(what, [probe, mode, tile, wg, str(sec)], files, sec - 1.5)
     kb = [sys.executable, os.path.join(ROOT, "tools", "kbench.py")]
     iters = str(int(sec / 0.5e-3))
-    var = os.path.join(ROOT, "make-a-scene_amd", "csrc", "build", "variants")
     conv = kb + ["conv_fwd", "--c", "128", "--hw", "256", "--iters", iters]
     measure("conv3x3_wide 128->128 @256^2 (shipped), random input", conv, files, sec - 1.5)
     measure("conv3x3_wide (shipped), ALL-ZERO input and weights", conv + ["--zero", "1"], files, sec - 1.5)
-    for v, what in (("wabl_nopatch", "wide -DW_ABL_NOPATCH (no activation DMA)"), ("wabl_now", "wide -DW_ABL_NOW (no weight DMA)"),
-                    ("wabl_noepi", "wide -DW_ABL_NOEPI (no epilogue / stores)"), ("wabl_mfma", "wide, all three: MFMAs + fragment reads only"),
-                    ("wabl_halfa", "wide -DW_ABL_HALF_A (0.5 fragment reads per MFMA)"),
-                    ("wabl_mfma_halfa", "wide, MFMAs + HALF the weight fragment reads only")):
-        so = os.path.join(var, v + ".so")
-        if os.path.exists(so):
-            measure(what, conv, files, sec - 1.5, env={"MAS_HIP_LIB": so})
     measure("conv3x3_wide <res,stats> (the forward's variant)", conv + ["--res", "1", "--stats", "1"], files, sec - 1.5)
     measure("conv_wgrad_dma 128->128 @256^2", kb + ["wgrad", "--c", "128", "--hw", "256", "--iters", iters], files, sec - 1.5)
     measure("gn_act (HBM-bound) 128 ch @256^2", kb + ["gn_act", "--c", "128", "--hw", "256", "--iters", str(int(sec / 0.2e-3))], files, sec - 1.5)

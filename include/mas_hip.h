@@ -845,6 +845,45 @@ int mas_obj_finalize(const float* partial, const MasObjPlan* p, float* out, void
 int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPlan* p, int level, int C, int dtype, const float* dout, void* seed,
                      void* stream);
 
+/* (Additions inside ABI v10.)  The same passes on an atlas of FIXED capacity, so that launch arguments, grids and every shape depend on the
+ * atlas geometry alone (a captured graph replays them; the host rewrites the table before each replay).  The geometry comes by value
+ * with every call -- max_cells, n_images, n_canvas, H, W (H and W multiples of 16) -- and everything about the boxes is read from
+ * table_dev, mas_obj_atlas_ints(...) int32 on the device with fixed strides:
+ *     header [MAS_OBJ_ATLAS_HEADER]: {n_cells, max_cells, n_images, n_canvas, H, W, 0, 0}
+ *     cells [max_cells] (MasObjCell, the first n_cells used) | img_cell0 [n_images + 1] | blk0 [5][max_cells + 1] (row l valid up to
+ *     blk0[l][n_cells]) | tiles [n_canvas][H / 16][W / 16]
+ *   n_cells and the blk0 stride (max_cells + 1) are the table's; a header with n_cells outside [0, max_cells] makes every work-group of
+ *   every kernel here return without reading or writing anything else.  The kernel bodies are mas_obj_*'s own: for the same cells on the
+ *   same canvas the values are theirs bit for bit.  (The ReLU backward takes no table: mas_obj_relu_bwd.)
+ *   mas_obj_atlas_ints    : the table's length in int32 (MAS_EINVAL < 0 for a geometry the library refuses).
+ *   mas_obj_head_grid_dev : G_l = ceil(n_canvas (H >> l)(W >> l) / MAS_OBJ_HEAD_PIX(C_l)) + max_cells, C = 64, 128, 256, 512, 512: the
+ *                           head's grid at level l.  It bounds blk0[l][n_cells] for every table: the cells' level-l rectangles are
+ *                           disjoint and inside the canvases, and each cell rounds up to whole blocks once.
+ *   mas_obj_canvas_fwd_dev, mas_obj_canvas_bwd_dev, mas_obj_relu_fwd_dev, mas_obj_pool_fwd_dev, mas_obj_pool_bwd_dev: as named.
+ *   mas_obj_head_fwd_dev  : level l on G_l blocks; block j < blk0[l][n_cells] writes partial[off_l + j], off_l = G_0 + .. + G_(l-1)
+ *                           (partial: sum of the five G_l floats); the other blocks return.  C is the level's.
+ *   mas_obj_finalize_dev  : out [1 + max_cells] written in full: the loss, the n_cells crop values, zeros.  n_cells == 0: all zeros.
+ *   mas_obj_head_bwd_dev  : dout [1 + max_cells]; seed written in full (all zeros for an empty table).                              */
+#define MAS_OBJ_ATLAS_HEADER 8
+int mas_obj_atlas_ints(int max_cells, int n_images, int n_canvas, int H, int W);
+int mas_obj_head_grid_dev(int level, int max_cells, int n_canvas, int H, int W);
+int mas_obj_canvas_fwd_dev(const MasFaceImage* img, const MasFaceImage* rec, const int32_t* table_dev, int max_cells, int n_images,
+                           int n_canvas, int H, int W, const float* shift, const float* scale, void* canvas, int dtype, void* stream);
+int mas_obj_canvas_bwd_dev(const void* dcanvas, int dtype, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W,
+                           const float* scale, const MasFaceImage* drec, void* stream);
+int mas_obj_relu_fwd_dev(void* y, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W, int level, int N, int C,
+                         int dtype, void* stream);
+int mas_obj_pool_fwd_dev(const void* x, void* y, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W, int level,
+                         int N, int C, int dtype, void* stream);
+int mas_obj_pool_bwd_dev(const void* a, const void* seed, const void* dz, void* dy, const int32_t* table_dev, int max_cells, int n_images,
+                         int n_canvas, int H, int W, int level, int N, int C, int dtype, void* stream);
+int mas_obj_head_fwd_dev(const void* feat, const float* w, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W,
+                         int level, int dtype, float* partial, void* stream);
+int mas_obj_finalize_dev(const float* partial, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W, float* out,
+                         void* stream);
+int mas_obj_head_bwd_dev(const void* feat, const float* w, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W,
+                         int level, int dtype, const float* dout, void* seed, void* stream);
+
 /* -------------------------------------------------------------------------------------------
  * Whole-image LPIPS-VGG16 (lpips.hip; mas_hip/lpips.py; losses.lpips.hip_path).  Additions inside ABI 10.  Everything of
  * losses/lpips.py:LPIPS.forward that is not one of the thirteen convolutions (those go through mas_conv_fwd), on plain NHWC maps:

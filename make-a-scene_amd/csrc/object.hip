@@ -39,13 +39,43 @@ __device__ __forceinline__ int cell_at(const MasObjPlan& p, int n, int y, int x,
     return (cy >= 0 && cy < (c.h >> l) && cx >= 0 && cx < (c.w >> l)) ? t : -1;
 }
 
+// What a kernel is told about the atlas -- every kernel body below is written once, over either:
+//   ListTab: the plan of one call, as the host made it: n_cells by value, blk0 rows of n_cells + 1, a grid cut to the boxes;
+//   DevTab : a table of FIXED capacity that the host rewrites between calls (mas_obj_*_dev): n_cells is read from the table's header, blk0
+//     rows are max_cells + 1 apart, the head runs on a grid that bounds every table, partial has fixed per-level offsets, and a header
+//     outside [0, max_cells] makes every work-group return.  Its p holds the pointers into the table and the canvas geometry.
+struct ListTab {
+    static constexpr bool FIXED_GRID = false;
+    MasObjPlan p;
+    __device__ __forceinline__ bool ok() const { return true; }
+    __device__ __forceinline__ int n_cells() const { return p.n_cells; }
+    __device__ __forceinline__ int blk_stride() const { return p.n_cells + 1; }
+    __device__ __forceinline__ int out_cells() const { return p.n_cells; }
+    __device__ __forceinline__ int part_off(int) const { return 0; }
+};
+
+struct DevTab {
+    static constexpr bool FIXED_GRID = true;
+    MasObjPlan p;                              // (p.n_cells is not used: the table's header says it)
+    const int32_t* header;
+    int max_cells;
+    int off[LEVELS];                           // first partial of every level: the prefix sums of the fixed grids
+    __device__ __forceinline__ bool ok() const { const int n = header[0]; return n >= 0 && n <= max_cells; }
+    __device__ __forceinline__ int n_cells() const { return header[0]; }
+    __device__ __forceinline__ int blk_stride() const { return max_cells + 1; }
+    __device__ __forceinline__ int out_cells() const { return max_cells; }
+    __device__ __forceinline__ int part_off(int l) const { return off[l]; }
+};
+
 __device__ __forceinline__ long long gsize() { return (long long)gridDim.x * NT; }
 __device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * NT + threadIdx.x; }
 
 // one thread per canvas pixel: CP channels
-template <typename T>
-__global__ __launch_bounds__(NT) void canvas_fwd_kernel(MasFaceImage img, MasFaceImage rec, MasObjPlan p, const float* __restrict__ shift,
+template <typename T, typename Tab>
+__global__ __launch_bounds__(NT) void canvas_fwd_kernel(MasFaceImage img, MasFaceImage rec, Tab tab, const float* __restrict__ shift,
                                                         const float* __restrict__ scale, T* __restrict__ out) {
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const long long hw = (long long)p.H * p.W;
     const long long total = 2LL * p.n_canvas * hw;
     const float s0 = shift[0], s1 = shift[1], s2 = shift[2], k0 = scale[0], k1 = scale[1], k2 = scale[2];
@@ -74,9 +104,11 @@ __global__ __launch_bounds__(NT) void canvas_fwd_kernel(MasFaceImage img, MasFac
 }
 
 // one thread per pixel of d rec: the cells of its image in table order
-template <typename TD, typename TR>
-__global__ __launch_bounds__(NT) void canvas_bwd_kernel(const TD* __restrict__ dcan, MasObjPlan p, const float* __restrict__ scale,
+template <typename TD, typename TR, typename Tab>
+__global__ __launch_bounds__(NT) void canvas_bwd_kernel(const TD* __restrict__ dcan, Tab tab, const float* __restrict__ scale,
                                                         MasFaceImage drec) {
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const long long hw = (long long)drec.H * drec.W;
     const long long total = (long long)drec.N * hw;
     const float k[3] = {scale[0], scale[1], scale[2]};
@@ -104,8 +136,10 @@ __global__ __launch_bounds__(NT) void canvas_bwd_kernel(const TD* __restrict__ d
 }
 
 // 8 channels per thread
-template <typename T>
-__global__ __launch_bounds__(NT) void relu_fwd_kernel(T* __restrict__ y, MasObjPlan p, int l, int N, int C) {
+template <typename T, typename Tab>
+__global__ __launch_bounds__(NT) void relu_fwd_kernel(T* __restrict__ y, Tab tab, int l, int N, int C) {
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const int hl = p.H >> l, wl = p.W >> l, c8 = C / 8;
     const long long total = (long long)N * hl * wl * c8;
     for (long long i = gtid(); i < total; i += gsize()) {
@@ -135,8 +169,10 @@ __global__ __launch_bounds__(NT) void relu_bwd_kernel(const T* da, const T* __re
 }
 
 // x at level l -> y at level l + 1; 8 channels of one output pixel per thread
-template <typename T>
-__global__ __launch_bounds__(NT) void pool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, MasObjPlan p, int l, int N, int C) {
+template <typename T, typename Tab>
+__global__ __launch_bounds__(NT) void pool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, Tab tab, int l, int N, int C) {
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const int hi = p.H >> l, wi = p.W >> l, ho = hi >> 1, wo = wi >> 1, c8 = C / 8;
     const long long total = (long long)N * ho * wo * c8;
     for (long long i = gtid(); i < total; i += gsize()) {
@@ -156,9 +192,11 @@ __global__ __launch_bounds__(NT) void pool_fwd_kernel(const T* __restrict__ x, T
 }
 
 // dy at level l (8 channels of one pixel per thread): a > 0 ? seed + routed dz : 0
-template <typename T>
+template <typename T, typename Tab>
 __global__ __launch_bounds__(NT) void pool_bwd_kernel(const T* __restrict__ a, const T* __restrict__ seed, const T* __restrict__ dz,
-                                                      T* __restrict__ dy, MasObjPlan p, int l, int N, int C) {
+                                                      T* __restrict__ dy, Tab tab, int l, int N, int C) {
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const int hi = p.H >> l, wi = p.W >> l, ho = hi >> 1, wo = wi >> 1, c8 = C / 8;
     const long long total = (long long)N * hi * wi * c8;
     for (long long i = gtid(); i < total; i += gsize()) {
@@ -206,14 +244,18 @@ __device__ __forceinline__ float group_sum(float v, int G) {
 }
 
 // per pixel of one cell: the LPIPS head's value; G = C / 8 lanes per pixel, 8 channels each
-template <typename T>
-__global__ __launch_bounds__(NT) void head_fwd_kernel(const T* __restrict__ feat, const float* __restrict__ w, MasObjPlan p, int l, int C,
+template <typename T, typename Tab>
+__global__ __launch_bounds__(NT) void head_fwd_kernel(const T* __restrict__ feat, const float* __restrict__ w, Tab tab, int l, int C,
                                                       float* __restrict__ partial) {
     __shared__ float red[NT];
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const int G = C / 8, NG = NT / G, ppb = HEAD_PASSES * NG;
-    const int* blk = p.blk0 + l * (p.n_cells + 1);
+    const int nc = tab.n_cells();
+    const int* blk = p.blk0 + l * tab.blk_stride();
     const int bid = blockIdx.x;
-    int lo = 0, hi = p.n_cells - 1;                 // the cell k with blk[k] <= bid < blk[k + 1]
+    if (Tab::FIXED_GRID && bid >= blk[nc]) return;  // a block of the fixed grid beyond the table's last one (every one when nc == 0)
+    int lo = 0, hi = nc - 1;                        // the cell k with blk[k] <= bid < blk[k + 1]
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (blk[mid] <= bid) lo = mid; else hi = mid - 1;
@@ -255,18 +297,23 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(const T* __restrict__ feat
     }
 }
 
-__global__ __launch_bounds__(NT) void finalize_kernel(const float* __restrict__ partial, MasObjPlan p, float* __restrict__ out) {
+template <typename Tab>
+__global__ __launch_bounds__(NT) void finalize_kernel(const float* __restrict__ partial, Tab tab, float* __restrict__ out) {
     __shared__ int off[LEVELS];
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
+    const int nc = tab.n_cells(), stride = tab.blk_stride();
     if (threadIdx.x == 0) {
         int o = 0;
-        for (int l = 0; l < LEVELS; ++l) { off[l] = o; o += p.blk0[l * (p.n_cells + 1) + p.n_cells]; }
+        for (int l = 0; l < LEVELS; ++l) { off[l] = Tab::FIXED_GRID ? tab.part_off(l) : o; o += p.blk0[l * stride + nc]; }
     }
     __syncthreads();
-    for (int k = threadIdx.x; k < p.n_cells; k += NT) {
+    for (int k = nc + threadIdx.x; k < tab.out_cells(); k += NT) out[1 + k] = 0.0f;      // (fixed capacity: the unused slots)
+    for (int k = threadIdx.x; k < nc; k += NT) {
         const MasObjCell c = p.cells[k];
         float v = 0.0f;
         for (int l = 0; l < LEVELS; ++l) {
-            const int* blk = p.blk0 + l * (p.n_cells + 1);
+            const int* blk = p.blk0 + l * stride;
             float s = 0.0f;
             for (int j = blk[k]; j < blk[k + 1]; ++j) s += partial[off[l] + j];
             v += s / (float)((c.h >> l) * (c.w >> l));
@@ -287,9 +334,11 @@ __global__ __launch_bounds__(NT) void finalize_kernel(const float* __restrict__ 
 }
 
 // seed = d out / d (rec feature) at level l, every rec-side pixel of the level (0 outside the cells); G lanes per pixel
-template <typename T>
-__global__ __launch_bounds__(NT) void head_bwd_kernel(const T* __restrict__ feat, const float* __restrict__ w, MasObjPlan p, int l, int C,
+template <typename T, typename Tab>
+__global__ __launch_bounds__(NT) void head_bwd_kernel(const T* __restrict__ feat, const float* __restrict__ w, Tab tab, int l, int C,
                                                       const float* __restrict__ dout, T* __restrict__ seed) {
+    if (!tab.ok()) return;
+    const MasObjPlan& p = tab.p;
     const int G = C / 8, NG = NT / G;
     const int hl = p.H >> l, wl = p.W >> l;
     const long long npix = (long long)p.n_canvas * hl * wl;
@@ -352,12 +401,120 @@ int check_img(const MasFaceImage* im, const char* what) {
     return MAS_OK;
 }
 
-int check_map(const MasObjPlan* p, int level, int N, int C, int dtype, int max_level, const char* what) {
-    if (int rc = check_plan(p, what)) return rc;
+int check_level(int level, int N, int C, int dtype, int max_level, const char* what) {
     if (level < 0 || level > max_level || N <= 0 || C <= 0 || C % 8 || !dt_ok(dtype))
         MAS_FAIL(MAS_EINVAL, "%s: level %d, N %d, C %d, dtype %d", what, level, N, C, dtype);
     return MAS_OK;
 }
+
+int check_map(const MasObjPlan* p, int level, int N, int C, int dtype, int max_level, const char* what) {
+    if (int rc = check_plan(p, what)) return rc;
+    return check_level(level, N, C, dtype, max_level, what);
+}
+
+// ---- the fixed-capacity table (mas_obj_*_dev): its geometry comes by value, everything about the boxes is in the table --------------------
+constexpr int HEAD_C[LEVELS] = {64, 128, 256, 512, 512};       // VGG16's channels at the five LPIPS levels
+constexpr int MAX_ATLAS_CELLS = 4096;
+
+struct Atlas { const int32_t* table; int max_cells, n_images, n_canvas, H, W; };
+
+bool atlas_geometry_ok(const Atlas& a) {
+    return a.max_cells >= 1 && a.max_cells <= MAX_ATLAS_CELLS && a.n_images >= 1 && a.n_canvas >= 1 && a.H >= MAS_OBJ_ALIGN && a.W >= MAS_OBJ_ALIGN &&
+           a.H % MAS_OBJ_ALIGN == 0 && a.W % MAS_OBJ_ALIGN == 0 && (long long)a.n_canvas * a.H * a.W <= (1LL << 28) && a.n_images <= (1 << 20);
+}
+
+int check_atlas(const Atlas& a, const char* what) {
+    if (!a.table) MAS_FAIL(MAS_EINVAL, "%s: null atlas table", what);
+    if (!atlas_geometry_ok(a))
+        MAS_FAIL(MAS_EINVAL, "%s: bad atlas (%d cells at most, %d images, %d canvases of %d x %d)", what, a.max_cells, a.n_images, a.n_canvas, a.H, a.W);
+    return MAS_OK;
+}
+
+// the head's grid at level l, whatever the table holds: the cells' level-l rectangles are disjoint and inside the canvases, and every cell
+// rounds its pixels up to whole blocks once
+int head_grid(const Atlas& a, int l) {
+    const long long pix = (long long)a.n_canvas * (a.H >> l) * (a.W >> l);
+    const int ppb = MAS_OBJ_HEAD_PIX(HEAD_C[l]);
+    return (int)((pix + ppb - 1) / ppb) + a.max_cells;
+}
+
+DevTab dev_tab(const Atlas& a) {
+    DevTab t;
+    const int32_t* cells = a.table + MAS_OBJ_ATLAS_HEADER;
+    const int32_t* img0 = cells + 8LL * a.max_cells;
+    const int32_t* blk0 = img0 + a.n_images + 1;
+    t.p.cells = reinterpret_cast<const MasObjCell*>(cells);
+    t.p.img_cell0 = img0;
+    t.p.blk0 = blk0;
+    t.p.tiles = blk0 + LEVELS * (a.max_cells + 1);
+    t.p.n_cells = 0; t.p.n_images = a.n_images; t.p.n_canvas = a.n_canvas; t.p.H = a.H; t.p.W = a.W; t.p.pad_ = 0;
+    t.header = a.table;
+    t.max_cells = a.max_cells;
+    int o = 0;
+    for (int l = 0; l < LEVELS; ++l) { t.off[l] = o; o += head_grid(a, l); }
+    return t;
+}
+
+// ---- the launches, once for both kinds of table ---------------------------------------------------------------------------------------
+template <typename Tab>
+void launch_canvas_fwd(const Tab& t, const MasFaceImage* img, const MasFaceImage* rec, const float* shift, const float* scale, void* canvas, int dtype,
+                       hipStream_t s) {
+    const dim3 grid(grid_for(2LL * t.p.n_canvas * t.p.H * t.p.W));
+    if (dtype == MAS_F32) hipLaunchKernelGGL((canvas_fwd_kernel<float, Tab>), grid, dim3(NT), 0, s, *img, *rec, t, shift, scale, (float*)canvas);
+    else hipLaunchKernelGGL((canvas_fwd_kernel<bf16_t, Tab>), grid, dim3(NT), 0, s, *img, *rec, t, shift, scale, (bf16_t*)canvas);
+}
+
+template <typename Tab>
+void launch_canvas_bwd(const Tab& t, const void* dcanvas, int dtype, const float* scale, const MasFaceImage* drec, hipStream_t s) {
+    const dim3 grid(grid_for((long long)drec->N * drec->H * drec->W));
+    if (dtype == MAS_F32) {
+        if (drec->dtype == MAS_F32) hipLaunchKernelGGL((canvas_bwd_kernel<float, float, Tab>), grid, dim3(NT), 0, s, (const float*)dcanvas, t, scale, *drec);
+        else hipLaunchKernelGGL((canvas_bwd_kernel<float, bf16_t, Tab>), grid, dim3(NT), 0, s, (const float*)dcanvas, t, scale, *drec);
+    } else {
+        if (drec->dtype == MAS_F32) hipLaunchKernelGGL((canvas_bwd_kernel<bf16_t, float, Tab>), grid, dim3(NT), 0, s, (const bf16_t*)dcanvas, t, scale, *drec);
+        else hipLaunchKernelGGL((canvas_bwd_kernel<bf16_t, bf16_t, Tab>), grid, dim3(NT), 0, s, (const bf16_t*)dcanvas, t, scale, *drec);
+    }
+}
+
+template <typename Tab>
+void launch_relu_fwd(const Tab& t, void* y, int level, int N, int C, int dtype, hipStream_t s) {
+    const dim3 grid(grid_for((long long)N * (t.p.H >> level) * (t.p.W >> level) * (C / 8)));
+    if (dtype == MAS_F32) hipLaunchKernelGGL((relu_fwd_kernel<float, Tab>), grid, dim3(NT), 0, s, (float*)y, t, level, N, C);
+    else hipLaunchKernelGGL((relu_fwd_kernel<bf16_t, Tab>), grid, dim3(NT), 0, s, (bf16_t*)y, t, level, N, C);
+}
+
+template <typename Tab>
+void launch_pool_fwd(const Tab& t, const void* x, void* y, int level, int N, int C, int dtype, hipStream_t s) {
+    const dim3 grid(grid_for((long long)N * (t.p.H >> (level + 1)) * (t.p.W >> (level + 1)) * (C / 8)));
+    if (dtype == MAS_F32) hipLaunchKernelGGL((pool_fwd_kernel<float, Tab>), grid, dim3(NT), 0, s, (const float*)x, (float*)y, t, level, N, C);
+    else hipLaunchKernelGGL((pool_fwd_kernel<bf16_t, Tab>), grid, dim3(NT), 0, s, (const bf16_t*)x, (bf16_t*)y, t, level, N, C);
+}
+
+template <typename Tab>
+void launch_pool_bwd(const Tab& t, const void* a, const void* seed, const void* dz, void* dy, int level, int N, int C, int dtype, hipStream_t s) {
+    const dim3 grid(grid_for((long long)N * (t.p.H >> level) * (t.p.W >> level) * (C / 8)));
+    if (dtype == MAS_F32)
+        hipLaunchKernelGGL((pool_bwd_kernel<float, Tab>), grid, dim3(NT), 0, s, (const float*)a, (const float*)seed, (const float*)dz, (float*)dy, t, level, N, C);
+    else
+        hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, Tab>), grid, dim3(NT), 0, s, (const bf16_t*)a, (const bf16_t*)seed, (const bf16_t*)dz, (bf16_t*)dy, t,
+                           level, N, C);
+}
+
+template <typename Tab>
+void launch_head_fwd(const Tab& t, const void* feat, const float* w, int level, int C, int dtype, int n_blocks, float* partial, hipStream_t s) {
+    if (dtype == MAS_F32) hipLaunchKernelGGL((head_fwd_kernel<float, Tab>), dim3(n_blocks), dim3(NT), 0, s, (const float*)feat, w, t, level, C, partial);
+    else hipLaunchKernelGGL((head_fwd_kernel<bf16_t, Tab>), dim3(n_blocks), dim3(NT), 0, s, (const bf16_t*)feat, w, t, level, C, partial);
+}
+
+template <typename Tab>
+void launch_head_bwd(const Tab& t, const void* feat, const float* w, int level, int C, int dtype, const float* dout, void* seed, hipStream_t s) {
+    const long long npix = (long long)t.p.n_canvas * (t.p.H >> level) * (t.p.W >> level);
+    const dim3 grid(grid_for(npix * (C / 8)));
+    if (dtype == MAS_F32) hipLaunchKernelGGL((head_bwd_kernel<float, Tab>), grid, dim3(NT), 0, s, (const float*)feat, w, t, level, C, dout, (float*)seed);
+    else hipLaunchKernelGGL((head_bwd_kernel<bf16_t, Tab>), grid, dim3(NT), 0, s, (const bf16_t*)feat, w, t, level, C, dout, (bf16_t*)seed);
+}
+
+bool head_c_ok(int C) { return C >= 64 && C <= 512 && !(C & (C - 1)); }
 
 }  // namespace
 
@@ -368,10 +525,7 @@ extern "C" int mas_obj_canvas_fwd(const MasFaceImage* img, const MasFaceImage* r
     if (int rc = check_img(rec, "obj_canvas_fwd")) return rc;
     if (int rc = check_plan(p, "obj_canvas_fwd")) return rc;
     if (!shift || !scale || !canvas || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_canvas_fwd: null argument or dtype %d", dtype);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for(2LL * p->n_canvas * p->H * p->W));
-    if (dtype == MAS_F32) hipLaunchKernelGGL(canvas_fwd_kernel<float>, grid, dim3(NT), 0, s, *img, *rec, *p, shift, scale, (float*)canvas);
-    else hipLaunchKernelGGL(canvas_fwd_kernel<bf16_t>, grid, dim3(NT), 0, s, *img, *rec, *p, shift, scale, (bf16_t*)canvas);
+    launch_canvas_fwd(ListTab{*p}, img, rec, shift, scale, canvas, dtype, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_canvas_fwd");
     return MAS_OK;
 }
@@ -381,15 +535,7 @@ extern "C" int mas_obj_canvas_bwd(const void* dcanvas, int dtype, const MasObjPl
     if (int rc = check_img(drec, "obj_canvas_bwd")) return rc;
     if (int rc = check_plan(p, "obj_canvas_bwd")) return rc;
     if (!dcanvas || !scale || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_canvas_bwd: null argument or dtype %d", dtype);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for((long long)drec->N * drec->H * drec->W));
-    if (dtype == MAS_F32) {
-        if (drec->dtype == MAS_F32) hipLaunchKernelGGL((canvas_bwd_kernel<float, float>), grid, dim3(NT), 0, s, (const float*)dcanvas, *p, scale, *drec);
-        else hipLaunchKernelGGL((canvas_bwd_kernel<float, bf16_t>), grid, dim3(NT), 0, s, (const float*)dcanvas, *p, scale, *drec);
-    } else {
-        if (drec->dtype == MAS_F32) hipLaunchKernelGGL((canvas_bwd_kernel<bf16_t, float>), grid, dim3(NT), 0, s, (const bf16_t*)dcanvas, *p, scale, *drec);
-        else hipLaunchKernelGGL((canvas_bwd_kernel<bf16_t, bf16_t>), grid, dim3(NT), 0, s, (const bf16_t*)dcanvas, *p, scale, *drec);
-    }
+    launch_canvas_bwd(ListTab{*p}, dcanvas, dtype, scale, drec, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_canvas_bwd");
     return MAS_OK;
 }
@@ -398,10 +544,7 @@ extern "C" int mas_obj_relu_fwd(void* y, const MasObjPlan* p, int level, int N, 
     MAS_ENTER();
     if (int rc = check_map(p, level, N, C, dtype, LEVELS - 1, "obj_relu_fwd")) return rc;
     if (!y) MAS_FAIL(MAS_EINVAL, "obj_relu_fwd: null tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for((long long)N * (p->H >> level) * (p->W >> level) * (C / 8)));
-    if (dtype == MAS_F32) hipLaunchKernelGGL(relu_fwd_kernel<float>, grid, dim3(NT), 0, s, (float*)y, *p, level, N, C);
-    else hipLaunchKernelGGL(relu_fwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (bf16_t*)y, *p, level, N, C);
+    launch_relu_fwd(ListTab{*p}, y, level, N, C, dtype, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_relu_fwd");
     return MAS_OK;
 }
@@ -421,10 +564,7 @@ extern "C" int mas_obj_pool_fwd(const void* x, void* y, const MasObjPlan* p, int
     MAS_ENTER();
     if (int rc = check_map(p, level, N, C, dtype, LEVELS - 2, "obj_pool_fwd")) return rc;
     if (!x || !y) MAS_FAIL(MAS_EINVAL, "obj_pool_fwd: null tensor");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for((long long)N * (p->H >> (level + 1)) * (p->W >> (level + 1)) * (C / 8)));
-    if (dtype == MAS_F32) hipLaunchKernelGGL(pool_fwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)x, (float*)y, *p, level, N, C);
-    else hipLaunchKernelGGL(pool_fwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)x, (bf16_t*)y, *p, level, N, C);
+    launch_pool_fwd(ListTab{*p}, x, y, level, N, C, dtype, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_pool_fwd");
     return MAS_OK;
 }
@@ -434,13 +574,7 @@ extern "C" int mas_obj_pool_bwd(const void* a, const void* seed, const void* dz,
     MAS_ENTER();
     if (int rc = check_map(p, level, N, C, dtype, LEVELS - 1, "obj_pool_bwd")) return rc;
     if (!a || !dy || (dz && level == LEVELS - 1)) MAS_FAIL(MAS_EINVAL, "obj_pool_bwd: null tensor, or a pooled gradient at the top level");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(grid_for((long long)N * (p->H >> level) * (p->W >> level) * (C / 8)));
-    if (dtype == MAS_F32)
-        hipLaunchKernelGGL(pool_bwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)a, (const float*)seed, (const float*)dz, (float*)dy, *p, level, N, C);
-    else
-        hipLaunchKernelGGL(pool_bwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)a, (const bf16_t*)seed, (const bf16_t*)dz, (bf16_t*)dy, *p,
-                           level, N, C);
+    launch_pool_bwd(ListTab{*p}, a, seed, dz, dy, level, N, C, dtype, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_pool_bwd");
     return MAS_OK;
 }
@@ -449,11 +583,9 @@ extern "C" int mas_obj_head_fwd(const void* feat, const float* w, const MasObjPl
                                 void* stream) {
     MAS_ENTER();
     if (int rc = check_map(p, level, 1, C, dtype, LEVELS - 1, "obj_head_fwd")) return rc;
-    if (!feat || !w || !partial || C < 64 || C > 512 || (C & (C - 1)) || n_blocks < p->n_cells)
+    if (!feat || !w || !partial || !head_c_ok(C) || n_blocks < p->n_cells)
         MAS_FAIL(MAS_EINVAL, "obj_head_fwd: null argument, C %d or %d blocks for %d cells", C, n_blocks, p->n_cells);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == MAS_F32) hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(n_blocks), dim3(NT), 0, s, (const float*)feat, w, *p, level, C, partial);
-    else hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(n_blocks), dim3(NT), 0, s, (const bf16_t*)feat, w, *p, level, C, partial);
+    launch_head_fwd(ListTab{*p}, feat, w, level, C, dtype, n_blocks, partial, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_head_fwd");
     return MAS_OK;
 }
@@ -462,7 +594,7 @@ extern "C" int mas_obj_finalize(const float* partial, const MasObjPlan* p, float
     MAS_ENTER();
     if (int rc = check_plan(p, "obj_finalize")) return rc;
     if (!partial || !out) MAS_FAIL(MAS_EINVAL, "obj_finalize: null argument");
-    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), partial, *p, out);
+    hipLaunchKernelGGL(finalize_kernel<ListTab>, dim3(1), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), partial, ListTab{*p}, out);
     MAS_CHECK_LAUNCH("obj_finalize");
     return MAS_OK;
 }
@@ -471,12 +603,120 @@ extern "C" int mas_obj_head_bwd(const void* feat, const float* w, const MasObjPl
                                 void* stream) {
     MAS_ENTER();
     if (int rc = check_map(p, level, 1, C, dtype, LEVELS - 1, "obj_head_bwd")) return rc;
-    if (!feat || !w || !dout || !seed || C < 64 || C > 512 || (C & (C - 1))) MAS_FAIL(MAS_EINVAL, "obj_head_bwd: null argument or C %d", C);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const long long npix = (long long)p->n_canvas * (p->H >> level) * (p->W >> level);
-    const dim3 grid(grid_for(npix * (C / 8)));
-    if (dtype == MAS_F32) hipLaunchKernelGGL(head_bwd_kernel<float>, grid, dim3(NT), 0, s, (const float*)feat, w, *p, level, C, dout, (float*)seed);
-    else hipLaunchKernelGGL(head_bwd_kernel<bf16_t>, grid, dim3(NT), 0, s, (const bf16_t*)feat, w, *p, level, C, dout, (bf16_t*)seed);
+    if (!feat || !w || !dout || !seed || !head_c_ok(C)) MAS_FAIL(MAS_EINVAL, "obj_head_bwd: null argument or C %d", C);
+    launch_head_bwd(ListTab{*p}, feat, w, level, C, dtype, dout, seed, reinterpret_cast<hipStream_t>(stream));
     MAS_CHECK_LAUNCH("obj_head_bwd");
+    return MAS_OK;
+}
+
+// ---- the same passes on a table of fixed capacity: nothing about the boxes comes from the host ---------------------------------------
+extern "C" int mas_obj_atlas_ints(int max_cells, int n_images, int n_canvas, int H, int W) {
+    MAS_ENTER();
+    const Atlas a{nullptr, max_cells, n_images, n_canvas, H, W};
+    if (!atlas_geometry_ok(a)) MAS_FAIL(MAS_EINVAL, "obj_atlas_ints: bad atlas (%d cells at most, %d images, %d canvases of %d x %d)", max_cells, n_images, n_canvas, H, W);
+    return MAS_OBJ_ATLAS_HEADER + 8 * max_cells + (n_images + 1) + LEVELS * (max_cells + 1) + n_canvas * (H / MAS_OBJ_ALIGN) * (W / MAS_OBJ_ALIGN);
+}
+
+extern "C" int mas_obj_head_grid_dev(int level, int max_cells, int n_canvas, int H, int W) {
+    MAS_ENTER();
+    const Atlas a{nullptr, max_cells, 1, n_canvas, H, W};
+    if (!atlas_geometry_ok(a) || level < 0 || level >= LEVELS) MAS_FAIL(MAS_EINVAL, "obj_head_grid_dev: level %d or a bad atlas (%d cells at most, %d canvases of %d x %d)", level, max_cells, n_canvas, H, W);
+    return head_grid(a, level);
+}
+
+extern "C" int mas_obj_canvas_fwd_dev(const MasFaceImage* img, const MasFaceImage* rec, const int32_t* table_dev, int max_cells, int n_images,
+                                      int n_canvas, int H, int W, const float* shift, const float* scale, void* canvas, int dtype, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_img(img, "obj_canvas_fwd_dev")) return rc;
+    if (int rc = check_img(rec, "obj_canvas_fwd_dev")) return rc;
+    if (int rc = check_atlas(a, "obj_canvas_fwd_dev")) return rc;
+    if (!shift || !scale || !canvas || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_canvas_fwd_dev: null argument or dtype %d", dtype);
+    launch_canvas_fwd(dev_tab(a), img, rec, shift, scale, canvas, dtype, reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_canvas_fwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_canvas_bwd_dev(const void* dcanvas, int dtype, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W,
+                                      const float* scale, const MasFaceImage* drec, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_img(drec, "obj_canvas_bwd_dev")) return rc;
+    if (int rc = check_atlas(a, "obj_canvas_bwd_dev")) return rc;
+    if (!dcanvas || !scale || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "obj_canvas_bwd_dev: null argument or dtype %d", dtype);
+    launch_canvas_bwd(dev_tab(a), dcanvas, dtype, scale, drec, reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_canvas_bwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_relu_fwd_dev(void* y, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W, int level, int N, int C,
+                                    int dtype, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_atlas(a, "obj_relu_fwd_dev")) return rc;
+    if (int rc = check_level(level, N, C, dtype, LEVELS - 1, "obj_relu_fwd_dev")) return rc;
+    if (!y) MAS_FAIL(MAS_EINVAL, "obj_relu_fwd_dev: null tensor");
+    launch_relu_fwd(dev_tab(a), y, level, N, C, dtype, reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_relu_fwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_pool_fwd_dev(const void* x, void* y, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W, int level,
+                                    int N, int C, int dtype, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_atlas(a, "obj_pool_fwd_dev")) return rc;
+    if (int rc = check_level(level, N, C, dtype, LEVELS - 2, "obj_pool_fwd_dev")) return rc;
+    if (!x || !y) MAS_FAIL(MAS_EINVAL, "obj_pool_fwd_dev: null tensor");
+    launch_pool_fwd(dev_tab(a), x, y, level, N, C, dtype, reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_pool_fwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_pool_bwd_dev(const void* a_, const void* seed, const void* dz, void* dy, const int32_t* table_dev, int max_cells, int n_images,
+                                    int n_canvas, int H, int W, int level, int N, int C, int dtype, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_atlas(a, "obj_pool_bwd_dev")) return rc;
+    if (int rc = check_level(level, N, C, dtype, LEVELS - 1, "obj_pool_bwd_dev")) return rc;
+    if (!a_ || !dy || (dz && level == LEVELS - 1)) MAS_FAIL(MAS_EINVAL, "obj_pool_bwd_dev: null tensor, or a pooled gradient at the top level");
+    launch_pool_bwd(dev_tab(a), a_, seed, dz, dy, level, N, C, dtype, reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_pool_bwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_head_fwd_dev(const void* feat, const float* w, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W,
+                                    int level, int dtype, float* partial, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_atlas(a, "obj_head_fwd_dev")) return rc;
+    if (int rc = check_level(level, 1, 8, dtype, LEVELS - 1, "obj_head_fwd_dev")) return rc;
+    if (!feat || !w || !partial) MAS_FAIL(MAS_EINVAL, "obj_head_fwd_dev: null argument");
+    const DevTab t = dev_tab(a);
+    launch_head_fwd(t, feat, w, level, HEAD_C[level], dtype, head_grid(a, level), partial + t.off[level], reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_head_fwd_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_finalize_dev(const float* partial, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W, float* out,
+                                    void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_atlas(a, "obj_finalize_dev")) return rc;
+    if (!partial || !out) MAS_FAIL(MAS_EINVAL, "obj_finalize_dev: null argument");
+    hipLaunchKernelGGL(finalize_kernel<DevTab>, dim3(1), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), partial, dev_tab(a), out);
+    MAS_CHECK_LAUNCH("obj_finalize_dev");
+    return MAS_OK;
+}
+
+extern "C" int mas_obj_head_bwd_dev(const void* feat, const float* w, const int32_t* table_dev, int max_cells, int n_images, int n_canvas, int H, int W,
+                                    int level, int dtype, const float* dout, void* seed, void* stream) {
+    MAS_ENTER();
+    const Atlas a{table_dev, max_cells, n_images, n_canvas, H, W};
+    if (int rc = check_atlas(a, "obj_head_bwd_dev")) return rc;
+    if (int rc = check_level(level, 1, 8, dtype, LEVELS - 1, "obj_head_bwd_dev")) return rc;
+    if (!feat || !w || !dout || !seed) MAS_FAIL(MAS_EINVAL, "obj_head_bwd_dev: null argument");
+    launch_head_bwd(dev_tab(a), feat, w, level, HEAD_C[level], dtype, dout, seed, reinterpret_cast<hipStream_t>(stream));
+    MAS_CHECK_LAUNCH("obj_head_bwd_dev");
     return MAS_OK;
 }

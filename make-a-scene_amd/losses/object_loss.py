@@ -26,7 +26,11 @@ class ObjectLoss(nn.Module):
     intended); it is NOT registered as a child, so sharing it adds no ``state_dict`` keys.  ``None`` builds one with LPIPS's checkpoint
     rules (``MAS_LPIPS_CKPT`` / ``MAS_VGG16_CKPT``), owned by this module.  ``dtype``: the activations' precision; ``None`` follows
     ``mas_hip.ops.compute_dtype()`` (bf16 by default, fp32 in the parity mode).  ``last_values``: every used crop's LPIPS of the
-    last call, in (image, box) order (None without used boxes)."""
+    last call, in (image, box) order (None without used boxes).
+
+    ``forward(images, reconstructions, atlas)`` with a ``mas_hip.objects.ObjectAtlas`` instead of the box lists is the same term at
+    fixed capacity (``mas_hip.objects.object_loss_static``: the crops are the ones last written into the atlas; nothing is read on the
+    host, so a graph can capture it).  ``last_values`` is then the atlas's ``max_cells`` slots, the unused ones 0."""
 
     def __init__(self, lpips=None, dtype=None):
         super().__init__()
@@ -40,6 +44,10 @@ class ObjectLoss(nn.Module):
 
     def forward(self, images, reconstructions, bbox_obj):
         from mas_hip import objects as O
+        if isinstance(bbox_obj, O.ObjectAtlas):
+            out = O.object_loss_static(self.net, images, reconstructions, bbox_obj, self.dtype)
+            self.last_values = out[1:].detach()
+            return out[0]
         out = O.object_loss(self.net, images, reconstructions, bbox_obj, self.dtype)
         if out is None:
             self.last_values = None

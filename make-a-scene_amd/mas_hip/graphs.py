@@ -46,6 +46,7 @@ Not supported: ``GradReducer`` / DistributedDataParallel wrappers (their collect
 that are not tensors, and a ``loss_fn`` that reads anything on the host."""
 import collections
 import contextlib
+import warnings
 
 import torch
 import torch.nn.functional as F
@@ -350,15 +351,28 @@ class GraphedGanStep(GraphedTrainStep):
       fixed-capacity node reads.  Every phase then has its graphs TWICE, keyed ``(closing, faces)``: without the term (a call without
       faces replays exactly what a step with ``face_loss=None`` replays) and with it; both are captured together and share the phase's
       pool, so batches with and without faces alternate without a capture.  ``example_bbox_face``: the boxes of the warm-up calls.
-    * refused at construction: an optimizer without ``device_step``, a codebook without its device reservoir, a ``reducer``, an
-      ``object_loss`` on the loss, and any other ``face_loss`` (a callable, a ``FaceLoss`` in ``train()`` mode): their crops are cut
-      from host box lists.  The perceptual term may be LPIPS with its HIP path on or off, any capturable callable, or ``None``."""
+    * the object term: a ``loss.object_loss`` that is a ``losses.object_loss.ObjectLoss`` (``object_loss="lpips"``) is captured.
+      ``step(images, bbox_face, bbox_obj)`` takes one list of boxes per image (``None``: no objects), plans them on the host and writes
+      them into the step's ``mas_hip.objects.ObjectAtlas`` (``step.object_atlas``: ``object_atlas=`` at construction is an
+      ``ObjectAtlas``, a dict of its keyword arguments, or ``None`` for its default geometry), which the captured fixed-capacity node
+      reads.  The graphs are then keyed ``(closing, faces, objects)``: a call whose boxes yield no used crop replays the variant
+      without the term -- exactly what a step with ``object_loss=None`` replays; all variants of a phase are captured together and
+      share its pool.  (Without an object term the keys stay ``(closing, faces)``.)  Boxes that do not fit the atlas
+      (``objects.AtlasOverflow``): ``on_overflow="eager"`` (the default) runs that ONE call eagerly through the same ``_step`` on the
+      side stream, under the conditions of the warm-up calls, with the box lists on the list path; it counts in ``step.eager_calls``,
+      warns once (``RuntimeWarning``), and leaves the graphs as they are.  ``on_overflow="raise"`` re-raises before the tick, like
+      a refused face box.  ``example_bbox_obj``: the boxes of the warm-up calls.
+    * refused at construction: an optimizer without ``device_step``, a codebook without its device reservoir, a ``reducer``, any
+      ``object_loss`` that is not an ``ObjectLoss`` (a callable), and any other ``face_loss`` (a callable, a ``FaceLoss`` in ``train()``
+      mode): their crops are cut from host box lists.  The perceptual term may be LPIPS with its HIP path on or off, any capturable
+      callable, or ``None``."""
 
     def __init__(self, model, loss, gen_optimizer, disc_optimizer, example_images, *, amp_dtype=None, accumulate=1, global_step=0, warmup=1,
-                 reducer=None, example_bbox_face=None):
+                 reducer=None, example_bbox_face=None, example_bbox_obj=None, object_atlas=None, on_overflow="eager"):
         name = type(self).__name__
+        capturable = {"face_loss": self._capturable_face, "object_loss": self._capturable_object}
         for term in ("face_loss", "object_loss"):
-            if getattr(loss, term, None) is not None and not (term == "face_loss" and self._capturable_face(loss.face_loss)):
+            if getattr(loss, term, None) is not None and not capturable[term](getattr(loss, term)):
                 raise NotImplementedError(f"{name}: the loss has a {term}, whose crops are cut from host box lists that a capture "
                                           f"cannot hold; build the loss with {term}=None, or train eagerly")
         if not hasattr(loss, "hip_tail") or not hasattr(loss, "discriminator"):
@@ -372,7 +386,21 @@ class GraphedGanStep(GraphedTrainStep):
         if getattr(loss, "face_loss", None) is not None:
             from . import face
             self.face_table = face.FaceTable(example_images.device)
+        if on_overflow not in ("eager", "raise"):
+            raise ValueError(f"{name}: on_overflow must be 'eager' or 'raise', got {on_overflow!r}")
+        self.on_overflow, self.eager_calls, self._warned_overflow = on_overflow, 0, False
+        self.object_atlas, self._objects, self._obj_lists = None, False, None
+        if getattr(loss, "object_loss", None) is not None:
+            from . import objects
+            if isinstance(object_atlas, objects.ObjectAtlas):
+                if object_atlas.device != example_images.device or object_atlas.n_images > example_images.shape[0]:
+                    raise ValueError(f"{name}: the object atlas is on {object_atlas.device} for {object_atlas.n_images} images, the batch "
+                                     f"has {example_images.shape[0]} on {example_images.device}")
+                self.object_atlas = object_atlas
+            else:
+                self.object_atlas = objects.ObjectAtlas(example_images.device, example_images.shape[0], **(object_atlas or {}))
         self._write_faces(example_bbox_face, example_images.shape[0])
+        self._write_objects(example_bbox_obj)
         super().__init__(None, gen_optimizer, (example_images,), amp_dtype=amp_dtype, warmup=warmup, modules=[model, loss], reducer=reducer,
                          accumulate=accumulate)
 
@@ -390,6 +418,34 @@ class GraphedGanStep(GraphedTrainStep):
             return False
         return isinstance(term, FaceLoss) and not term.training
 
+    @staticmethod
+    def _capturable_object(term):
+        """a ``losses.object_loss.ObjectLoss``: the one object term whose crops a device table (``objects.ObjectAtlas``) can carry"""
+        try:
+            from losses.object_loss import ObjectLoss
+        except ImportError:
+            return False
+        return isinstance(term, ObjectLoss)
+
+    def _write_objects(self, bbox_obj):
+        """the call's boxes into the atlas (host planning, one asynchronous copy); sets which variant the call takes.  Boxes that do
+        not fit: re-raised (``on_overflow="raise"``), or kept as host lists for one eager call; the atlas keeps what it held.  Without
+        an object term the boxes are ignored."""
+        self._objects, self._obj_lists = False, None
+        if self.object_atlas is None:
+            return
+        from . import objects
+        try:
+            self._objects = self.object_atlas.write(bbox_obj) > 0
+        except objects.AtlasOverflow as e:
+            if self.on_overflow == "raise":
+                raise
+            if not self._warned_overflow:
+                self._warned_overflow = True
+                warnings.warn(f"{type(self).__name__}: {e}; this call runs eagerly on the list path (on_overflow='eager'; this warning "
+                              "is issued once, step.eager_calls counts)", RuntimeWarning, stacklevel=3)
+            self._objects, self._obj_lists = True, objects.box_lists(bbox_obj)
+
     def _write_faces(self, bbox_face, n_images):
         """the call's boxes into the table (host planning and checks, one asynchronous copy); sets which variant the call takes.
         Without a face term the boxes are ignored, as the loss ignores them."""
@@ -397,20 +453,23 @@ class GraphedGanStep(GraphedTrainStep):
 
     def _keys(self):
         variants = (False, True) if self.face_table is not None else (False,)
-        return tuple((closing, faces) for closing in super()._keys() for faces in variants)
+        keys = tuple((closing, faces) for closing in super()._keys() for faces in variants)
+        if self.object_atlas is None:
+            return keys
+        return tuple(key + (objects,) for key in keys for objects in (False, True))
 
     def _key(self, closing):
-        return (closing, self._faces)
+        return (closing, self._faces) if self.object_atlas is None else (closing, self._faces, self._objects)
 
     def _settle_for_capture(self):
         """the face term alone, once, eagerly, on whatever the table holds: its weights' packed images, the BatchNorm address table and
         the convolutions' choices exist before a capture meets them (the term is frozen: no value moves)"""
-        if self.face_table is None:
-            return
         x = self._static[0]
-        rec = x.detach().clone().requires_grad_(True)
-        with self._autocast():
-            self.loss_module.face_loss(x, rec, self.face_table).backward()
+        for term, table in ((self.loss_module.face_loss, self.face_table), (self.loss_module.object_loss, self.object_atlas)):
+            if table is not None:                             # (the object term likewise: its LPIPS weights are frozen)
+                rec = x.detach().clone().requires_grad_(True)
+                with self._autocast():
+                    term(x, rec, table).backward()
 
     def set_global_step(self, n):
         """writes the device counter (a resume); no capture depends on its value"""
@@ -421,8 +480,13 @@ class GraphedGanStep(GraphedTrainStep):
         return GanStepOut(*(t.detach() for t in out))
 
     def _step(self, key):
-        closing, faces = key
+        closing, faces, objects = key if len(key) == 3 else key + (False,)
         model, crit, images = self.model, self.loss_module, self._static[0]
+        # the object term's boxes: the atlas (what a capture holds), or the host lists of a call that did not fit it (eager only);
+        # a call without a used crop runs without the term, as a loss built with object_loss=None does
+        term, bbox_obj = getattr(crit, "object_loss", None), None
+        if objects:
+            bbox_obj = self._obj_lists if self._obj_lists is not None else self.object_atlas
         if self.accumulate == 1:
             for opt in self._opts:
                 opt.zero_grad(set_to_none=True)
@@ -436,10 +500,14 @@ class GraphedGanStep(GraphedTrainStep):
                 for p in disc:
                     p.requires_grad_(False)
                 crit.advance_global_step = True
-                loss, (nll_loss, _, _) = crit(0, self.global_step, images, rec, q_loss, bbox_face=self.face_table if faces else None,
-                                              last_layer=model.decoder.model[-1])
+                if term is not None and not objects:
+                    crit.object_loss = None
+                loss, (nll_loss, _, _) = crit(0, self.global_step, images, rec, q_loss, bbox_obj=bbox_obj,
+                                              bbox_face=self.face_table if faces else None, last_layer=model.decoder.model[-1])
                 loss.backward()
             finally:
+                if term is not None:
+                    crit.object_loss = term
                 crit.advance_global_step = advance
                 for p, f in zip(disc, flags):
                     p.requires_grad_(f)
@@ -451,7 +519,32 @@ class GraphedGanStep(GraphedTrainStep):
                 self._zero_grads_in_place()
         return GanStepOut(loss, d_loss, nll_loss, terms["g_loss"], terms["d_weight"])
 
-    def __call__(self, images, bbox_face=None):
+    def _eager_call(self, images):
+        """one call without a graph -- the tick, the hyperparameters, the static input and ``_step`` as a replay would run them, eagerly on
+        the side stream under the conditions of ``_warm_up``.  The graphs stay valid: an eager ``optimizer.step()`` uploads tables of
+        its own and bumps no ``state_generation``, and under ``accumulate > 1`` the backward adds into the persistent gradients the
+        graphs add into.  The outputs are this call's own tensors, not the graphs' static ones."""
+        closing = self._tick()
+        for opt in self._opts:
+            opt.sync_hyperparameters()
+        s = self._static[0]
+        if images.shape != s.shape or images.dtype != s.dtype or images.device != s.device:
+            self._graphs, self._sig = {}, None                # (the next replay captures for the new shape, as it would have anyway)
+            self._static = [images.detach().clone()]
+        elif images is not s:
+            s.copy_(images, non_blocking=True)
+        main = torch.cuda.current_stream(self._side.device)
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side), ops.wgrad_stream_off(), self._codebooks_in("ticked_by_caller"), self._autocast():
+            out = self._detached(self._step(self._key(closing)))
+        main.wait_stream(self._side)
+        self.eager_calls += 1
+        return out
+
+    def __call__(self, images, bbox_face=None, bbox_obj=None):
         self._check_inputs((images,))
         self._write_faces(bbox_face, images.shape[0])         # (before the tick: a box that is refused leaves the counters alone)
+        self._write_objects(bbox_obj)
+        if self._obj_lists is not None:                       # the boxes do not fit the atlas: this one call runs eagerly
+            return self._eager_call(images)
         return self._replay((images,))

@@ -26,7 +26,18 @@ per call with k = 0, 1, 2 alternating as a data set would, in four columns that 
   graphed, face_loss=None  the step as it was before the face term could be captured
 
 then the face node alone, forward + backward at the batch's images: the list node against the fixed-capacity node at n = 1 and n = 3 faces
-(2n rows forward and n backward against 6 and 3)."""
+(2n rows forward and n backward against 6 and 3).
+
+``--objects`` measures the object term inside the step INSTEAD: ``object_loss="lpips"`` on the loss (the perceptual LPIPS's weights), seeded
+boxes of 48..160 px with 0 / 2 / 6 used crops per image alternating call by call, in columns that alternate block by block in one process:
+
+  eager, lists           the step as it runs without this class: ATen tail, host-step Adams, the boxes as lists (the atlas cut to them)
+  graphed, HxW[xN]       GraphedGanStep(images, None, bbox_obj) with an ObjectAtlas of that geometry: the default, one of twice its area
+                         and, beyond B = 2, one scaled with the batch (a default canvas per two images); a call whose boxes do not fit
+                         runs eagerly on the list path and counts in eager_calls
+
+with the atlas efficiency (crop area / canvas area) of each box set on the fixed canvases and on the list path's own, then the object node
+alone, forward + backward: the list node against the fixed-capacity node on each atlas the six-crop set fits."""
 import argparse, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "make-a-scene_amd"))
@@ -42,6 +53,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--seconds", type=float, default=2.0, help="wall time one timed block should fill")
 ap.add_argument("--configs", default="2:8,32:1", help="batch:accumulate pairs")
 ap.add_argument("--faces", action="store_true", help="measure the face term inside the step (see above) instead of the three forms")
+ap.add_argument("--objects", action="store_true", help="measure the object term inside the step (see above) instead of the three forms")
 a = ap.parse_args()
 
 IMG_CFG = dict(ddconfig=dict(z_channels=256, in_channels=3, out_channels=3, channels=[128, 128, 128, 256, 512, 512], num_res_blocks=2,
@@ -65,7 +77,7 @@ def device_activities(fn):
         return None
 
 
-def gan_call(model, crit, gopt, dopt, x, step, closing, last_layer=None, rec_fn=None, bbox_face=None):
+def gan_call(model, crit, gopt, dopt, x, step, closing, last_layer=None, rec_fn=None, bbox_face=None, bbox_obj=None):
     rec, q = model(x) if rec_fn is None else rec_fn()
     d_loss = crit(1, step, x, rec)
     d_loss.backward()
@@ -73,7 +85,7 @@ def gan_call(model, crit, gopt, dopt, x, step, closing, last_layer=None, rec_fn=
     for p in disc:
         p.requires_grad_(False)
     try:
-        loss, _ = crit(0, step, x, rec, q, bbox_face=bbox_face, last_layer=last_layer if last_layer is not None else model.decoder.model[-1])
+        loss, _ = crit(0, step, x, rec, q, bbox_face=bbox_face, bbox_obj=bbox_obj, last_layer=last_layer if last_layer is not None else model.decoder.model[-1])
         loss.backward()
     finally:
         for p in disc:
@@ -192,10 +204,128 @@ def bench_faces():
         torch.cuda.empty_cache()
 
 
+def object_boxes(batch, per_image, seed):
+    """``per_image`` seeded boxes of 48..160 px on every image of a 256 x 256 batch, some partly outside it"""
+    import random
+    rng = random.Random(seed)
+    out = []
+    for _ in range(batch):
+        boxes = []
+        for _ in range(per_image):
+            h, w = rng.randint(48, 160), rng.randint(48, 160)
+            y0, x0 = rng.randint(-h // 4, 256 - 3 * h // 4), rng.randint(-w // 4, 256 - 3 * w // 4)
+            boxes.append([x0, y0, x0 + w, y0 + h])
+        out.append(boxes)
+    return out
+
+
+def bench_objects():
+    """--objects: the step columns and the node alone, per configuration"""
+    import warnings
+    from mas_hip import objects as O
+    for cfg in a.configs.split(","):
+        batch, acc = (int(v) for v in cfg.split(":"))
+        x = torch.rand(batch, 3, 256, 256, generator=torch.Generator().manual_seed(0)).to(dev)
+        cycle = [object_boxes(batch, k, 10 + k) for k in (0, 2, 6)]
+        atlases = {"544x1088": dict(), "1088x1088": dict(height=1088)}
+        if batch > 2:
+            atlases[f"544x1088x{batch // 2}"] = dict(canvases=batch // 2, max_cells=6 * batch)
+        for name, kw in atlases.items():
+            probe = O.ObjectAtlas("cpu", batch, **kw)
+            eff = []
+            for boxes in cycle[1:]:
+                if probe.fits(boxes):
+                    probe.write(boxes)
+                eff.append(f"{probe.efficiency():.3f}" if probe.fits(boxes) else "does not fit")
+            print(f"B={batch} atlas {name}: efficiency (crop area / canvas area) at 2 / 6 crops per image: {' / '.join(eff)}", flush=True)
+        tight = [O.make_plan(boxes, batch) for boxes in cycle[1:]]
+        print(f"B={batch} list path's own canvases: " + " / ".join(f"{p.n_canvas} x {p.H} x {p.W}, efficiency {p.efficiency():.3f}" for p in tight), flush=True)
+        names = ("eager, lists",) + tuple(f"graphed, {k}" for k in atlases)
+        cols, steps = {}, {}
+        for name in names:
+            torch.manual_seed(1)
+            model = VQBASE(**IMG_CFG)
+            with torch.no_grad():
+                model.quantize.embedding.weight.normal_(0.0, 1.0)
+            model = model.to(dev).train()
+            model.quantize.q_counter = model.quantize.q_re_end
+            crit = VQLPIPSWithDiscriminator(disc_start=0, perceptual_loss="lpips", face_loss=None, object_loss="lpips").to(dev)
+            on = name != names[0]
+            if on:
+                model.quantize.enable_device_reservoir(seed=7)
+            gopt = optim.Adam(model.parameters(), lr=5e-6 / acc, betas=(0.5, 0.9), device_step=on)
+            dopt = optim.Adam(crit.discriminator.parameters(), lr=5e-6 / acc, betas=(0.5, 0.9), device_step=on)
+            if on:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore", RuntimeWarning)
+                    step = graphs.GraphedGanStep(model, crit, gopt, dopt, x, accumulate=acc, warmup=acc, global_step=0,
+                                                 object_atlas=atlases[name[len("graphed, "):]])
+
+                    def call(step=step, n=[0]):
+                        n[0] += 1
+                        return step(x, None, cycle[n[0] % 3]).loss
+                    for _ in range(3 * acc):
+                        call()
+                steps[name] = step
+                print(f"B={batch} accumulate={acc} {name}: {step.captures} capture(s)", flush=True)
+            else:
+                def call(model=model, crit=crit, gopt=gopt, dopt=dopt, n=[0]):
+                    n[0] += 1
+                    with hip_tail(False):
+                        return gan_call(model, crit, gopt, dopt, x, n[0], n[0] % acc == 0, bbox_obj=cycle[n[0] % 3])
+                for _ in range(3 * acc):
+                    call()
+            cols[name] = call
+        unit = 3 * acc                                            # a block holds whole cycles of the boxes and whole optimizer steps
+        guarded = {k: k in steps and all(steps[k].object_atlas.fits(b) for b in cycle) for k in cols}     # (an eager call reads on the host)
+        n_calls = {k: max(1, int(a.seconds / block(fn, unit, guarded[k])[0]) // unit) * unit for k, fn in cols.items()}
+        times = {k: [] for k in cols}
+        before = {k: s.eager_calls for k, s in steps.items()}
+        for _ in range(2):
+            for k, fn in cols.items():
+                dt, loss = block(fn, n_calls[k], guarded[k])
+                assert bool(torch.isfinite(loss)), (k, float(loss))
+                times[k].append(dt)
+        for k in cols:
+            extra = f", eager_calls {steps[k].eager_calls - before[k]} of {2 * n_calls[k]}" if k in steps else ""
+            print(f"VQ-IMG 256x256 B={batch} accumulate={acc} training call, crops per image 0/2/6 alternating, {k}: "
+                  + " / ".join(f"{t * 1e3:.2f}" for t in times[k]) + f" ms/call ({n_calls[k]} calls per block{extra})", flush=True)
+        lp = crit.object_loss.net
+        del cols, steps, model, gopt, dopt, step, crit
+        torch.cuda.empty_cache()
+
+        # ---- the node alone: the list node (a canvas cut to the boxes) against the fixed-capacity node on each atlas ------------------------
+        rec = (x + 0.1 * torch.randn_like(x)).clamp(0, 1)
+        for per, boxes in ((2, cycle[1]), (6, cycle[2])):
+            tables = {"lists": boxes}
+            for name, kw in atlases.items():
+                atlas = O.ObjectAtlas(dev, batch, **kw)
+                if atlas.fits(boxes):
+                    atlas.write(boxes)
+                    tables[name] = atlas
+            res = {}
+            for _ in range(2):
+                for k, bb in tables.items():
+                    def node(bb=bb):
+                        r = rec.clone().requires_grad_(True)
+                        out = (O.object_loss_static if isinstance(bb, O.ObjectAtlas) else O.object_loss)(lp, x, r, bb)
+                        out[0].backward()
+                        return out[0]
+                    for _ in range(3):
+                        node()
+                    res.setdefault(k, []).append(block(node, 20)[0])
+            for k in tables:
+                print(f"object node alone B={batch}, {per} crops per image, {k}: " + " / ".join(f"{t * 1e3:.3f}" for t in res[k]) + " ms wall", flush=True)
+        del lp, rec, tables
+        torch.cuda.empty_cache()
+
+
 with hip_path(True):
     if a.faces:
         bench_faces()
-    for cfg in ([] if a.faces else a.configs.split(",")):
+    if a.objects:
+        bench_objects()
+    for cfg in ([] if a.faces or a.objects else a.configs.split(",")):
         batch, acc = (int(v) for v in cfg.split(":"))
         x = torch.rand(batch, 3, 256, 256, generator=torch.Generator().manual_seed(0)).to(dev)
         cols, counts = {}, {}

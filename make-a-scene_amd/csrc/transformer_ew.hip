@@ -92,7 +92,15 @@ __global__ __launch_bounds__(NT) void gelu_bwd_kernel(const T* __restrict__ x, c
     constexpr bool EXACT = sizeof(T) == 4;
     auto grad = [](float a, float g) {
         const float a2 = a * a, t = tanh_f<EXACT>(GK * a * (1.0f + GC * a2));
-        return g * (0.5f * (1.0f + t) + 0.5f * a * (1.0f - t * t) * GK * (1.0f + 3.0f * GC * a2));
+        // a2 is inf for |a| >= 2^64 (finite in bf16 and fp32), where tanh has saturated and the derivative is exactly 1 or 0: the last
+        // factor must not turn (1 - t * t) = 0 into 0 * inf.  Either branch yields g * 1 or g * 0 there and the plain formula everywhere
+        // else; there are two because each keeps its own type's other outputs bit for bit what the unguarded expression gives.
+        if constexpr (EXACT) {
+            const float r = g * (0.5f * (1.0f + t) + 0.5f * a * (1.0f - t * t) * GK * (1.0f + 3.0f * GC * a2));
+            return a2 > 3.402823466e38f ? g * (a > 0.0f ? 1.0f : 0.0f) : r;
+        } else {
+            return g * (0.5f * (1.0f + t) + 0.5f * a * (1.0f - t * t) * GK * (1.0f + 3.0f * GC * fminf(a2, 3.402823466e38f)));
+        }
     };
     float acc[CS ? N : 1];
 #pragma unroll
@@ -638,6 +646,7 @@ extern "C" size_t mas_colsum_workspace(int rows, int cols) {
 }
 
 extern "C" int mas_colsum(const void* x, int dtype, int rows, int cols, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    MAS_ENTER();
     if (!x || !out || !workspace) MAS_FAIL(MAS_EINVAL, "colsum: null argument");
     if (rows <= 0 || cols <= 0) MAS_FAIL(MAS_EINVAL, "colsum: bad shape rows=%d cols=%d", rows, cols);
     if (dtype != MAS_BF16 && dtype != MAS_F32) MAS_FAIL(MAS_EUNSUPPORTED, "colsum: dtype %d (bf16 or fp32)", dtype);

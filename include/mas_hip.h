@@ -668,6 +668,40 @@ int mas_img_agreement(const unsigned char* a, const unsigned char* b, int N, int
 int mas_img_agreement_reduce(const double* partials, int n_partials, int N, int C, int H, int W, double* ssim, void* stream);
 int mas_code_usage(const void* indices, int index_bytes, long long n, int K, long long* counts, void* stream);
 
+/* mas_token_readout, mas_token_readout_accumulate (additions under ABI 10): the stage-2 validation read-out -- per token the negative
+ *   log-likelihood, the entropy of the predictive distribution, the predicted token and the rank of the true one, from ONE read of the
+ *   logits in their own dtype, and their accumulation per position of the token grid.
+ *   mas_token_readout: logits, dtype, rows, V, inner, outer_stride, ld, target, ignore_index exactly as for mas_token_ce_fwd (fp32 or bf16,
+ *     read in place, element alignment only, any V >= 1, 64-bit offsets).  Per row r, with m = max_j x_j, d_j = x_j - m, l = sum_j exp(d_j):
+ *       nll[r]     fp32  = (m - x_t) + log l                           (m and log l kept apart, as in mas_token_ce_fwd)
+ *       entropy[r] fp32  = log l - (sum_j exp(d_j) d_j) / l            (an entry of -inf adds 0 to both sums; 0 * inf is never formed)
+ *       argmax[r]  int32 = the FIRST index of the maximum              (torch.argmax's rule)
+ *       rank[r]    int32 = #{j : x_j > x_t} + #{j < t : x_j == x_t}    (the stored values compared as fp32, exact: the position of t in a
+ *                                                                       stable descending sort; a hit at top-k is rank < k)
+ *     target == ignore_index: the row is not read; nll = entropy = 0, argmax = rank = -1.  INVALID rows -- any other target outside
+ *     [0, V) (not read either), a row that holds a NaN or +inf, a row of -inf alone: nll = entropy = NaN, argmax = -1, rank = V; the call
+ *     returns normally.  x_t = -inf in an otherwise valid row is valid: nll = +inf.  No load is indexed by a target value.  Rows that start
+ *     on a 16-byte boundary and hold at most 4 16-byte units per lane of the 256 (V <= 8192 bf16, 4096 fp32, tail V % unit included) are
+ *     read from memory once; longer rows and unaligned rows are walked a second time for the rank.  No atomics: results repeat bit for bit.
+ *   mas_token_readout_accumulate: the four per-row arrays of mas_token_readout, target, rows, ignore_index, L = the number of positions
+ *     (row r belongs to position r % L; rows % L != 0: MAS_EINVAL), ks = HOST array of nk <= MAS_TOKEN_MAX_KS thresholds, each >= 1.
+ *     A row COUNTS when its target is not ignore_index and it is not invalid (argmax >= 0).  ADDED to what the device accumulators hold:
+ *       nll_sum, entropy_sum fp64 [L]: per position a local sum that starts at 0 and takes (double)nll[r] of the counted rows r = p, p + L,
+ *         ... in increasing r, added ONCE to the held value (fixed order, no float atomics);
+ *       count int64 [L]: the counted rows;  hits int64 [L][nk]: those with rank < ks[i];
+ *       rank_hist int64 [MAS_TOKEN_RANK_BINS]: bin 0 = rank 0, bin b >= 1 = rank in [2^(b-1), 2^b), counted rows;
+ *       invalid int64 [1]: the invalid rows.  (The last two: 64-bit integer atomics, exact in any order.)
+ *   Both: no host synchronisation (they capture into a graph); every argument check precedes the launch.  Null arguments, an empty shape,
+ *     a negative stride, nk outside 0 .. MAS_TOKEN_MAX_KS, a threshold below 1: MAS_EINVAL.  Another dtype: MAS_EUNSUPPORTED.          */
+enum { MAS_TOKEN_MAX_KS = 8, MAS_TOKEN_RANK_BINS = 33 };
+int mas_token_readout(const void* logits, int dtype, long long rows, int V, long long inner, long long outer_stride, long long ld,
+                      const int64_t* target, long long ignore_index, float* nll, float* entropy, int32_t* argmax, int32_t* rank,
+                      void* stream);
+int mas_token_readout_accumulate(const float* nll, const float* entropy, const int32_t* argmax, const int32_t* rank, const int64_t* target,
+                                 long long rows, long long ignore_index, long long L, const int* ks, int nk, double* nll_sum,
+                                 double* entropy_sum, long long* count, long long* hits, long long* rank_hist, long long* invalid,
+                                 void* stream);
+
 /* mas_layernorm_pair_* (ABI v9): the sandwich LayerNorm + residual of one sub-block and the pre-LayerNorm of the next as ONE pass,
  *   xnew = residual + LN1(h),  y2 = LN2(xnew)      (reference models/transformer.py:201-203 + :205, and :207-209 + :197 of the next layer
  *   or the final LayerNorm :264) -- the row stays in registers between the two: 12 B per element instead of 16, bit for bit the values

@@ -2399,6 +2399,92 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, *, reduction: str 
 
 
 # --------------------------------------------------------------------------- #
+# stage-2 read-out: per-token nll, entropy, rank, argmax and their per-position accumulation (token_readout.hip)
+# --------------------------------------------------------------------------- #
+def _check_token_inputs(logits, target, what: str):
+    if not isinstance(logits, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise ValueError(f"{what}: logits and target must be tensors")
+    if target.is_floating_point() or target.is_complex():
+        raise ValueError(f"{what}: class-probability (float) targets are not offered; pass int64 class indices")
+    if logits.dim() < 1 or tuple(target.shape) != tuple(logits.shape[:-1]):
+        raise ValueError(f"{what}: logits [..., V] {tuple(logits.shape)} need a target of shape [...], got {tuple(target.shape)}")
+    if logits.numel() == 0:
+        raise ValueError(f"{what}: empty logits")
+
+
+def _require_token_device(logits, target, what: str):
+    _require_cuda(logits, what)
+    _require_cuda(target, what)
+    _check_dtype(logits, what)
+
+
+def _token_readout(logits, target, ignore_index, what):
+    """-> (nll fp32, entropy fp32, rank int32, argmax int32, target int64), each flat [rows] (``mas_token_readout``)"""
+    x, inner, outer, ld = _ce_layout(logits.detach())
+    v = x.shape[-1]
+    rows = x.numel() // v
+    tgt = target.detach().long().reshape(-1).contiguous()
+    nll = torch.empty(rows, dtype=torch.float32, device=x.device)
+    ent = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rank = torch.empty(rows, dtype=torch.int32, device=x.device)
+    arg = torch.empty(rows, dtype=torch.int32, device=x.device)
+    check(lib().mas_token_readout(_ptr(x), _DT[x.dtype], rows, v, inner, outer, ld, _ptr(tgt), ignore_index, _ptr(nll), _ptr(ent), _ptr(arg),
+                                  _ptr(rank), _stream()), what)
+    return nll, ent, rank, arg, tgt
+
+
+def token_readout(logits: torch.Tensor, target: torch.Tensor, *, ignore_index: int = -100):
+    """Per token, from ONE read of ``logits`` [..., V] (fp32 or bf16, the in-place [B, L, V] slice of [B, S, V] included, as
+    ``ops.cross_entropy`` takes them) and ``target`` [...] int64 -> ``(nll, entropy, rank, argmax)``, each shaped like ``target``:
+    ``nll`` fp32 = -log p(target); ``entropy`` fp32 of the predictive distribution, in nats; ``rank`` int32 = the position of the target in
+    a stable descending sort of the row (0: the model's first choice; top-k hit: ``rank < k``); ``argmax`` int32 = the first index of the
+    maximum.  ``target == ignore_index``: the row is not read, nll = entropy = 0, rank = argmax = -1.  Any other target outside [0, V), a
+    row with a NaN or +inf, a row of -inf alone: nll = entropy = NaN, argmax = -1, rank = V.  No autograd node: the logits are detached.
+    No host synchronisation."""
+    _check_token_inputs(logits, target, "token_readout")
+    _require_token_device(logits, target, "token_readout")
+    nll, ent, rank, arg, _ = _token_readout(logits, target, int(ignore_index), "token_readout")
+    return nll.view(target.shape), ent.view(target.shape), rank.view(target.shape), arg.view(target.shape)
+
+
+def token_agreement(logits: torch.Tensor, target: torch.Tensor, *, positions: Optional[int] = None, ks=(1, 5), ignore_index: int = -100,
+                    out=None):
+    """The validation read-out of a batch of stage-2 logits -> ``mas_hip.tokenmetrics.TokenAgreement``: per position of the token grid the
+    fp64 sums of ``token_readout``'s nll and entropy, the tokens counted and the top-``ks`` hits; the histogram of the target's rank and
+    the number of invalid rows (``mas_token_readout`` + ``mas_token_readout_accumulate``).  Flattened row ``r`` belongs to position
+    ``r % positions``; ``positions`` defaults to ``target.shape[-1]`` and must divide the number of rows.  ``out``: a ``TokenAgreement`` of
+    the same ``ks`` and positions on the logits' device that the batch is ADDED to (and which is returned); without it a zeroed one is
+    made.  Ignored and invalid rows are not counted.  Sums are taken in a fixed order: the same batches give the same bits.  No autograd
+    node, no host synchronisation (the call captures into a graph)."""
+    from .tokenmetrics import TokenAgreement, check_ks
+    _check_token_inputs(logits, target, "token_agreement")
+    ks = check_ks(ks, "token_agreement")
+    rows = target.numel()
+    if positions is None:
+        positions = target.shape[-1] if target.dim() >= 1 else 1
+    positions = int(positions)
+    if positions < 1 or rows % positions != 0:
+        raise ValueError(f"token_agreement: {rows} rows are not a multiple of positions = {positions}")
+    if out is not None:
+        if not isinstance(out, TokenAgreement):
+            raise ValueError(f"token_agreement: out must be a TokenAgreement, got {type(out).__name__}")
+        if out.ks != ks or out.positions != positions:
+            raise ValueError(f"token_agreement: out holds ks {out.ks} / {out.positions} positions, the call has ks {ks} / {positions}")
+    _require_token_device(logits, target, "token_agreement")
+    if out is not None:
+        if out.device != logits.device:
+            raise ValueError(f"token_agreement: out is on {out.device}, the logits on {logits.device}")
+    else:
+        out = TokenAgreement(positions, ks, device=logits.device)
+    nll, ent, rank, arg, tgt = _token_readout(logits, target, int(ignore_index), "token_agreement")
+    kk = (C.c_int * len(ks))(*ks)
+    check(lib().mas_token_readout_accumulate(_ptr(nll), _ptr(ent), _ptr(arg), _ptr(rank), _ptr(tgt), rows, int(ignore_index), positions, kk,
+                                             len(ks), _ptr(out.nll_sum), _ptr(out.entropy_sum), _ptr(out.count), _ptr(out.hits),
+                                             _ptr(out.rank_hist), _ptr(out.invalid), _stream()), "token_readout_accumulate")
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # VQ-SEG objective: weighted logits-BCE (+ MSE of the sigmoid) (seg_loss.hip)
 # --------------------------------------------------------------------------- #
 _SEG_TARGET_DT = {torch.float32: F32, torch.bfloat16: BF16, torch.uint8: SEG_U8}

@@ -645,3 +645,18 @@ class MakeAScene(nn.Module):
         logits = self._image_logits(text_tokens, seg_tokens, img_tokens)
         logp = -ops.cross_entropy(logits, img_tokens, reduction="none")
         return logp if per_token else logp.sum(1)
+
+    @torch.no_grad()
+    def validation_metrics(self, text_tokens, seg_tokens, img_tokens, *, ks=(1, 5), out=None):
+        """What a validation batch says about the model -> ``mas_hip.tokenmetrics.TokenAgreement`` with one position per image token:
+        negative log-likelihood (``.nll``, ``.perplexity``, ``.bits_per_token``), top-``ks`` accuracy (``.accuracy``), the entropy of the
+        predictive distribution (``.mean_entropy``), the histogram of the true token's rank and the per-position maps
+        (``.grid(32)`` of ``.nll_by_position`` for the 32 x 32 token grid).  The logits are computed for the image positions only and read
+        once by ``ops.token_agreement`` as they are -- fp32, or bf16 under bf16 autocast.  ``out``: the holder of earlier batches, which
+        this batch is added to on the device (no host read): ``acc = None; for t, s, i in loader: acc = model.validation_metrics(t, s, i,
+        out=acc)``.  The model must be in ``eval()`` mode.  A wrapper that only routes ``forward()`` uses
+        ``ops.token_agreement(wrapped(text, seg, img), img, ks=ks, out=acc)``."""
+        if self.training:
+            raise RuntimeError("validation_metrics: measure the frozen model in eval() mode")
+        logits = self._image_logits(text_tokens, seg_tokens, img_tokens)
+        return ops.token_agreement(logits, img_tokens, positions=self.image_length, ks=ks, out=out)

@@ -7,30 +7,18 @@
 //     of the level and the head's gradient seed folded in);
 //   the LPIPS head per level (channel normalisation of both sides, difference, square, lin<k> weights; per-image fixed-order partial
 //     sums), one finalize launch (a tree over the partial sums), and the head's backward for the rec side.
-// These are object.hip's kernels without the atlas: no tile table, no cell record per pixel.  The per-pixel head arithmetic is a
-// second copy of object.hip's.  Activations are bf16 or fp32; arithmetic in fp32; no float atomics anywhere
-// (bitwise repeatable).
-#include "mas_common.h"
+// These are object.hip's kernels without the atlas: no tile table, no cell record per pixel.  What the two files share lives in
+// lpips_core.h, which also says what each keeps for itself and why.  Activations are bf16 or fp32; arithmetic in
+// fp32; no float atomics anywhere (bitwise repeatable).
+#include "lpips_core.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int CP = MAS_OBJ_CANVAS_C;       // canvas channels: RGB + zeros (one 16-byte vector in bf16)
-constexpr int HEAD_PASSES = 4;             // pixel passes of one head block: 8192 / C pixels = HEAD_PASSES * NT / (C / 8)
 constexpr int MAX_LEVELS = 8;
 constexpr long long MAX_PIX = 1LL << 30;   // pixels per image
 constexpr int MAX_BLOCKS = 1 << 18;        // partial sums per image and level: 256 chains of <= 1024 in the finalize
 
-template <typename T> using V8 = typename Vec8<T>::type;
-
 struct Levels { int n; int hw[MAX_LEVELS]; int blocks[MAX_LEVELS]; };
-
-__device__ __forceinline__ float ld_img(const MasFaceImage& im, long long off) {
-    return im.dtype == MAS_BF16 ? (float)reinterpret_cast<const bf16_t*>(im.data)[off] : reinterpret_cast<const float*>(im.data)[off];
-}
-
-__device__ __forceinline__ long long gsize() { return (long long)gridDim.x * NT; }
-__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * NT + threadIdx.x; }
 
 // one thread per canvas pixel: CP channels
 template <typename T>
@@ -144,17 +132,9 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const T* __restrict__ a, c
                 if (arg == me) g[k] += (float)dv[k];
             }
         }
-        V8<T> o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (T)((float)av[k] > 0.0f ? g[k] : 0.0f);
+        const V8<T> o = relu_mask<T>(av, g);
         st8(dy + i * 8, o);
     }
-}
-
-// sum over the G lanes of one pixel group (G a power of two <= 64, groups aligned inside the wave)
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // block j of image b: 8192 / C pixels; G = C / 8 lanes per pixel, 8 channels each
@@ -187,13 +167,7 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(const T* __restrict__ feat
         }
         acc += group_sum(d, G);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.0f;
-        for (int g = 0; g < NG; ++g) s += red[g * G];
-        partial[blockIdx.x] = s;
-    }
+    head_block_sum(acc, red, G, partial + blockIdx.x);
 }
 
 // one work-group per image
@@ -255,19 +229,11 @@ __global__ __launch_bounds__(NT) void head_bwd_kernel(const T* __restrict__ feat
     }
 }
 
-int grid_for(long long n) {
-    long long g = (n + NT - 1) / NT;
-    const long long cap = 16LL * mas_num_cus();
-    return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
-
-bool dt_ok(int dt) { return dt == MAS_F32 || dt == MAS_BF16; }
 bool head_c_ok(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
 
-int check_img(const MasFaceImage* im, const char* what) {
-    if (!im || !im->data) MAS_FAIL(MAS_EINVAL, "%s: null image", what);
-    if (!dt_ok(im->dtype)) MAS_FAIL(MAS_EINVAL, "%s: dtype %d", what, im->dtype);
-    if (im->C != 3 || im->N <= 0 || im->H <= 0 || im->W <= 0) MAS_FAIL(MAS_EINVAL, "%s: need [N>0, 3, H>0, W>0], got C=%d", what, im->C);
+// check_img and this file's bound on the pixels of one image
+int check_image(const MasFaceImage* im, const char* what) {
+    if (int rc = check_img(im, what)) return rc;
     if ((long long)im->H * im->W > MAX_PIX) MAS_FAIL(MAS_EUNSUPPORTED, "%s: more than 2^30 pixels per image", what);
     return MAS_OK;
 }
@@ -292,8 +258,8 @@ int head_blocks(int H, int W, int C) { return (int)(((long long)H * W + 8192 / C
 extern "C" int mas_lpips_pack_fwd(const MasFaceImage* real, const MasFaceImage* fake, const float* shift, const float* scale, void* canvas,
                                   int dtype, void* stream) {
     MAS_ENTER();
-    if (int rc = check_img(real, "lpips_pack_fwd")) return rc;
-    if (int rc = check_img(fake, "lpips_pack_fwd")) return rc;
+    if (int rc = check_image(real, "lpips_pack_fwd")) return rc;
+    if (int rc = check_image(fake, "lpips_pack_fwd")) return rc;
     if (!shift || !scale || !canvas || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "lpips_pack_fwd: null argument or dtype %d", dtype);
     if (real->N != fake->N || real->H != fake->H || real->W != fake->W)
         MAS_FAIL(MAS_EINVAL, "lpips_pack_fwd: real [%d, 3, %d, %d] and fake [%d, 3, %d, %d] differ", real->N, real->H, real->W, fake->N, fake->H,
@@ -308,7 +274,7 @@ extern "C" int mas_lpips_pack_fwd(const MasFaceImage* real, const MasFaceImage* 
 
 extern "C" int mas_lpips_pack_bwd(const void* dcanvas, int dtype, const float* scale, const MasFaceImage* dfake, void* stream) {
     MAS_ENTER();
-    if (int rc = check_img(dfake, "lpips_pack_bwd")) return rc;
+    if (int rc = check_image(dfake, "lpips_pack_bwd")) return rc;
     if (!dcanvas || !scale || !dt_ok(dtype)) MAS_FAIL(MAS_EINVAL, "lpips_pack_bwd: null argument or dtype %d", dtype);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(grid_for((long long)dfake->N * dfake->H * dfake->W));

@@ -14,20 +14,11 @@
 //   the LPIPS head per level (channel normalisation of both sides, squared difference, lin<k> weights, per-crop fixed-order partial
 //     sums), one finalize launch for the crops' values and the loss, and the head's backward for the rec side.
 // Activations are bf16 or fp32; arithmetic in fp32; no float atomics anywhere (bitwise repeatable).
-#include "mas_common.h"
+#include "lpips_core.h"
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int CP = MAS_OBJ_CANVAS_C;       // canvas channels: RGB + zeros (one 16-byte vector in bf16)
 constexpr int LEVELS = 5;
-constexpr int HEAD_PASSES = 4;             // pixel passes of one head block: MAS_OBJ_HEAD_PIX(C) = HEAD_PASSES * NT / (C / 8)
-
-template <typename T> using V8 = typename Vec8<T>::type;
-
-__device__ __forceinline__ float ld_img(const MasFaceImage& im, long long off) {
-    return im.dtype == MAS_BF16 ? (float)reinterpret_cast<const bf16_t*>(im.data)[off] : reinterpret_cast<const float*>(im.data)[off];
-}
 
 // the cell whose level-l valid rectangle holds pixel (y, x) of canvas n, or -1
 __device__ __forceinline__ int cell_at(const MasObjPlan& p, int n, int y, int x, int l) {
@@ -66,9 +57,6 @@ struct DevTab {
     __device__ __forceinline__ int out_cells() const { return max_cells; }
     __device__ __forceinline__ int part_off(int l) const { return off[l]; }
 };
-
-__device__ __forceinline__ long long gsize() { return (long long)gridDim.x * NT; }
-__device__ __forceinline__ long long gtid() { return (long long)blockIdx.x * NT + threadIdx.x; }
 
 // one thread per canvas pixel: CP channels
 template <typename T, typename Tab>
@@ -230,17 +218,9 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const T* __restrict__ a, c
                 if (arg == me) g[k] += (float)dv[k];
             }
         }
-        V8<T> o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (T)((float)av[k] > 0.0f ? g[k] : 0.0f);
+        const V8<T> o = relu_mask<T>(av, g);
         st8(dy + i * 8, o);
     }
-}
-
-// sum over the G lanes of one pixel group (G a power of two <= 64, groups aligned inside the wave)
-__device__ __forceinline__ float group_sum(float v, int G) {
-    for (int m = G >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // per pixel of one cell: the LPIPS head's value; G = C / 8 lanes per pixel, 8 channels each
@@ -288,13 +268,7 @@ __global__ __launch_bounds__(NT) void head_fwd_kernel(const T* __restrict__ feat
         }
         acc += group_sum(d, G);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s = 0.0f;
-        for (int g = 0; g < NG; ++g) s += red[g * G];
-        partial[bid] = s;
-    }
+    head_block_sum(acc, red, G, partial + bid);
 }
 
 template <typename Tab>
@@ -379,25 +353,10 @@ __global__ __launch_bounds__(NT) void head_bwd_kernel(const T* __restrict__ feat
     }
 }
 
-int grid_for(long long n) {
-    long long g = (n + NT - 1) / NT;
-    const long long cap = 16LL * mas_num_cus();
-    return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
-
-bool dt_ok(int dt) { return dt == MAS_F32 || dt == MAS_BF16; }
-
 int check_plan(const MasObjPlan* p, const char* what) {
     if (!p || !p->cells || !p->img_cell0 || !p->tiles || !p->blk0) MAS_FAIL(MAS_EINVAL, "%s: null plan table", what);
     if (p->n_cells <= 0 || p->n_images <= 0 || p->n_canvas <= 0 || p->H <= 0 || p->W <= 0 || p->H % MAS_OBJ_ALIGN || p->W % MAS_OBJ_ALIGN)
         MAS_FAIL(MAS_EINVAL, "%s: bad plan (%d cells, %d images, %d canvases of %d x %d)", what, p->n_cells, p->n_images, p->n_canvas, p->H, p->W);
-    return MAS_OK;
-}
-
-int check_img(const MasFaceImage* im, const char* what) {
-    if (!im || !im->data) MAS_FAIL(MAS_EINVAL, "%s: null image", what);
-    if (!dt_ok(im->dtype)) MAS_FAIL(MAS_EINVAL, "%s: dtype %d", what, im->dtype);
-    if (im->C != 3 || im->N <= 0 || im->H <= 0 || im->W <= 0) MAS_FAIL(MAS_EINVAL, "%s: need [N>0, 3, H>0, W>0], got C=%d", what, im->C);
     return MAS_OK;
 }
 

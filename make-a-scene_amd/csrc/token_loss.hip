@@ -9,52 +9,9 @@
 // one over memory); the two work-group reductions per row are hidden by the four or five work-groups resident per CU.  Longer rows, and rows
 // that are not 16-byte aligned, stream with a per-lane online (m, l) merged in a fixed order, so V is bounded by neither registers nor LDS.
 // The target logit is picked by comparing the running column index with t -- there is no load indexed by a target value.
-#include "mas_common.h"
-#include <math.h>
+#include "token_row_core.h"
 
 namespace {
-
-constexpr int NT = 256, NW = NT / 64;
-constexpr int KMAX = 4;                 // register-resident 16-byte units per lane: V <= 256 * 4 * (8 bf16 | 4 fp32)
-
-template <typename T> struct Unit { static constexpr int N = 16 / (int)sizeof(T); };
-
-template <typename T, int N>
-__device__ __forceinline__ void cvt_unit(const u32x4& raw, float (&v)[N]) {
-    const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = (float)e[i];
-}
-template <typename T, int N>
-__device__ __forceinline__ void ld_unit(const T* p, float (&v)[N]) {
-    const u32x4 raw = *reinterpret_cast<const u32x4*>(p);
-    cvt_unit<T, N>(raw, v);
-}
-template <typename T, int N>
-__device__ __forceinline__ void st_unit(T* p, const float (&v)[N]) {
-    u32x4 raw;
-    T* e = reinterpret_cast<T*>(&raw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) e[i] = (T)v[i];              // the one rounding from fp32
-    *reinterpret_cast<u32x4*>(p) = raw;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ const T* row_ptr(const T* x, long long r, long long inner, long long outer_stride, long long ld) {
-    return x + (r / inner) * outer_stride + (r % inner) * ld;
-}
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename T>
 __global__ __launch_bounds__(NT) void token_ce_fwd_kernel(const T* __restrict__ x, long long rows, int V, long long inner,
@@ -71,12 +28,10 @@ __global__ __launch_bounds__(NT) void token_ce_fwd_kernel(const T* __restrict__ 
             if (tid == 0) { row_loss[r] = 0.0f; stats[2 * r] = 0.0f; stats[2 * r + 1] = 0.0f; }
             continue;
         }
-        const T* xr = row_ptr(x, r, inner, outer_stride, ld);
-        const int nfull = aligned16(xr) ? V / N : 0;             // 16-byte units; the rest of the row goes element by element
-        const int e0 = nfull * N;
+        const auto [xr, nfull, e0] = row_plan(x, r, V, inner, outer_stride, ld);
         const int tc = t >= 0 && t < (long long)V ? (int)t : -1; // the target's column, or no column at all
         float M, l = 0.0f, s = 0.0f, xt = 0.0f;                  // s = sum_j (x_j - M): m - mean_j x_j without the cancellation of sum_j x_j
-        if (nfull <= KMAX * NT && V - e0 <= NT) {
+        if (nfull <= KMAX * NT && V - e0 <= NT) {                // resident: token_readout.hip spells the same test (token_row_core.h)
             // the row fits in registers: exact maximum first, then the sums, from the same registers
             u32x4 raw[KMAX];                                    // as loaded: 4 VGPRs per unit, converted at each use
             float vt = 0.0f;
@@ -94,11 +49,8 @@ __global__ __launch_bounds__(NT) void token_ce_fwd_kernel(const T* __restrict__ 
             }
             const bool has_t = tid < V - e0;
             if (has_t) { vt = (float)xr[e0 + tid]; mx = fmaxf(mx, vt); }
-            mx = wave_max(mx);
-            if (lane == 0) s_max[wave] = mx;
-            __syncthreads();
-            M = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-            const float ms = M == -INFINITY ? 0.0f : M;
+            M = row_max(mx, s_max, lane, wave);
+            const float ms = exp_shift(M);
 #pragma unroll
             for (int k = 0; k < KMAX; ++k) {
                 const int u = k * NT + tid;
@@ -128,12 +80,10 @@ __global__ __launch_bounds__(NT) void token_ce_fwd_kernel(const T* __restrict__ 
             for (int u = tid; u < nfull; u += NT) {
                 float v[N];
                 ld_unit<T, N>(xr + (size_t)u * N, v);
-                float um = v[0];
-#pragma unroll
-                for (int e = 1; e < N; ++e) um = fmaxf(um, v[e]);
+                const float um = unit_max(v);
                 if (ni == 0) ci = v[0];
-                if (um > mi) { li *= __expf(mi - um); mi = um; }
-                const float ms = mi == -INFINITY ? 0.0f : mi;
+                if (um > mi) { li *= __expf(mi - um); mi = um; }   // the online step: token_readout.hip has the same one, with its a
+                const float ms = exp_shift(mi);
 #pragma unroll
                 for (int e = 0; e < N; ++e) {
                     li += __expf(v[e] - ms);
@@ -147,17 +97,14 @@ __global__ __launch_bounds__(NT) void token_ce_fwd_kernel(const T* __restrict__ 
                 const float a = (float)xr[j];
                 if (ni == 0) ci = a;
                 if (a > mi) { li *= __expf(mi - a); mi = a; }
-                const float ms = mi == -INFINITY ? 0.0f : mi;
+                const float ms = exp_shift(mi);
                 li += __expf(a - ms);
                 si += a - ci;
                 if (j == tc) xt = a;
                 ni += 1;
             }
-            const float mx = wave_max(mi);
-            if (lane == 0) s_max[wave] = mx;
-            __syncthreads();
-            M = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
-            const float ms = M == -INFINITY ? 0.0f : M;
+            M = row_max(mi, s_max, lane, wave);
+            const float ms = exp_shift(M);
             l = ni ? li * __expf(mi - ms) : 0.0f;                // (mi == M: exp(0) = 1 exactly)
             s = ni ? si - (float)ni * (ms - ci) : 0.0f;
         }
@@ -231,8 +178,7 @@ __global__ __launch_bounds__(NT) void token_ce_bwd_kernel(const T* __restrict__ 
         float w = grad_per_row ? grad[r] : grad[0];
         if (loss_count) w = w / loss_count[1];                   // mean: the count the forward left on the device
         const float m = stats[2 * r], logl = stats[2 * r + 1];
-        const T* xr = row_ptr(x, r, inner, outer_stride, ld);
-        const int nfull = aligned16(xr) ? V / N : 0;
+        const auto [xr, nfull, e0] = row_plan(x, r, V, inner, outer_stride, ld);   // (e0: not needed here)
         for (int u0 = 0; u0 < nfull; u0 += KMAX * NT) {          // KMAX loads in flight per lane
             float v[KMAX][N];
 #pragma unroll
@@ -264,29 +210,16 @@ __global__ __launch_bounds__(NT) void token_ce_bwd_kernel(const T* __restrict__ 
     }
 }
 
-int ce_check(const char* what, const void* logits, int dtype, long long rows, int V, long long inner, long long outer_stride, long long ld,
-             const void* target, float eps) {
-    if (!logits || !target) MAS_FAIL(MAS_EINVAL, "%s: null argument", what);
-    if (rows <= 0 || V <= 0 || inner <= 0) MAS_FAIL(MAS_EINVAL, "%s: rows=%lld V=%d inner=%lld must be positive", what, rows, V, inner);
-    if (outer_stride < 0 || ld < 0) MAS_FAIL(MAS_EINVAL, "%s: negative stride (outer_stride=%lld ld=%lld)", what, outer_stride, ld);
-    if (!(eps >= 0.0f && eps <= 1.0f)) MAS_FAIL(MAS_EINVAL, "%s: label_smoothing=%g outside [0, 1]", what, (double)eps);
-    if (dtype != MAS_BF16 && dtype != MAS_F32) MAS_FAIL(MAS_EUNSUPPORTED, "%s: dtype %d (fp32 / bf16 logits)", what, dtype);
-    return MAS_OK;
-}
-
-// one work-group per row; past 2^20 rows the work-groups walk the rows with the grid as stride
-inline unsigned ce_grid(long long rows) { return (unsigned)(rows < (1LL << 20) ? rows : (1LL << 20)); }
-
 }  // namespace
 
 extern "C" int mas_token_ce_fwd(const void* logits, int dtype, long long rows, int V, long long inner, long long outer_stride, long long ld,
                                 const int64_t* target, long long ignore_index, float label_smoothing, float* row_loss, float* stats,
                                 void* stream) {
     MAS_ENTER();
-    if (int rc = ce_check("token_ce_fwd", logits, dtype, rows, V, inner, outer_stride, ld, target, label_smoothing)) return rc;
+    if (int rc = row_check("token_ce_fwd", logits, dtype, rows, V, inner, outer_stride, ld, target, label_smoothing)) return rc;
     if (!row_loss || !stats) MAS_FAIL(MAS_EINVAL, "token_ce_fwd: null argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(ce_grid(rows)), block(NT);
+    const dim3 grid(row_grid(rows)), block(NT);
     const long long* tg = reinterpret_cast<const long long*>(target);
     if (dtype == MAS_BF16)
         hipLaunchKernelGGL((token_ce_fwd_kernel<bf16_t>), grid, block, 0, s, (const bf16_t*)logits, rows, V, inner, outer_stride, ld, tg,
@@ -316,13 +249,13 @@ extern "C" int mas_token_ce_bwd(const void* logits, int dtype, long long rows, i
                                 const int64_t* target, long long ignore_index, float label_smoothing, const float* stats,
                                 const float* grad, const float* loss_count, int reduction, void* dx, void* stream) {
     MAS_ENTER();
-    if (int rc = ce_check("token_ce_bwd", logits, dtype, rows, V, inner, outer_stride, ld, target, label_smoothing)) return rc;
+    if (int rc = row_check("token_ce_bwd", logits, dtype, rows, V, inner, outer_stride, ld, target, label_smoothing)) return rc;
     if (!stats || !grad || !dx) MAS_FAIL(MAS_EINVAL, "token_ce_bwd: null argument");
     if (reduction != MAS_CE_NONE && reduction != MAS_CE_MEAN && reduction != MAS_CE_SUM)
         MAS_FAIL(MAS_EINVAL, "token_ce_bwd: reduction %d", reduction);
     if (reduction == MAS_CE_MEAN && !loss_count) MAS_FAIL(MAS_EINVAL, "token_ce_bwd: the mean needs the {loss, count} pair of token_ce_reduce");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid(ce_grid(rows)), block(NT);
+    const dim3 grid(row_grid(rows)), block(NT);
     const long long* tg = reinterpret_cast<const long long*>(target);
     const float* lc = reduction == MAS_CE_MEAN ? loss_count : nullptr;
     const int per_row = reduction == MAS_CE_NONE ? 1 : 0;

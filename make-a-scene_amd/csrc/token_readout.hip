@@ -12,56 +12,13 @@
 // over the row (16 .. 64 KB, read a moment ago by the same work-group: it comes from L2).
 // x_t is picked by comparing the running column with t: no load is indexed by a target value.  No atomics in token_readout; integer
 // atomics only (exact in any order) for the two global tallies of token_readout_accumulate.
-// The row walk repeats token_loss.hip's (Unit, cvt_unit, row_ptr, the resident / streaming split): DESIGN 2.19 names the shared header
-// that a later change would make of the two.
-#include "mas_common.h"
+// The row walk's parts (Unit, cvt_unit, row_ptr, the row plan, the exchange of maxima, the wave reductions) are token_loss.hip's, from
+// token_row_core.h; the loops over them are this kernel's own.
+#include "token_row_core.h"
 #include <float.h>
 #include <limits.h>
-#include <math.h>
 
 namespace {
-
-constexpr int NT = 256, NW = NT / 64;
-constexpr int KMAX = 4;                 // register-resident 16-byte units per lane: V <= 256 * 4 * (8 bf16 | 4 fp32)
-
-template <typename T> struct Unit { static constexpr int N = 16 / (int)sizeof(T); };
-
-template <typename T, int N>
-__device__ __forceinline__ void cvt_unit(const u32x4& raw, float (&v)[N]) {
-    const T* e = reinterpret_cast<const T*>(&raw);
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = (float)e[i];
-}
-
-template <typename T>
-__device__ __forceinline__ const T* row_ptr(const T* x, long long r, long long inner, long long outer_stride, long long ld) {
-    return x + (r / inner) * outer_stride + (r % inner) * ld;
-}
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-// how many ACTIVE lanes of the wave hold the predicate: one compare into a lane mask and two scalar instructions.  The callers add it up in
-// every active lane; lane 0 has the wave's smallest row index and is active whenever any lane of its wave is, so ITS total is the wave's.
-__device__ __forceinline__ int wave_count(bool p) { return __popcll(__ballot(p)); }
 
 // second pass, one element against the row's maximum M: l += e, a += e d with d = x - M, e = exp(d).  An entry of -inf has e = 0 and its d
 // is clamped to -FLT_MAX inside the product, so 0 * inf is never formed; a NaN keeps e = NaN and poisons l, which is how the row is found.
@@ -109,12 +66,10 @@ __global__ __launch_bounds__(NT) void token_readout_kernel(const T* __restrict__
             }
             continue;
         }
-        const T* xr = row_ptr(x, r, inner, outer_stride, ld);
-        const int nfull = aligned16(xr) ? V / N : 0;             // 16-byte units; the rest of the row goes element by element
-        const int e0 = nfull * N;
+        const auto [xr, nfull, e0] = row_plan(x, r, V, inner, outer_stride, ld);
         const int tc = (int)t;
         const int tu = tc < e0 ? tc / N : -1, te = tc % N;       // the unit that holds column t and the element inside it (no unit: the tail)
-        const bool resident = nfull <= KMAX * NT && V - e0 <= NT;
+        const bool resident = nfull <= KMAX * NT && V - e0 <= NT;   // token_loss.hip spells the same test (token_row_core.h)
         float mx = -INFINITY, xt = 0.0f;
         int mcol = INT_MAX;                                      // where this lane first met its maximum: a unit's first column, or a tail column
         bool munit = false;                                      // ... and which of the two
@@ -132,9 +87,7 @@ __global__ __launch_bounds__(NT) void token_readout_kernel(const T* __restrict__
                     raw[k] = *reinterpret_cast<const u32x4*>(xr + (size_t)u * N);
                     float v[N];
                     cvt_unit<T, N>(raw[k], v);
-                    float um = v[0];
-#pragma unroll
-                    for (int e = 1; e < N; ++e) um = fmaxf(um, v[e]);
+                    const float um = unit_max(v);
                     if (um > mx) { mx = um; mcol = u * N; munit = true; }
                     if (u == tu) {
 #pragma unroll
@@ -152,20 +105,18 @@ __global__ __launch_bounds__(NT) void token_readout_kernel(const T* __restrict__
             for (int u = tid; u < nfull; u += NT) {
                 float v[N];
                 cvt_unit<T, N>(*reinterpret_cast<const u32x4*>(xr + (size_t)u * N), v);
-                float um = v[0];
-#pragma unroll
-                for (int e = 1; e < N; ++e) um = fmaxf(um, v[e]);
+                const float um = unit_max(v);
                 if (u == tu) {
 #pragma unroll
                     for (int e = 0; e < N; ++e) if (e == te) xt = v[e];
                 }
-                if (um > mx) {                                   // the lane's maximum moves: rescale what it holds (f = 0 from mx = -inf)
+                if (um > mx) {       // the lane's maximum moves: rescale what it holds (f = 0 from mx = -inf); token_loss.hip's step for (m, l)
                     const float f = __expf(mx - um);
                     ai = f > 0.0f ? f * (ai + (mx - um) * li) : 0.0f;
                     li *= f;
                     mx = um; mcol = u * N; munit = true;
                 }
-                const float ms = mx == -INFINITY ? 0.0f : mx;
+                const float ms = exp_shift(mx);
 #pragma unroll
                 for (int e = 0; e < N; ++e) sum_elem(v[e], ms, li, ai);
             }
@@ -179,15 +130,12 @@ __global__ __launch_bounds__(NT) void token_readout_kernel(const T* __restrict__
                     li *= f;
                     mx = a; mcol = j; munit = false;
                 }
-                sum_elem(a, mx == -INFINITY ? 0.0f : mx, li, ai);
+                sum_elem(a, exp_shift(mx), li, ai);
             }
         }
         // exchange 1: the row's maximum and x_t (the one lane that met column t writes it)
         if ((tc < e0 ? tc / N : tc - e0) % NT == tid) s_xt = xt;  // unit u and tail element e0 + j belong to lanes u % 256 and j % 256
-        const float wm = wave_max(mx);
-        if (lane == 0) s_max[wave] = wm;
-        __syncthreads();
-        const float M = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+        const float M = row_max(mx, s_max, lane, wave);
         const float XT = s_xt;
         // the first index of the maximum: a lane whose maximum is the row's looks for the element inside the unit it remembered (its first
         // unit with that value: units and tail come in increasing columns within a lane); the smallest such column wins in exchange 2
@@ -320,20 +268,14 @@ __global__ __launch_bounds__(NT) void token_readout_accumulate_kernel(const floa
     }
 }
 
-// one work-group per row; past 2^20 rows the work-groups walk the rows with the grid as stride
-inline unsigned row_grid(long long rows) { return (unsigned)(rows < (1LL << 20) ? rows : (1LL << 20)); }
-
 }  // namespace
 
 extern "C" int mas_token_readout(const void* logits, int dtype, long long rows, int V, long long inner, long long outer_stride, long long ld,
                                  const int64_t* target, long long ignore_index, float* nll, float* entropy, int32_t* argmax, int32_t* rank,
                                  void* stream) {
     MAS_ENTER();
-    if (rows <= 0 || V <= 0 || inner <= 0)
-        MAS_FAIL(MAS_EINVAL, "token_readout: rows=%lld V=%d inner=%lld must be positive", rows, V, inner);
-    if (outer_stride < 0 || ld < 0) MAS_FAIL(MAS_EINVAL, "token_readout: negative stride (outer_stride=%lld ld=%lld)", outer_stride, ld);
-    if (dtype != MAS_BF16 && dtype != MAS_F32) MAS_FAIL(MAS_EUNSUPPORTED, "token_readout: dtype %d (fp32 / bf16 logits)", dtype);
-    if (!logits || !target || !nll || !entropy || !argmax || !rank) MAS_FAIL(MAS_EINVAL, "token_readout: null argument");
+    if (int rc = row_check("token_readout", logits, dtype, rows, V, inner, outer_stride, ld, target, 0.0f)) return rc;
+    if (!nll || !entropy || !argmax || !rank) MAS_FAIL(MAS_EINVAL, "token_readout: null argument");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(row_grid(rows)), block(NT);
     const long long* tg = reinterpret_cast<const long long*>(target);

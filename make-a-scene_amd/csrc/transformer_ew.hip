@@ -6,6 +6,7 @@
 // [B, S, 4d] tensor, and every LayerNorm is bracketed by dtype-cast copies; here each is one pass with
 // 16-byte loads/stores and fp32 arithmetic, bf16 or fp32 storage on either side.
 #include "mas_common.h"
+#include "mas_wave.h"
 #include <math.h>
 
 namespace {
@@ -131,14 +132,8 @@ __global__ __launch_bounds__(NT) void gelu_bwd_kernel(const T* __restrict__ x, c
 // ---------------------------------------------------------------------------------------------------------
 // LayerNorm.  One wave per row; a lane owns the same columns of every row (column = (k*64 + lane)*VEC + e for
 // k < KMAX), the row lives in registers, statistics are exact two-pass (mean, then centred sum of squares) in
-// fp32 with wave-level DPP/permute reductions -- no LDS, no second read of x.
+// fp32 with wave-level DPP/permute reductions (wave_sum, mas_wave.h) -- no LDS, no second read of x.
 constexpr int LN_KMAX = 4;              // D <= 64 * VEC * 4  (2048 bf16 / 1024 fp32 columns)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <typename TI, typename TO>
 __global__ __launch_bounds__(NT) void layernorm_fwd_kernel(const TI* __restrict__ x, const float* __restrict__ gamma,

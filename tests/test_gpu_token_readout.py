@@ -133,6 +133,51 @@ def test_outer_stride_past_2_31(dtype):
     del view, got
 
 
+# (dtype, V, ld or None for a contiguous [6, V], the branch of the row walk it reaches); "slice": the [2, 3, V] slice of [2, 5, V]
+SAME_WALK = [
+    (torch.bfloat16, 8, None, "one unit, no tail"),
+    (torch.bfloat16, 8192, None, "the last fully resident row"),
+    (torch.bfloat16, 8200, None, "first streaming row, units only"),
+    (torch.bfloat16, 2049, 2056, "resident with a one-element tail"),
+    (torch.bfloat16, 2049, None, "ld = 2049: unaligned rows stream element by element"),
+    (torch.float32, 4096, None, "resident limit"),
+    (torch.float32, 4100, None, "streaming"),
+    (torch.float32, 1003, 1004, "resident, three-element tail"),
+    (torch.bfloat16, 2049, "slice", "outer_stride != inner * ld"),
+    (torch.float32, 2049, "slice", "outer_stride != inner * ld"),
+]
+
+
+@pytest.mark.parametrize("dtype,v,ld,branch", SAME_WALK, ids=["%s-V%d-%s" % (str(c[0])[6:], c[1], c[2]) for c in SAME_WALK])
+def test_nll_is_the_loss_row_value_bit_for_bit(dtype, v, ld, branch):
+    """the read-out's nll and cross_entropy(reduction="none", label_smoothing=0) walk a row with the same code (csrc/token_row_core.h) and
+    form m, l and (m - x_t) + log l with the same fp32 operations in the same order: equal bits, not close values.  Finite logits at two
+    scales, valid targets and one ignored row (both give 0)."""
+    from mas_hip import ops
+    dev = _dev()
+    for scale in (1.0, 30.0):
+        g = torch.Generator().manual_seed(1000 * v + int(scale))
+        x = (torch.randn(6, v, generator=g) * scale).to(dev).to(dtype)
+        t = torch.randint(0, v, (6,), generator=g).to(dev)
+        t[4] = R.IGNORE
+        if ld == "slice":
+            base = torch.full((2, 5, v), 777.0, dtype=dtype, device=dev)
+            base[:, 1:4] = x.view(2, 3, v)
+            view, tt = base[:, 1:4], t.view(2, 3)
+            assert not view.is_contiguous() and view.stride(0) != view.shape[1] * view.stride(1)
+        elif ld is not None:
+            buf = torch.zeros(1, 6, ld, dtype=dtype, device=dev)
+            buf[0, :, :v] = x
+            view, tt = buf[:, :, :v], t.view(1, 6)
+            assert not view.is_contiguous() and view.stride(1) == ld and (ld * view.element_size()) % 16 == 0
+        else:
+            view, tt = x, t
+        nll = ops.token_readout(view, tt, ignore_index=R.IGNORE)[0]
+        loss = ops.cross_entropy(view, tt, reduction="none", ignore_index=R.IGNORE, label_smoothing=0.0)
+        assert nll.shape == tt.shape and torch.isfinite(nll).all() and float(nll.reshape(-1)[4]) == 0.0
+        assert torch.equal(nll, loss), (branch, scale, (nll - loss).abs().max().item())
+
+
 def _acc_numpy(acc):
     return {k: getattr(acc, k).cpu().numpy() for k in ACC_FIELDS}
 

@@ -31,8 +31,9 @@ def test_entries_are_declared_exported_and_bound():
         assert hasattr(raw, name), name + " is not exported"
         assert name in mas_hip.EXPORTS and getattr(L, name).argtypes == mas_hip._SIGNATURES[name][1]
     assert (mas_hip.TOKEN_MAX_KS, mas_hip.TOKEN_RANK_BINS) == (8, 33) == (R.MAX_KS, R.RANK_BINS)
-    src = open(os.path.join(ROOT, "make-a-scene_amd", "csrc", "token_readout.hip")).read()
-    assert "asm" not in re.sub(r"//[^\n]*", "", src)             # no inline assembly in this file
+    for name in ("token_readout.hip", "token_row_core.h", "mas_wave.h"):   # the file and the headers that hold its row walk
+        src = open(os.path.join(ROOT, "make-a-scene_amd", "csrc", name)).read()
+        assert "asm" not in re.sub(r"//[^\n]*", "", src), name   # no inline assembly in this file
 
 
 def test_bad_arguments_come_back_as_codes_before_any_launch():
